@@ -9,8 +9,16 @@ bytes processed by seal and open on all ranks / wall time of the timed region
 (max over ranks), in GiB/s.  Weak scaling: each rank owns its own 2^20 records
 (seq r*2^20 + i); there is no collective in the data path.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
         torchrun --nproc-per-node N bench.py --gpus N ...   (N > 1)
+A plain run sets up, warms up, times the K steps and prints the headline line
+(value, ms_per_step, the configuration).  --full adds every other measurement
+and check to the line: event-timed kernel times and rooflines, the energy
+window, the round-trip and oracle checks of the last step, the CPU baseline,
+the C2 sub-record, the copy-inclusive record path and (N > 1) the RCCL
+scatter/gather.  The options that shape those legs only matter with --full.
+--dump-outputs DIR writes what the last timed step left in the caller's
+buffers (dump_outputs) as DIR/<name>.npy.
 With --gpus N > 1 and no launcher environment (WORLD_SIZE unset) bench.py
 starts the N rank processes itself (one per GPU, 127.0.0.1 rendezvous)
 before anything touches a GPU, and exits with the worst rank's code.
@@ -40,6 +48,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline figure (kernel times, rooflines, "
+                         "energy, round-trip and oracle checks, CPU baseline, C2 sub-record, record path, "
+                         "scatter/gather); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (sealed records, opened records, tags, "
+                         "status; seeded samples where large) as DIR/<name>.npy")
     ap.add_argument("--workload", choices=["c1", "c2"], default="c1",
                     help="c1: 16 KiB records, one key (the metric's config); c2: Zipf 64 B-16 KiB, 256 keys")
     ap.add_argument("--records", type=int, default=1 << 20, help="records per GPU (C1: 2^20)")
@@ -753,6 +768,73 @@ def make_workload(args, workload, count, seq0, dev, stream):
     return w
 
 
+DUMP_TAG_RECORDS = 1 << 20    # tags and status bytes: every record up to this many, a seeded sample beyond
+DUMP_SAMPLE_RECORDS = 120     # whole records (sealed and opened) in the seeded sample ...
+DUMP_SAMPLE_BYTES = 1 << 22   # ... and the most bytes they may hold (4 bytes of .npy per byte)
+
+
+def dump_outputs(dirpath, w, rank, world):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step, as float arrays (every value is a byte, or a little-endian 32-bit
+    word of a tag, and exact), under 64 MB in all at the default size:
+
+    * tags.npy (float64, m x 4): the Poly1305 tag of each sealed record as four
+      32-bit words; status.npy (float32, m): each record's open status.  Every
+      record in order when the batch has at most DUMP_TAG_RECORDS of them,
+      else a seeded sample whose indices are tag_records.npy (float64).
+    * sample_records.npy (float64): the indices of a seeded sample of records
+      (the first and, unless the byte cap cuts the sample short, the last
+      included); sealed_sample.npy / opened_sample.npy
+      (float32): those records' sealed bytes (ct || tag) and the plaintext the
+      open wrote back, one row per record (C1) or back to back (C2).
+
+    The inputs and both samples depend only on the arguments, so two builds
+    run with the same arguments are compared file by file.  Ranks other than
+    the only one write <name>_rank<r>.npy."""
+    import numpy as np
+    import torch
+
+    count, n, lay = w["count"], w["n"], w["lay"]
+    ct, back, status = w["ct"], w["back"], w["status"]
+    dev = ct.device
+    rng = np.random.default_rng(SEED)
+
+    def pick(k):
+        if count <= k:
+            return np.arange(count, dtype=np.int64)
+        some = rng.choice(count, size=k - 2, replace=False)
+        return np.unique(np.concatenate([[0, count - 1], some])).astype(np.int64)
+
+    t_idx = pick(DUMP_TAG_RECORDS)
+    r_idx = pick(DUMP_SAMPLE_RECORDS)
+    t_dev = torch.from_numpy(t_idx).to(dev)
+    if lay is None:
+        r_idx = r_idx[:max(1, DUMP_SAMPLE_BYTES // (2 * n + 16))]
+        r_dev = torch.from_numpy(r_idx).to(dev)
+        rows = ct.view(count, w["cs"])
+        tags = rows[t_dev, n:n + 16]
+        sealed = rows[r_dev, :n + 16]
+        opened = back.view(count, n)[r_dev]
+    else:
+        lens, in_off, out_off = lay.lens.astype(np.int64), lay.in_off.astype(np.int64), lay.out_off.astype(np.int64)
+        r_idx = r_idx[np.cumsum(2 * lens[r_idx] + 16) <= DUMP_SAMPLE_BYTES]
+        tag_at = torch.from_numpy(out_off[t_idx] + lens[t_idx]).to(dev)
+        tags = ct[(tag_at.view(-1, 1) + torch.arange(16, device=dev).view(1, 16)).view(-1)].view(-1, 16)
+        sealed = torch.cat([ct[int(out_off[i]):int(out_off[i] + lens[i]) + 16] for i in r_idx])
+        opened = torch.cat([back[int(in_off[i]):int(in_off[i] + lens[i])] for i in r_idx])
+    out = {"tags": np.ascontiguousarray(tags.cpu().numpy()).view("<u4").astype(np.float64),
+           "status": status[t_dev].cpu().numpy().astype(np.float32),
+           "sample_records": r_idx.astype(np.float64),
+           "sealed_sample": sealed.cpu().numpy().astype(np.float32),
+           "opened_sample": opened.cpu().numpy().astype(np.float32)}
+    if len(t_idx) < count:
+        out["tag_records"] = t_idx.astype(np.float64)
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in out.items():
+        np.save(d / (f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"), a)
+
+
 def energy_fields(mon_e, tm_e, count, dom):
     """Energy per record at the power cap: the board power
     averaged over the second half of a >= --energy-seconds window of event-timed
@@ -773,10 +855,12 @@ def energy_fields(mon_e, tm_e, count, dom):
             "note": "board power (sysfs, mean of the window's second half) x event-timed launch time / records"}
 
 
-def run_measurement(args, w, steps, warmup, dist, backend, rank, local, local_dev, dev, stream, sampler, lib, bus):
-    """Warm-up, the timed region (barrier + sync on both sides, MAX over ranks),
-    event-timed kernel times right after it, an energy window, and the checks of
-    the last step (outside every timed region)."""
+def run_measurement(args, w, steps, warmup, dist, backend, rank, local, local_dev, dev, stream, sampler, lib, bus,
+                    dump_dir=None):
+    """Warm-up, the timed region (barrier + sync on both sides, MAX over ranks)
+    and, with --dump-outputs, the last step's outputs; a plain run ends there.
+    --full: event-timed kernel times right after it, an energy window, and the
+    checks of the last step (outside every timed region)."""
     import ctypes as C
 
     import torch
@@ -797,6 +881,10 @@ def run_measurement(args, w, steps, warmup, dist, backend, rank, local, local_de
     elapsed = shard.timed(dist, step, steps, sync=torch.cuda.synchronize,
                           device=dev if backend == "nccl" else None)
     t_region1 = time.perf_counter()
+    if dump_dir:
+        dump_outputs(dump_dir, w, rank, dist.get_world_size() if dist else 1)
+    if not args.full:
+        return {"elapsed": elapsed}
 
     # per-kernel device time with HIP events on the launch stream, right after
     # the timed steps while the GPU is still at its steady-state clock (round 2
@@ -857,14 +945,26 @@ def run_measurement(args, w, steps, warmup, dist, backend, rank, local, local_de
             "correct": correct, "ranks": ranks, "flags": flags}
 
 
-def kernel_fields(args, w, r, steps, world, dist, backend, dev, lib, props):
-    """value, the dominant launch's HBM roofline (PMC traffic of the same build
-    and layout), its VALU issue bound and the event-timed kernel times."""
-    count, n, tm, mon = w["count"], w["n"], r["tm"], r["mon"]
+def headline_fields(args, w, r, steps, world, dist, backend, dev, lib):
+    """What the timed region alone gives: value, ms_per_step, records per
+    second, and the loaded library's identity."""
+    from suruga_amd import batch as B
+
     total_payload_per_step = w["payload_per_step"] * world if not args.strong else int(
         sum_over_ranks(dist, w["payload_per_step"], dev if backend == "nccl" else None))
-    value = total_payload_per_step * steps / r["elapsed"] / 2**30
-    ms_per_step = r["elapsed"] / steps * 1e3
+    return {"value": total_payload_per_step * steps / r["elapsed"] / 2**30,
+            "ms_per_step": r["elapsed"] / steps * 1e3,
+            "build": lib.sg_build_info().decode(), "provenance": B.N.loaded_info(),
+            "records_per_s": round((args.records if args.strong else w["count"] * world) * steps / r["elapsed"], 1)}
+
+
+def kernel_fields(args, w, r, steps, world, dist, backend, dev, lib, props):
+    """--full: headline_fields plus the dominant launch's HBM roofline (PMC
+    traffic of the same build and layout), its VALU issue bound and the
+    event-timed kernel times."""
+    count, n, tm, mon = w["count"], w["n"], r["tm"], r["mon"]
+    head = headline_fields(args, w, r, steps, world, dist, backend, dev, lib)
+    ms_per_step, build, provenance = head["ms_per_step"], head["build"], head["provenance"]
     # dominant kernel's roofline (algorithmic bytes per launch, SURVEY.md 8d):
     # seal R+W = 2n + 69 per record, open = 2n + 70
     dom = "open" if tm["open_ms"] >= tm["seal_ms"] else "seal"
@@ -878,7 +978,6 @@ def kernel_fields(args, w, r, steps, world, dist, backend, dev, lib, props):
     traffic, traffic_src, tj = None, None, None
     # the PMC traffic summary of this exact kernel build and workload (the newest
     # profiles/traffic_*.json whose build string and record shape match)
-    build = lib.sg_build_info().decode()
     cands = [Path(args.traffic)] if args.traffic else sorted(
         (ROOT / "profiles").glob("traffic_*.json"), key=lambda q: q.stat().st_mtime, reverse=True)
     for q in cands:
@@ -895,9 +994,6 @@ def kernel_fields(args, w, r, steps, world, dist, backend, dev, lib, props):
                            "and record layout in a separate profiling run (not this run)")
             break
     # the static ISA census of the loaded library's sources (tools/isa_census.py)
-    from suruga_amd import batch as B
-
-    provenance = B.N.loaded_info()
     isa = None
     isa_path = ROOT / "profiles" / f"isa_{provenance['source_hash']}.json"
     if isa_path.exists():
@@ -925,7 +1021,7 @@ def kernel_fields(args, w, r, steps, world, dist, backend, dev, lib, props):
                        "keying launches are inside the seal/open window")
     energy = energy_fields(r["mon_e"], r["tm_e"], count, dom) if r["mon_e"] is not None else None
     return {
-        "value": value, "ms_per_step": ms_per_step, "dom": dom, "build": build, "provenance": provenance,
+        **head, "dom": dom,
         "sclk": sclk,
         "roofline": {"bound": "hbm", "kernel": dom_kernel,
                      "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -942,7 +1038,18 @@ def kernel_fields(args, w, r, steps, world, dist, backend, dev, lib, props):
                       "note": "HIP events on the launch stream over steps run right after the timed region; "
                               + keying_note},
         "energy": energy,
-        "records_per_s": round((args.records if args.strong else count * world) * steps / r["elapsed"], 1),
+    }
+
+
+def headline_line(args, world, cfg, kf):
+    """The fields every run prints (kf: headline_fields or kernel_fields)."""
+    return {
+        "metric": METRIC, "value": round(kf["value"], 3), "unit": "GiB/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(kf["ms_per_step"], 4),
+        "higher_is_better": True, "scaling": "strong" if args.strong else "weak", "vs_baseline": None, "dtype": "u32",
+        "data": "synthetic (splitmix64 records generated on device)",
+        "config": dict(cfg, parallelism=f"record-shard x{world}", kernels=kf["build"], library=kf["provenance"]),
+        "records_per_s": kf["records_per_s"], "full": args.full,
     }
 
 
@@ -990,6 +1097,16 @@ def main():
     stream = torch.cuda.Stream(dev)
     w = make_workload(args, args.workload, count, seq0, dev, stream)
     lib = B.N.load()
+    if not args.full:  # a plain run: the timed steps, their outputs if asked for, the headline line
+        r = run_measurement(args, w, args.steps, args.warmup, dist, backend, rank, local, local_dev, dev, stream,
+                            None, lib, None, args.dump_outputs)
+        kf = headline_fields(args, w, r, args.steps, world, dist, backend, dev, lib)
+        if rank == 0:
+            print(json.dumps(headline_line(args, world, w["cfg"], kf)), flush=True)
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # the shader clock and board power (sysfs, plain reads on a background
     # thread from the warm-up to the end of the last measurement): the
     # issue-bound roofline is priced at the mean clock of the event-timed steps
@@ -999,7 +1116,7 @@ def main():
     bus = f"{props.pci_domain_id:04x}:{props.pci_bus_id:02x}:{props.pci_device_id:02x}.0"
     sampler = devmon.Sampler(bus).start()
     r = run_measurement(args, w, args.steps, args.warmup, dist, backend, rank, local, local_dev, dev, stream,
-                        sampler, lib, bus)
+                        sampler, lib, bus, args.dump_outputs)
     kf = kernel_fields(args, w, r, args.steps, world, dist, backend, dev, lib, props)
     correct, ranks, flags, exact = r["correct"], r["ranks"], r["flags"], r["exact"]
 
@@ -1052,11 +1169,7 @@ def main():
     sampler.stop()
     if rank == 0:
         line = {
-            "metric": METRIC, "value": round(kf["value"], 3), "unit": "GiB/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(kf["ms_per_step"], 4),
-            "higher_is_better": True, "scaling": "strong" if args.strong else "weak", "vs_baseline": None, "dtype": "u32",
-            "data": "synthetic (splitmix64 records generated on device)",
-            "config": dict(cfg1, parallelism=f"record-shard x{world}", kernels=kf["build"], library=kf["provenance"]),
+            **headline_line(args, world, cfg1, kf),
             "roofline": kf["roofline"],
             "valu_roofline": kf["valu_roofline"],
             "sclk_mhz": kf["sclk"],
@@ -1065,7 +1178,6 @@ def main():
             "energy": kf["energy"],
             "device_monitor": r["mon"],
             "kernel_ms": kf["kernel_ms"],
-            "records_per_s": kf["records_per_s"],
             "cpu_baseline": cpu,
         }
         line.update(correctness_fields(r["correct"], ranks, flags, exact))

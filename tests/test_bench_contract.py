@@ -16,6 +16,8 @@ from conftest import ROOT
 
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
         "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"}
+# the side measurements and checks of the line are behind --full
+FULL = [sys.executable, str(ROOT / "bench.py"), "--full"]
 
 
 def _port():
@@ -37,8 +39,8 @@ def test_bench_help():
 
 @pytest.mark.gpu
 def test_bench_single_gpu_small(gpu):
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--records", "4096", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--record-path-bytes", str(24 << 20)], capture_output=True, text=True,
+    p = subprocess.run(FULL + ["--records", "4096", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                              "--record-path-bytes", str(24 << 20)], capture_output=True, text=True,
                        timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     j = _last_json(p.stdout)
@@ -66,13 +68,129 @@ def test_bench_single_gpu_small(gpu):
         assert e["board_power_w"] > 0 and e["seal_uj_per_record"] > 0 and e["open_uj_per_record"] > 0
 
 
+def test_bench_help_names_full_and_dump_outputs():
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_outputs(gpu, oracle, tmp_path):
+    """A plain run (no --full) times --steps steps and prints the headline line
+    alone: none of the side measurements or checks.  --dump-outputs writes the
+    last step's outputs as float .npy files: every tag and status byte, and a
+    seeded sample of sealed and opened records, which equal the oracle's."""
+    import numpy as np
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    n, count = 16384, 4096
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--records", str(count), "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True,
+                       timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    j = _last_json(p.stdout)
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus",
+            "config"} <= set(j)
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["full"] is False and j["value"] > 0 and j["ms_per_step"] > 0
+    assert j["metric"] == bench.METRIC and j["unit"] == "GiB/s" and j["higher_is_better"] is True
+    assert j["value"] == pytest.approx(2 * count * n / (j["ms_per_step"] * 1e-3) / 2**30, rel=1e-3)
+    assert not {"cpu_baseline", "c2", "record_path", "roofline", "valu_roofline", "kernel_ms", "energy",
+                "device_monitor", "bitexact_fold", "correct", "scatter_gather"} & set(j)
+    out = {q.stem: np.load(q) for q in (tmp_path / "out").glob("*.npy")}
+    assert set(out) == {"tags", "status", "sample_records", "sealed_sample", "opened_sample"}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= 64e6
+    assert out["tags"].shape == (count, 4) and out["status"].shape == (count,) and not out["status"].any()
+    idx = out["sample_records"].astype(np.int64)
+    assert idx[0] == 0 and idx[-1] == count - 1 and len(set(idx)) == len(idx) >= 100
+    assert out["sealed_sample"].shape == (len(idx), n + 16) and out["opened_sample"].shape == (len(idx), n)
+    for row, i in enumerate(idx):
+        i = int(i)
+        pt = oracle.fill_record(bench.SEED, i, n)
+        exp = oracle.seal(bench.KEY, i.to_bytes(8, "big"), pt, oracle.tls_ad(i, n))
+        assert out["sealed_sample"][row].astype(np.uint8).tobytes() == exp, i
+        assert out["opened_sample"][row].astype(np.uint8).tobytes() == pt, i
+        assert out["tags"][i].astype("<u4").tobytes() == exp[n:], i
+
+
+def test_dump_outputs_samples_are_seeded_and_exact(tmp_path, monkeypatch):
+    """dump_outputs on host tensors, with the caps lowered so that both the
+    tags and the whole records are sampled: the same indices on every call
+    (first and last record included), listed in tag_records.npy /
+    sample_records.npy, and the dumped values are the buffers' bytes."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_TAG_RECORDS", 16)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_RECORDS", 8)
+    count, n, cs = 50, 64, 128
+    g = torch.Generator().manual_seed(1)
+    w = {"count": count, "n": n, "cs": cs, "lay": None,
+         "ct": torch.randint(0, 256, (count * cs,), dtype=torch.uint8, generator=g),
+         "back": torch.randint(0, 256, (count * n,), dtype=torch.uint8, generator=g),
+         "status": torch.randint(0, 4, (count,), dtype=torch.uint8, generator=g)}
+    bench.dump_outputs(tmp_path / "a", w, 0, 1)
+    bench.dump_outputs(tmp_path / "b", w, 0, 1)
+    a = {q.stem: np.load(q) for q in (tmp_path / "a").glob("*.npy")}
+    assert set(a) == {"tags", "status", "tag_records", "sample_records", "sealed_sample", "opened_sample"}
+    for name, arr in a.items():
+        assert arr.dtype in (np.float32, np.float64) and np.array_equal(arr, np.load(tmp_path / "b" / f"{name}.npy"))
+    rows, back = w["ct"].view(count, cs).numpy(), w["back"].view(count, n).numpy()
+    t, r = a["tag_records"].astype(np.int64), a["sample_records"].astype(np.int64)
+    for idx, most in ((t, 16), (r, 8)):
+        assert idx[0] == 0 and idx[-1] == count - 1 and most - 2 <= len(idx) <= most and (np.diff(idx) > 0).all()
+    assert np.array_equal(a["tags"].astype("<u4").view(np.uint8), rows[t, n:n + 16])
+    assert np.array_equal(a["status"], w["status"].numpy()[t])
+    assert np.array_equal(a["sealed_sample"], rows[r, :n + 16]) and np.array_equal(a["opened_sample"], back[r])
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_c2(gpu, oracle, tmp_path):
+    """--dump-outputs of the mixed-size workload: the sampled records lie back
+    to back; each sealed one is the oracle's sealing of the opened one under
+    its connection key and sequence number, and its tag is the record's row
+    of tags.npy."""
+    import struct
+
+    import numpy as np
+
+    from suruga_amd import workloads as W
+
+    count = 4096
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "c2", "--records", str(count),
+                        "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True,
+                       text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert _last_json(p.stdout)["steps"] == 2
+    out = {q.stem: np.load(q) for q in tmp_path.glob("*.npy")}
+    assert set(out) == {"tags", "status", "sample_records", "sealed_sample", "opened_sample"}
+    lay = W.c2_layout(count, ct_align=128, pt_align=64)
+    idx = out["sample_records"].astype(np.int64)
+    assert idx[0] == 0 and idx[-1] == count - 1 and len(idx) >= 100
+    assert out["tags"].shape == (count, 4) and not out["status"].any()
+    sealed, opened = out["sealed_sample"].astype(np.uint8).tobytes(), out["opened_sample"].astype(np.uint8).tobytes()
+    assert len(opened) == int(lay.lens[idx].sum()) and len(sealed) == len(opened) + 16 * len(idx)
+    a = q = 0
+    for i in idx:
+        m, s, k = int(lay.lens[i]), int(lay.seq[i]), int(lay.key_index[i])
+        exp = oracle.seal(lay.keys[32 * k:32 * k + 32], struct.pack(">Q", s), opened[a:a + m], oracle.tls_ad(s, m))
+        assert sealed[q:q + m + 16] == exp, int(i)
+        assert out["tags"][i].astype("<u4").tobytes() == exp[m:], int(i)
+        a, q = a + m, q + m + 16
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("strong", [False, True])
 def test_bench_two_ranks_one_card(gpu, strong):
     env = dict(os.environ, SG_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), str(ROOT / "bench.py"), "--gpus", "2",
-           "--records", "4096", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + (["--strong"] if strong else [])
+           "--full", "--records", "4096", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    cmd += ["--strong"] if strong else []
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     j = _last_json(p.stdout)
@@ -103,9 +221,8 @@ def test_bench_gpus_two_launches_its_own_ranks(gpu):
     driver uses), both on the test box's one card with the gloo group."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["SG_DIST_BACKEND"] = "gloo"
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--records", "4096", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=300, cwd=ROOT,
-                       env=env)
+    p = subprocess.run(FULL + ["--gpus", "2", "--records", "4096", "--steps", "2", "--warmup", "1",
+                              "--no-cpu-baseline"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     j = _last_json(p.stdout)
     assert j["n_gpus"] == 2 and j["correct"] and j["scaling"] == "weak"
@@ -166,9 +283,8 @@ def test_bench_failing_rank_fails_the_line(gpu):
     "correct": false and the run exits non-zero."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(SG_DIST_BACKEND="gloo", SG_BENCH_CORRUPT_RANK="1")
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--records", "4096", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--sg-records", "0"], capture_output=True, text=True,
-                       timeout=300, cwd=ROOT, env=env)
+    p = subprocess.run(FULL + ["--gpus", "2", "--records", "4096", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                              "--sg-records", "0"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert p.returncode != 0
     j = _last_json(p.stdout)
     assert j["correct"] is False and j["bitexact_fold"] is False
@@ -183,8 +299,8 @@ def test_bench_local_rank_maps_to_visible_device(gpu):
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "MASTER_PORT")}
     env["LOCAL_RANK"] = "1"
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--records", "4096", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--record-path-bytes", "0"], capture_output=True, text=True, timeout=300,
+    p = subprocess.run(FULL + ["--records", "4096", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                              "--record-path-bytes", "0"], capture_output=True, text=True, timeout=300,
                        cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     j = _last_json(p.stdout)
@@ -199,7 +315,7 @@ def test_bench_c2_two_ranks_scatter_gather(gpu):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["SG_DIST_BACKEND"] = "gloo"
     p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--workload", "c2", "--records", "8192",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--sg-records", "1024"],
+                        "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--sg-records", "1024"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     j = _last_json(p.stdout)
@@ -219,8 +335,8 @@ def test_bench_two_real_devices(gpu):
         pytest.skip("needs two visible GPUs")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT",
                                                             "SG_DIST_BACKEND")}
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--records", "4096", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--c2-steps", "0", "--energy-seconds", "0"],
+    p = subprocess.run(FULL + ["--gpus", "2", "--records", "4096", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                              "--c2-steps", "0", "--energy-seconds", "0"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     j = _last_json(p.stdout)

@@ -8,8 +8,8 @@ B=$1; R=${2:-3}; shift 2 || shift $#
 OUT=${GRAFT_REPO_ROOT:-.}/gpurun_out/ab
 mkdir -p "$OUT"
 for i in $(seq 1 "$R"); do
-  timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > "$OUT/a_$i.json"
-  SURUGA_GPU_LIB=$B timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > "$OUT/b_$i.json"
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > "$OUT/a_$i.json"
+  SURUGA_GPU_LIB=$B timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > "$OUT/b_$i.json"
 done
 python - "$OUT" "$R" <<'PY'
 import json, sys

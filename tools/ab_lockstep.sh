@@ -8,8 +8,8 @@ R=${1:-2}; shift || true
 OUT=${GRAFT_REPO_ROOT:-.}/gpurun_out/ab_ls
 mkdir -p "$OUT"
 for i in $(seq 1 "$R"); do
-  SG_LOCKSTEP=0 timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > "$OUT/a_$i.json"
-  SG_LOCKSTEP=1 timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > "$OUT/b_$i.json"
+  SG_LOCKSTEP=0 timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > "$OUT/a_$i.json"
+  SG_LOCKSTEP=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > "$OUT/b_$i.json"
 done
 python - "$OUT" "$R" <<'PY'
 import json, sys

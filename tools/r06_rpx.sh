@@ -8,7 +8,7 @@ timeout -k 10 300 python -u -m pytest -x -q --timeout 240 --timeout-method threa
 for kd in ${VALS:-0 1}; do
   t=$VAR$kd
   env $VAR=$kd timeout -k 10 200 python -u tools/record_path_bench.py --threads 8 --registered 0,1 --json-out $O/rp_$t.json > $O/rp_$t.log 2>&1 || { echo "$t failed"; tail -5 $O/rp_$t.log; exit 1; }
-  env $VAR=$kd timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --c2-steps 3 --no-cpu-baseline --no-bitexact --energy-seconds 0 > $O/bench_$t.json 2> $O/bench_$t.err || { echo "bench $t failed"; tail -5 $O/bench_$t.err; exit 1; }
+  env $VAR=$kd timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --c2-steps 3 --no-cpu-baseline --no-bitexact --energy-seconds 0 > $O/bench_$t.json 2> $O/bench_$t.err || { echo "bench $t failed"; tail -5 $O/bench_$t.err; exit 1; }
   python - $O $t <<'PY'
 import json, sys
 o, t = sys.argv[1], sys.argv[2]

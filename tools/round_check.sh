@@ -11,8 +11,8 @@ rc=$?; tail -1 "$OUT/gpu_tests.log"
 if [ $rc -gt 1 ]; then echo "pytest rc=$rc: stopping"; exit $rc; fi
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$OUT/smoke.log" 2>&1 || { echo "smoke failed"; tail -5 "$OUT/smoke.log"; exit 1; }
 tail -1 "$OUT/smoke.log"
-timeout -k 10 400 python -u bench.py > "$OUT/bench_c1.json" 2> "$OUT/bench_c1.err" || { echo "bench c1 failed"; exit 1; }
-timeout -k 10 400 python -u bench.py --workload c2 > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err" || { echo "bench c2 failed"; exit 1; }
+timeout -k 10 400 python -u bench.py --full > "$OUT/bench_c1.json" 2> "$OUT/bench_c1.err" || { echo "bench c1 failed"; exit 1; }
+timeout -k 10 400 python -u bench.py --full --workload c2 > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err" || { echo "bench c2 failed"; exit 1; }
 python - "$OUT" <<'PY'
 import json, sys
 for w in ("c1", "c2"):
