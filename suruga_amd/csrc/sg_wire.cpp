@@ -1,9 +1,10 @@
 // sg_wire.cpp -- the TLS record header parser of sg_read_records and
-// sg_parse_records (klutzy/suruga src/tls.rs:217-281), split out of
-// sg_record.cpp so that the bytes a peer controls are parsed by code that
-// builds and runs without a GPU: tests/cpp/test_host_san.cpp runs it under
-// AddressSanitizer and UndefinedBehaviorSanitizer over a corpus of malformed
-// and truncated headers.
+// sg_parse_records (klutzy/suruga src/tls.rs:217-281) and the record layer's
+// framing arithmetic (sg_wire.h), split out of sg_record.cpp so that the
+// bytes a peer controls are parsed, and the offsets derived from them
+// computed, by code that builds and runs without a GPU:
+// tests/cpp/test_host_san.cpp runs it under AddressSanitizer and
+// UndefinedBehaviorSanitizer over a corpus of malformed and truncated headers.
 #include "sg_wire.h"
 
 #include "sg_err.h"
@@ -30,7 +31,29 @@ int32_t parse_wire(const uint8_t* wire, size_t wire_len, size_t max_records, std
     return SG_OK;
 }
 
+void chunk_shape(const WireRec* r, uint32_t k, ChunkShape* out) {
+    const WireRec& R0 = r[0];
+    bool same = true, tls = true, dense = true;
+    out->pre[0] = 0;
+    for (uint32_t i = 0; i < k; ++i) {
+        const WireRec& R = r[i];
+        same = same && R.flen == R0.flen;
+        tls = tls && R.type == R0.type && R.major == R0.major && R.minor == R0.minor;
+        dense = dense && R.off == R0.off + (size_t)i * (SG_HEADER_LEN + R0.flen);
+        out->pre[i + 1] = out->pre[i] + (R.flen - SG_MAC_LEN);
+    }
+    out->same = same;
+    out->tls = tls;
+    out->dense = dense;
+    out->flen = R0.flen;
+}
+
 }  // namespace sg
+
+extern "C" size_t sg_wire_bound(size_t len) {
+    const size_t recs = (len + SG_RECORD_MAX_LEN - 1) / SG_RECORD_MAX_LEN;
+    return len + recs * (SG_HEADER_LEN + SG_MAC_LEN);
+}
 
 extern "C" int sg_parse_records(const uint8_t* wire, size_t wire_len, size_t max_records, sg_wire_record* recs,
                                 size_t* count, int32_t* error) {

@@ -10,24 +10,37 @@
 //     with the exact expected outcome computed by an independent model below;
 //   * suruga_amd/csrc/sg_keysched.cpp -- SHA-256 / HMAC-SHA256 / the P_SHA256
 //     PRF / the key block, on the FIPS 180-4 and RFC 4231 vectors, the PRF's
-//     split-read invariance (prf.rs:135-162) and a threaded key derivation.
+//     split-read invariance (prf.rs:135-162) and a threaded key derivation;
+//   * the framing arithmetic of sg_wire.h / sg_wire.cpp -- the writer's plan
+//     (record lengths, wire offsets, wire_need) fed back through the parser,
+//     the shape of a chunk of parsed records with its prefix sums, and the
+//     explicit nonce / AD bytes, each against a plain statement below;
+//   * suruga_amd/csrc/sg_copy_pool.cpp -- the framing copies' thread pool:
+//     every index exactly once, concurrent callers, and no touch of a job
+//     after its run() has returned.
 //
-// No GPU: neither file includes a HIP header.  Exit code 0 = every check
+// -DSG_POOL_ONLY builds the pool's checks alone (with sg_copy_pool.cpp), for
+// the ThreadSanitizer run.
+//
+// No GPU: none of the files includes a HIP header.  Exit code 0 = every check
 // passed; a sanitizer report aborts the program (halt_on_error).
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <memory>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/suruga_gpu.h"
+#include "../../suruga_amd/csrc/sg_copy_pool.h"
 #include "../../suruga_amd/csrc/sg_err.h"
+#include "../../suruga_amd/csrc/sg_wire.h"
 
-// sg_capi.cpp owns the thread-local message; this program only needs the code
-int sg::fail(int code, const char*, const char*) { return code; }
-
-static int g_fail = 0;
+static std::atomic<int> g_fail{0};
 #define CHECK(c)                                                               \
     do {                                                                       \
         if (!(c)) {                                                            \
@@ -35,6 +48,10 @@ static int g_fail = 0;
             ++g_fail;                                                          \
         }                                                                      \
     } while (0)
+
+#ifndef SG_POOL_ONLY
+// sg_capi.cpp owns the thread-local message; this program only needs the code
+int sg::fail(int code, const char*, const char*) { return code; }
 
 static uint64_t g_rng = 0x5341'4e49'5449'5a45ull;  // deterministic corpus
 static uint64_t rnd() {
@@ -171,6 +188,116 @@ static void parser_corpus() {
     CHECK(sg_parse_records(one, 5, 1, &r, &count, nullptr) == SG_E_ARG);
 }
 
+// ---- the framing arithmetic ----------------------------------------------------
+// The writer's plan: a zero payload framed at the planned offsets parses back
+// into exactly the planned records.
+static void write_plan() {
+    const size_t lens[] = {1, 16383, 16384, 16385, 32768, 256u * 16384u + 1};
+    for (size_t len : lens) {
+        const sg::WritePlan plan(len);
+        CHECK(plan.nrec == (len + 16383) / 16384);
+        size_t sum = 0;
+        for (uint64_t r = 0; r < plan.nrec; ++r) {
+            CHECK(plan.rec_len(r) == (r + 1 < plan.nrec ? 16384u : len - r * 16384));
+            CHECK(plan.wire_off(r) == r * (5 + 16384 + 16));
+            sum += plan.rec_len(r);
+        }
+        CHECK(sum == len);
+        CHECK(plan.wire_need() == sg_wire_bound(len));
+        CHECK(plan.wire_need() == len + plan.nrec * 21);
+        // exact-size heap image: ASan flags a header written past wire_need
+        uint8_t* w = static_cast<uint8_t*>(std::calloc(plan.wire_need(), 1));
+        for (uint64_t r = 0; r < plan.nrec; ++r)
+            sg::put_header(w + plan.wire_off(r), (uint8_t)(20 + r % 4), 3, (uint8_t)(r % 3), plan.rec_len(r) + 16);
+        std::vector<sg::WireRec> recs;
+        CHECK(sg::parse_wire(w, plan.wire_need(), 1u << 20, recs) == SG_OK);
+        CHECK(recs.size() == plan.nrec);
+        for (uint64_t r = 0; r < plan.nrec && r < recs.size(); ++r) {
+            CHECK(recs[r].off == plan.wire_off(r) + 5 && recs[r].flen == plan.rec_len(r) + 16);
+            CHECK(recs[r].type == 20 + r % 4 && recs[r].major == 3 && recs[r].minor == r % 3);
+            CHECK(w[plan.wire_off(r) + 3] * 256u + w[plan.wire_off(r) + 4] == recs[r].flen);
+        }
+        std::free(w);
+    }
+    CHECK(sg::WritePlan(0).nrec == 0 && sg::WritePlan(0).wire_need() == 0 && sg_wire_bound(0) == 0);
+}
+
+// k back-to-back records of fragment length flen, the first header at `base`
+static std::vector<sg::WireRec> dense_list(uint32_t k, uint32_t flen, size_t base = 100) {
+    std::vector<sg::WireRec> v;
+    for (uint32_t i = 0; i < k; ++i) v.push_back({base + 5 + (size_t)i * (5 + flen), flen, 23, 3, 3});
+    return v;
+}
+
+static void check_shape(const std::vector<sg::WireRec>& v, bool same, bool tls, bool dense) {
+    auto sh = std::make_unique<sg::ChunkShape>();  // (on the heap: ASan sees a write past it)
+    std::memset(sh.get(), 0xA5, sizeof *sh);
+    sg::chunk_shape(v.data(), (uint32_t)v.size(), sh.get());
+    CHECK(sh->same == same && sh->tls == tls && sh->dense == dense);
+    CHECK(sh->flen == v[0].flen);
+    uint32_t sum = 0;
+    for (size_t i = 0; i < v.size(); ++i) {
+        CHECK(sh->pre[i] == sum);
+        sum += v[i].flen - 16;
+    }
+    CHECK(sh->pre[v.size()] == sum);
+    if (v.size() < sg::kChunk) CHECK(sh->pre[v.size() + 1] == 0xA5A5A5A5u);  // nothing past pre[k]
+}
+
+static void chunk_shapes() {
+    check_shape(dense_list(sg::kChunk, 16384 + 16), true, true, true);
+    check_shape(dense_list(9, 80), true, true, true);
+    check_shape(dense_list(1, 16), true, true, true);  // k = 1, an empty plaintext
+    {  // one record of another length: in the middle the later records shift, at the end they do not
+        auto v = dense_list(9, 80);
+        v[4].flen = 81;
+        for (size_t i = 5; i < v.size(); ++i) v[i].off += 1;
+        check_shape(v, false, true, false);
+        auto w = dense_list(9, 80);
+        w[8].flen = 79;
+        check_shape(w, false, true, true);
+        auto f = dense_list(9, 80);  // the first one differs from all others
+        f[0].flen = 96;
+        for (size_t i = 1; i < f.size(); ++i) f[i].off += 16;
+        check_shape(f, false, true, false);
+    }
+    for (int field = 0; field < 3; ++field) {  // one of another type / version
+        auto v = dense_list(9, 80);
+        (field == 0 ? v[8].type : field == 1 ? v[3].major : v[1].minor) ^= 1;
+        check_shape(v, true, false, true);
+    }
+    {  // a gap before record 6
+        auto v = dense_list(9, 80);
+        for (size_t i = 6; i < v.size(); ++i) v[i].off += 3;
+        check_shape(v, true, true, false);
+    }
+}
+
+// Explicit nonce / AD (tls.rs:250-265), stated digit by digit.
+static void explicit_meta() {
+    const uint64_t seqs[] = {0, 0xFFFFFFFFull, 0x100000000ull, 0xFFFFFFFFFFFFFFFFull};
+    const size_t bytes = (size_t)sg::kChunk * (8 + 13);
+    CHECK(sg::kMetaBytes == 8 + 13);
+    for (uint64_t seq : seqs)
+        for (uint32_t i : {0u, 1u, sg::kChunk - 1}) {
+            uint8_t* meta = static_cast<uint8_t*>(std::malloc(bytes));
+            std::memset(meta, 0xA5, bytes);
+            const sg::WireRec R = {0, (uint32_t)(16 + 0x1234 + i), (uint8_t)(20 + i % 4), 3, (uint8_t)(1 + i % 3)};
+            sg::put_explicit_meta(meta, i, seq, R);
+            std::vector<uint8_t> exp(bytes, 0xA5);
+            uint64_t q = seq;
+            for (int d = 7; d >= 0; --d, q /= 256) exp[8 * i + d] = exp[8 * sg::kChunk + 13 * i + d] = (uint8_t)(q % 256);
+            uint8_t* ad = exp.data() + 8 * sg::kChunk + 13 * i;
+            ad[8] = R.type;
+            ad[9] = R.major;
+            ad[10] = R.minor;
+            ad[11] = (uint8_t)((R.flen - 16) / 256);
+            ad[12] = (uint8_t)((R.flen - 16) % 256);
+            CHECK(std::memcmp(meta, exp.data(), bytes) == 0);
+            std::free(meta);
+        }
+}
+
 // ---- the key schedule --------------------------------------------------------
 static std::string hex(const uint8_t* p, size_t n) {
     static const char* d = "0123456789abcdef";
@@ -241,11 +368,66 @@ static void keysched() {
     CHECK(sg_derive_keys(1, pm.data(), 65, 65, cr.data(), sr.data(), nullptr, c1.data(), s1.data(), 1) == SG_E_ARG);
 }
 
+#endif  // !SG_POOL_ONLY
+
+// ---- the copy pool -------------------------------------------------------------
+// Per-index counters on the heap, and the job's std::function on the heap
+// too: both are freed right after run() returns, so a worker that touches a
+// finished job reads or calls freed memory, which ASan reports.
+static void pool_run_counted(uint32_t n) {
+    std::unique_ptr<std::atomic<uint32_t>[]> cnt(new std::atomic<uint32_t>[n ? n : 1]);
+    for (uint32_t i = 0; i < n; ++i) cnt[i].store(0);
+    std::atomic<uint32_t>* c = cnt.get();
+    auto fn = std::make_unique<std::function<void(uint32_t)>>([c, n](uint32_t i) {
+        CHECK(i < n);
+        if (i < n) c[i].fetch_add(1);
+    });
+    sg::CopyPool::shared().run(n, *fn);
+    for (uint32_t i = 0; i < n; ++i) CHECK(cnt[i].load() == 1);
+    fn.reset();
+    cnt.reset();
+}
+
+static void copy_pool() {
+    setenv("SG_COPY_THREADS", "4", 1);  // read once, by the pool's first use below
+    const std::thread::id me = std::this_thread::get_id();
+    for (int via = 0; via < 2; ++via) {  // the pool's run() and copy_run(): 0 and 1 run inline
+        auto run = [&](uint32_t n, const std::function<void(uint32_t)>& fn) {
+            if (via) sg::copy_run(n, fn);
+            else sg::CopyPool::shared().run(n, fn);
+        };
+        int calls = 0;
+        bool here = true;
+        run(0, [&](uint32_t) { ++calls; });
+        CHECK(calls == 0);
+        run(1, [&](uint32_t i) {
+            ++calls;
+            here = here && i == 0 && std::this_thread::get_id() == me;
+        });
+        CHECK(calls == 1 && here);
+    }
+    for (uint32_t n : {2u, 7u, 1000u}) pool_run_counted(n);
+    // four callers at once, 200 runs each of mixed sizes
+    std::vector<std::thread> callers;
+    for (uint32_t t = 0; t < 4; ++t)
+        callers.emplace_back([t] {
+            const uint32_t sizes[] = {1000, 2, 0, 7, 1, 64, 257, 3};
+            for (uint32_t it = 0; it < 200; ++it) pool_run_counted(sizes[(it + t) % 8]);
+        });
+    for (auto& th : callers) th.join();
+}
+
 int main() {
+#ifndef SG_POOL_ONLY
     parser_corpus();
+    write_plan();
+    chunk_shapes();
+    explicit_meta();
     keysched();
+#endif
+    copy_pool();
     if (g_fail) {
-        std::fprintf(stderr, "%d checks failed\n", g_fail);
+        std::fprintf(stderr, "%d checks failed\n", g_fail.load());
         return 1;
     }
     std::printf("host sanitizer checks passed\n");

@@ -8,12 +8,9 @@ per-direction + duplex record-path check in a child process of its own:
 
 * SG_RECORD_SDMA=1: staged calls through the copy-engine pipeline instead of
   the direct one;
-* SG_RECORD_SDMA=1 SG_RECORD_DEVICE_WAITS=1: round 5's device-waited form;
 * SG_RECORD_KD2H=1: zero-copy output by kernel stores instead of an SDMA D2H;
-* SG_COPY_STREAMS=0 SG_RECORD_SLOTS=2: per-slot streams, the shallowest
-  pipeline;
-* SG_ZERO_COPY=0: registered buffers through the staged path;
-* SG_DIRECT_PRIO=0: the direct pipeline's kernel streams at default priority.
+* SG_RECORD_SLOTS=2: the shallowest pipeline;
+* SG_ZERO_COPY=0: registered buffers through the staged path.
 """
 from __future__ import annotations
 
@@ -30,11 +27,9 @@ ROOT = Path(__file__).resolve().parent.parent
 
 VARIANTS = {
     "sdma": {"SG_RECORD_SDMA": "1"},
-    "device_waits": {"SG_RECORD_SDMA": "1", "SG_RECORD_DEVICE_WAITS": "1"},
     "kd2h": {"SG_RECORD_KD2H": "1"},
-    "slot_streams": {"SG_COPY_STREAMS": "0", "SG_RECORD_SLOTS": "2"},
+    "shallow": {"SG_RECORD_SLOTS": "2"},
     "no_zero_copy": {"SG_ZERO_COPY": "0"},
-    "direct_default_prio": {"SG_DIRECT_PRIO": "0"},
 }
 
 

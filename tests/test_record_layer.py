@@ -489,6 +489,66 @@ def test_gpu_zero_copy_edges(gpu, oracle):
     assert np.array_equal(results[False], results[True])
 
 
+@pytest.mark.gpu
+def test_gpu_zero_copy_mixed_chunks(gpu, oracle):
+    """Registered-buffer read whose chunks take different ways inside one
+    call: 520 records of 64 B plaintext, record 300 of 65 B.  Chunk 0 (records
+    0-255) is uniform and goes zero-copy, chunk 1 (256-511) holds the odd
+    record and goes through the staging, chunk 2 has 8 records.  `out`,
+    `records` and `out_len` equal the unregistered read's and the input; with
+    one byte of record 300 flipped exactly 300 records are delivered and `out`
+    holds nothing of record 300 or of any record after it."""
+    import ctypes as C
+
+    import numpy as np
+
+    from suruga_amd import ChaCha20Poly1305
+    from suruga_amd import _native as N
+
+    lib = N.load()
+    key = bytes(range(5, 37))
+    count, odd, seq0 = 520, 300, 3
+    lens = [65 if r == odd else 64 for r in range(count)]
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    total = int(offs[-1])
+    data = np.frombuffer(oracle.fill_record(0x4D, 9, total), dtype=np.uint8).copy()
+    pieces, woff = [], [0]
+    for r, n in enumerate(lens):
+        pt = data[offs[r]:offs[r + 1]].tobytes()
+        ct = oracle.seal(key, struct.pack(">Q", seq0 + r), pt, oracle.tls_ad(seq0 + r, n))
+        pieces.append(bytes([23, 3, 3]) + struct.pack(">H", n + 16) + ct)
+        woff.append(woff[-1] + len(pieces[-1]))
+    wire = np.frombuffer(b"".join(pieces), dtype=np.uint8).copy()
+    assert wire.size < 100 << 10
+    dec = ChaCha20Poly1305().new_decryptor(key)
+    res = N.SgReadResult()
+
+    def read(w, out):
+        N.check(lib.sg_read_records(dec._ptr, seq0, w.ctypes.data, w.size, out.ctypes.data, out.size, None, None,
+                                    1 << 20, C.byref(res)))
+        return res.records, res.out_len, res.error
+
+    plain = np.full(total, 0xEE, dtype=np.uint8)
+    assert read(wire.copy(), plain) == (count, total, N.SG_OK)
+    out = np.full(total, 0xEE, dtype=np.uint8)
+    for a in (wire, out):
+        N.check(lib.sg_host_register(a.ctypes.data, a.nbytes))
+    try:
+        assert read(wire, out) == (count, total, N.SG_OK)
+        assert np.array_equal(out, plain) and np.array_equal(out, data)
+        wire[woff[odd] + 5 + 20] ^= 0x04
+        out[:] = 0xEE
+        assert read(wire, out) == (odd, int(offs[odd]), N.SG_E_BAD_MAC)
+        assert np.array_equal(out[:offs[odd]], data[:offs[odd]])
+        # cleared (a zero-copy chunk) or never written (the staged one)
+        assert np.isin(out[offs[odd]:], (0, 0xEE)).all(), "bytes of undelivered records left in out"
+        leaked = [r for r in range(odd, count) if np.array_equal(out[offs[r]:offs[r + 1]], data[offs[r]:offs[r + 1]])]
+        assert leaked == [], f"plaintext of undelivered records {leaked[:5]} in out"
+    finally:
+        for a in (wire, out):
+            N.check(lib.sg_host_unregister(a.ctypes.data))
+
+
 def test_frame_record_index_math():
     """sg_frame_kernel finds the wire record of destination byte b as
     r = (b * rdiv) >> 40, rdiv = ceil(2^40 / pitch) (sg_kernels.hip), for

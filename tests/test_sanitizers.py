@@ -11,11 +11,13 @@ restatement; run it under ASan/UBSan in this container").
 2. The asserts are live in that build: an Int1305 product of out-of-range
    limbs aborts.
 3. The library's host-only sources -- the record header parser that takes a
-   peer's bytes (sg_wire.cpp, tls.rs:217-238) and the key schedule
-   (sg_keysched.cpp) -- built with g++ -fsanitize=address,undefined into
+   peer's bytes and the framing arithmetic (sg_wire.cpp, tls.rs:217-238), the
+   key schedule (sg_keysched.cpp) and the framing copies' thread pool
+   (sg_copy_pool.cpp) -- built with g++ -fsanitize=address,undefined into
    tests/cpp/test_host_san.cpp's corpus run.
+4. The thread pool's checks of the same program alone under ThreadSanitizer.
 
-CPU only: no GPU, no HIP runtime (neither host source includes a HIP header).
+CPU only: no GPU, no HIP runtime (no host source includes a HIP header).
 """
 from __future__ import annotations
 
@@ -81,9 +83,28 @@ def test_host_sources_under_asan_ubsan(tmp_path):
     exe = tmp_path / "test_host_san"
     csrc = ROOT / "suruga_amd" / "csrc"
     cmd = ["g++", "-std=c++17", "-Wall", "-Wextra", "-pthread", *SAN, "-o", str(exe),
-           str(ROOT / "tests" / "cpp" / "test_host_san.cpp"), str(csrc / "sg_wire.cpp"), str(csrc / "sg_keysched.cpp")]
+           str(ROOT / "tests" / "cpp" / "test_host_san.cpp"), str(csrc / "sg_wire.cpp"), str(csrc / "sg_keysched.cpp"),
+           str(csrc / "sg_copy_pool.cpp")]
     p = subprocess.run(cmd, capture_output=True, text=True)
     assert p.returncode == 0, p.stderr[-4000:]
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=dict(os.environ, **SAN_ENV))
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
+    assert "host sanitizer checks passed" in r.stdout
+
+
+def test_copy_pool_under_tsan(tmp_path):
+    """The copy pool's checks of tests/cpp/test_host_san.cpp alone
+    (-DSG_POOL_ONLY) under ThreadSanitizer, as a stand-alone program."""
+    lib = subprocess.run(["gcc", "-print-file-name=libtsan.so"], capture_output=True, text=True).stdout.strip()
+    if not lib or not Path(lib).exists():
+        pytest.skip("gcc's libtsan.so is not installed")
+    exe = tmp_path / "test_pool_tsan"
+    cmd = ["g++", "-std=c++17", "-Wall", "-Wextra", "-pthread", "-fsanitize=thread", "-fno-omit-frame-pointer", "-g",
+           "-O1", "-DSG_POOL_ONLY", "-o", str(exe), str(ROOT / "tests" / "cpp" / "test_host_san.cpp"),
+           str(ROOT / "suruga_amd" / "csrc" / "sg_copy_pool.cpp")]
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[-4000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1"))
+    assert r.returncode == 0 and "ThreadSanitizer" not in r.stderr, (r.stdout + r.stderr)[-4000:]
     assert "host sanitizer checks passed" in r.stdout
