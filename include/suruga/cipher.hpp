@@ -145,7 +145,11 @@ public:
     Bytes encrypt(Slice nonce, Slice plain, Slice ad) override {
         detail::check_nonce(nonce);
         Bytes out(plain.size + SG_MAC_LEN);
-        check_sg(sg_seal(ctx_.get(), nonce.data, nonce.size, plain.data, plain.size, ad.data, ad.size, out.data()));
+        // any length, as the reference (mod.rs:22-24): above the single-record
+        // bounds the message path spreads the one message over the chip
+        const bool lng = plain.size > SG_MAX_RECORD_LEN || ad.size > SG_MAX_AD_LEN;
+        check_sg((lng ? sg_seal_msg : sg_seal)(ctx_.get(), nonce.data, nonce.size, plain.data, plain.size, ad.data,
+                                               ad.size, out.data()));
         return out;
     }
     sg_ctx* handle() const { return ctx_.get(); }  // batched record layer (tls.hpp)
@@ -163,8 +167,9 @@ public:
         if (encrypted.size < SG_MAC_LEN)  // :68-70
             throw TlsError(TlsErrorKind::BadRecordMac, "message too short");
         Bytes out(encrypted.size - SG_MAC_LEN);
-        const int rc = sg_open(ctx_.get(), nonce.data, nonce.size, encrypted.data, encrypted.size, ad.data, ad.size,
-                               out.data());
+        const bool lng = out.size() > SG_MAX_RECORD_LEN || ad.size > SG_MAX_AD_LEN;
+        const int rc = (lng ? sg_open_msg : sg_open)(ctx_.get(), nonce.data, nonce.size, encrypted.data, encrypted.size,
+                                                     ad.data, ad.size, out.data());
         if (rc == SG_E_SHORT) throw TlsError(TlsErrorKind::BadRecordMac, "message too short");
         if (rc == SG_E_BAD_MAC) throw TlsError(TlsErrorKind::BadRecordMac, "wrong mac");  // :89-90
         check_sg(rc);

@@ -195,6 +195,83 @@ size_t sg_workspace_size(uint32_t count);
 int sg_seal_batch(const sg_batch* b);
 int sg_open_batch(const sg_batch* b);
 
+/* ---- long messages: any data and AD length, one message over the whole chip
+ * Encryptor::encrypt / Decryptor::decrypt take data and additional data of any
+ * length (cipher/mod.rs:22-32, chacha20_poly1305.rs:19-94).  sg_seal, sg_open
+ * and the batch calls keep their bounds (SG_MAX_AD_LEN, SG_MAX_RECORD_LEN);
+ * the message calls below take one key, one nonce, n data bytes and ad_len AD
+ * bytes, same construction, and spread the one message over a persistent grid
+ * (sg_msg.hip: the MAC stream is cut into tiles whose Poly1305 partial sums
+ * are combined exactly, so the tag is the sequential one bit for bit).
+ *
+ * The bound is 4 GiB - 64 for data and, separately, for AD: well inside the
+ * 2^32 blocks of the counter (state word 12 only).  The kernels index with 64
+ * bits throughout; the bound is where the CPU parity checker can still verify
+ * a message within a test's time, and lifting it needs only a faster checker. */
+#define SG_MSG_MAX_LEN      0xFFFFFFC0ull   /* data bytes and, separately, AD bytes */
+#define SG_MSG_KEEP_FAILED  0x1u            /* open: leave the unauthenticated plaintext
+                                               of a failed open in `out` (default: zeroed
+                                               on the device, same stream)              */
+
+typedef struct sg_msg {
+    const uint8_t* key;        /* 32 bytes, device                                  */
+    uint8_t        nonce[8];   /* by value                                          */
+    const uint8_t* ad;         /* device, ad_len bytes                              */
+    uint64_t       ad_len;
+    const uint8_t* in;         /* device; seal: n bytes of pt, open: n + 16 (ct||tag) */
+    uint64_t       in_len;
+    uint8_t*       out;        /* device; seal: n + 16, open: n. out == in allowed   */
+    uint8_t*       status;     /* open: one device byte (SG_OK / SG_E_BAD_MAC)      */
+    uint32_t       flags;      /* SG_MSG_*                                          */
+    void*          stream;     /* as sg_batch.stream; non-NULL: fully asynchronous   */
+    void*          workspace;  /* >= sg_msg_workspace_size() bytes, 16-byte aligned
+                                  device memory, or NULL: library cache (not under
+                                  stream capture)                                    */
+    size_t         workspace_size;
+} sg_msg;
+
+size_t sg_msg_workspace_size(void);
+/* Device-resident message.  Any alignment of in, out and ad; out may equal in
+ * exactly (in place), any other overlap is SG_E_ARG.  Open returns SG_E_SHORT
+ * for in_len < 16 before anything is touched; otherwise the MAC result lands
+ * in *status, after the decryption has run unconditionally
+ * (chacha20_poly1305.rs:80-93).  Returns SG_OK, SG_E_SHORT or < 0. */
+int sg_seal_msg_dev(const sg_msg* m);
+int sg_open_msg_dev(const sg_msg* m);
+
+/* Host pointers, same argument meaning and return values as sg_seal / sg_open,
+ * any length up to SG_MSG_MAX_LEN.  AD and data are copied into device buffers
+ * of a per-context cache that only grows, the device form runs on the
+ * context's stream, and the result is copied back; a failed open copies
+ * nothing back and zeroes out.  There is no chunked pipeline: these calls are
+ * bound by the host link and exist for the trait path (Encryptor::encrypt /
+ * Decryptor::decrypt above the single-record bounds). */
+int sg_seal_msg(sg_ctx* ctx, const uint8_t* nonce, size_t nonce_len, const uint8_t* pt, size_t n,
+                const uint8_t* ad, size_t adlen, uint8_t* out);
+int sg_open_msg(sg_ctx* ctx, const uint8_t* nonce, size_t nonce_len, const uint8_t* in, size_t in_len,
+                const uint8_t* ad, size_t adlen, uint8_t* out);
+
+/* The launch geometry of a message (host only, no GPU): the MAC stream
+ * ad || le64(ad_len) || ct || le64(n) has mac_blocks 16-byte blocks (the last
+ * may be short); zero_blocks virtual all-zero blocks in front make
+ * zero_blocks + mac_blocks == tiles * tile_blocks; tile_bytes = 16 *
+ * tile_blocks; group g of `groups` workgroups owns tiles
+ * [g * tiles_per_group, min(tiles, (g + 1) * tiles_per_group)).  The kernels
+ * take exactly this struct.  groups: 0 = automatic, else the wanted number of
+ * workgroups (the plan may use fewer: no group is empty).  SG_OK or SG_E_ARG
+ * (NULL out, a length above SG_MSG_MAX_LEN). */
+typedef struct sg_msg_plan {
+    uint64_t mac_blocks, tiles, zero_blocks;
+    uint32_t tile_blocks, tile_bytes, groups, tiles_per_group; /* last group takes the rest */
+} sg_msg_plan;
+int sg_msg_plan_for(uint64_t n, uint64_t adlen, uint32_t groups /* 0 = automatic */, sg_msg_plan* out);
+
+/* Workgroups of the message kernels: 0 = automatic, else that many (at most
+ * 1024); a test and A/B switch like sg_set_lockstep.  Initial value:
+ * environment SG_MSG_GROUPS, else 0.  Returns the previous setting; a negative
+ * argument only queries. */
+int sg_set_msg_groups(int n);
+
 /* ---- batched record layer over host memory ------------------------------
  * The throughput form of TlsWriter / TlsReader (tls.rs:68-380): many records
  * per call, pipelined inside the library, up to four chunks of 256 records in

@@ -6,6 +6,7 @@ Layout:
   suruga_amd/csrc/           gfx950 HIP kernels + C-ABI implementation
   suruga_amd/cipher.py       mirror of suruga's Aead/Encryptor/Decryptor traits
   suruga_amd/batch.py        device-resident batch seal/open (record-layer batching)
+  suruga_amd/msg.py          one long message (any data / AD length) over the whole chip
   suruga_amd/_native.py      ctypes binding of libsuruga_gpu.so
 
 The HIP library is the only compute path; importing the cipher classes works

@@ -24,9 +24,11 @@ ORACLE_DIR = ROOT / "oracle"
 ORACLE_LIB = ORACLE_DIR / "liboracle.so"
 
 HIP_SOURCES = [CSRC / "sg_kernels.hip", CSRC / "sg_wpr.hip", CSRC / "sg_pack.hip", CSRC / "sg_capi.cpp", CSRC / "sg_record.cpp",
-               CSRC / "sg_keysched.cpp", CSRC / "sg_wire.cpp", CSRC / "sg_copy_pool.cpp"]
+               CSRC / "sg_keysched.cpp", CSRC / "sg_wire.cpp", CSRC / "sg_copy_pool.cpp",
+               CSRC / "sg_msg.hip", CSRC / "sg_msg_capi.cpp", CSRC / "sg_msg_plan.cpp"]
 HIP_DEPS = HIP_SOURCES + [CSRC / "sg_internal.h", CSRC / "sg_device.h", CSRC / "sg_host.h", CSRC / "sg_err.h",
                           CSRC / "sg_wire.h", CSRC / "sg_copy_pool.h", CSRC / "sg_env.h", CSRC / "sg_chacha_grp.inc",
+                          CSRC / "sg_msg_plan.h",
                           ROOT / "include" / "suruga_gpu.h"]
 ORACLE_SOURCES = [ORACLE_DIR / "suruga_oracle.c"]
 ORACLE_DEPS = ORACLE_SOURCES + [ORACLE_DIR / "suruga_oracle.h", ORACLE_DIR / "so_pool.h"]
@@ -151,6 +153,26 @@ def build_cpp_tests(force: bool = False) -> Path:
     return CPP_TEST_BIN
 
 
+CPP_MSG_SRC = ROOT / "tests" / "cpp" / "test_msg.cpp"
+CPP_MSG_BIN = ROOT / "tests" / "cpp" / "test_msg"
+
+
+def build_cpp_msg_test(force: bool = False) -> Path:
+    """tests/cpp/test_msg: the long-message dispatch of include/suruga/cipher.hpp
+    (Encryptor / Decryptor above the single-record bounds) against the CPU
+    parity checker, linked against both in-tree libraries."""
+    lib, orc = build_library(), build_oracle()
+    deps = [CPP_MSG_SRC, ROOT / "include" / "suruga" / "cipher.hpp", ROOT / "include" / "suruga_gpu.h",
+            ORACLE_DIR / "suruga_oracle.h", lib, orc]
+    if force or _stale(CPP_MSG_BIN, deps):
+        tmp = CPP_MSG_BIN.with_suffix(f".tmp{os.getpid()}")
+        _run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-o", str(tmp), str(CPP_MSG_SRC),
+              f"-L{lib.parent}", f"-L{orc.parent}", "-lsuruga_gpu", "-loracle",
+              "-Wl,-rpath,$ORIGIN/../../suruga_amd:$ORIGIN/../../oracle"])
+        os.replace(tmp, CPP_MSG_BIN)
+    return CPP_MSG_BIN
+
+
 OSSL_SRC = ORACLE_DIR / "ossl_aead.c"
 OSSL_LIB = ORACLE_DIR / "libossl_aead.so"
 
@@ -192,6 +214,7 @@ def build_all(force: bool = False) -> None:
     build_oracle(force)
     build_ossl(force)
     build_cpp_tests(force)
+    build_cpp_msg_test(force)
     build_loopback_cpp(force)
 
 

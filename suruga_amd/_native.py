@@ -26,6 +26,8 @@ SG_NONCE_LEN = 8
 SG_MAC_LEN = 16
 SG_MAX_AD_LEN = 255
 SG_MAX_RECORD_LEN = 32768
+SG_MSG_MAX_LEN = 0xFFFFFFC0
+SG_MSG_KEEP_FAILED = 0x1
 
 # Every symbol include/suruga_gpu.h declares (checked by tests/test_abi.py).
 EXPORTS = [
@@ -38,6 +40,8 @@ EXPORTS = [
     "sg_host_register", "sg_host_unregister",
     "sg_sha256", "sg_hmac_sha256", "sg_prf_new", "sg_prf_get_bytes", "sg_prf_free",
     "sg_derive_keys", "sg_finished_verify_data",
+    "sg_msg_workspace_size", "sg_seal_msg_dev", "sg_open_msg_dev", "sg_seal_msg", "sg_open_msg",
+    "sg_msg_plan_for", "sg_set_msg_groups",
 ]
 
 
@@ -74,6 +78,33 @@ class SgBatch(C.Structure):
         ("workspace", C.c_void_p),
         ("workspace_size", C.c_size_t),
     ]
+
+
+class SgMsg(C.Structure):
+    """Mirror of ``struct sg_msg``."""
+
+    _fields_ = [
+        ("key", C.c_void_p),
+        ("nonce", C.c_uint8 * 8),
+        ("ad", C.c_void_p),
+        ("ad_len", C.c_uint64),
+        ("in_", C.c_void_p),
+        ("in_len", C.c_uint64),
+        ("out", C.c_void_p),
+        ("status", C.c_void_p),
+        ("flags", C.c_uint32),
+        ("stream", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_size", C.c_size_t),
+    ]
+
+
+class SgMsgPlan(C.Structure):
+    """Mirror of ``struct sg_msg_plan``."""
+
+    _fields_ = [("mac_blocks", C.c_uint64), ("tiles", C.c_uint64), ("zero_blocks", C.c_uint64),
+                ("tile_blocks", C.c_uint32), ("tile_bytes", C.c_uint32), ("groups", C.c_uint32),
+                ("tiles_per_group", C.c_uint32)]
 
 
 class SgReadResult(C.Structure):
@@ -199,6 +230,19 @@ def _declare(lib: C.CDLL) -> None:
     lib.sg_derive_keys.argtypes = [C.c_uint32, vp, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp, C.c_int]
     lib.sg_finished_verify_data.restype = C.c_int
     lib.sg_finished_verify_data.argtypes = [vp, C.c_int, vp, vp]
+    lib.sg_msg_workspace_size.restype = C.c_size_t
+    lib.sg_msg_workspace_size.argtypes = []
+    for f in (lib.sg_seal_msg_dev, lib.sg_open_msg_dev):
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(SgMsg)]
+    for f in (lib.sg_seal_msg, lib.sg_open_msg):
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
+                      C.c_char_p, C.c_size_t, u8p]
+    lib.sg_msg_plan_for.restype = C.c_int
+    lib.sg_msg_plan_for.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(SgMsgPlan)]
+    lib.sg_set_msg_groups.restype = C.c_int
+    lib.sg_set_msg_groups.argtypes = [C.c_int]
 
 
 def load(path: Path | None = None) -> C.CDLL:

@@ -117,7 +117,11 @@ class ChaCha20Poly1305Encryptor(_GpuCtx, Encryptor):
     def encrypt(self, nonce: bytes, plain: bytes, ad: bytes) -> bytes:
         nonce, plain, ad = _check_nonce(nonce), bytes(plain), bytes(ad)
         out = (C.c_uint8 * (len(plain) + N.SG_MAC_LEN))()
-        N.check(self._lib.sg_seal(self._ptr, nonce, len(nonce), plain, len(plain), ad, len(ad), out))
+        # any length, as the reference (mod.rs:22-24): above the single-record
+        # bounds the message path spreads the one message over the chip
+        long = len(plain) > N.SG_MAX_RECORD_LEN or len(ad) > N.SG_MAX_AD_LEN
+        seal = self._lib.sg_seal_msg if long else self._lib.sg_seal
+        N.check(seal(self._ptr, nonce, len(nonce), plain, len(plain), ad, len(ad), out))
         return bytes(out)
 
 
@@ -128,8 +132,9 @@ class ChaCha20Poly1305Decryptor(_GpuCtx, Decryptor):
         nonce, encrypted, ad = _check_nonce(nonce), bytes(encrypted), bytes(ad)
         n = max(len(encrypted) - N.SG_MAC_LEN, 0)
         out = (C.c_uint8 * max(n, 1))()
-        rc = N.check(self._lib.sg_open(self._ptr, nonce, len(nonce), encrypted, len(encrypted), ad,
-                                       len(ad), out))
+        long = n > N.SG_MAX_RECORD_LEN or len(ad) > N.SG_MAX_AD_LEN
+        open_ = self._lib.sg_open_msg if long else self._lib.sg_open
+        rc = N.check(open_(self._ptr, nonce, len(nonce), encrypted, len(encrypted), ad, len(ad), out))
         if rc == N.SG_E_SHORT:
             raise TlsError(TlsErrorKind.BadRecordMac, "message too short")
         if rc == N.SG_E_BAD_MAC:

@@ -312,6 +312,29 @@ int run_batch(const sg_batch* b, bool open) {
 
 }  // namespace
 
+namespace sg {
+
+int scratch_acquire(size_t need, hipStream_t s, void** ptr, void** handle) {
+    int dev = 0;
+    SG_HIP(hipGetDevice(&dev));
+    DeviceState* d = nullptr;
+    int rc;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        rc = device_state(dev, &d);
+    }
+    if (rc != SG_OK) return rc;
+    CachedWs* w = nullptr;
+    if ((rc = ws_acquire(d, need, s, &w)) != SG_OK) return rc;
+    *ptr = w->ptr;
+    *handle = w;
+    return SG_OK;
+}
+
+void scratch_release(void* handle, hipStream_t s, bool launched) { ws_release((CachedWs*)handle, s, launched); }
+
+}  // namespace sg
+
 // ---------------------------------------------------------------------------
 // single-record contexts (Encryptor / Decryptor)
 // ---------------------------------------------------------------------------
@@ -390,6 +413,8 @@ void sg_ctx_free(sg_ctx* c) {
     (void)hipHostFree(c->h_in);
     (void)hipHostFree(c->h_out);
     (void)hipFree(c->d_ws);
+    (void)hipFree(c->m_buf);
+    (void)hipFree(c->m_ad);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }

@@ -1,5 +1,5 @@
 // sg_host.h -- private host-side declarations shared by the C-ABI translation
-// units (sg_capi.cpp, sg_record.cpp).  Not part of the public ABI.
+// units (sg_capi.cpp, sg_record.cpp, sg_msg_capi.cpp).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,6 +15,12 @@ int hip_fail(hipError_t e, const char* where);
 
 struct RecordStaging;                   // sg_record.cpp
 void record_staging_free(RecordStaging* rs);
+
+// A buffer of >= need bytes from the library's workspace cache (sg_capi.cpp)
+// for one call on stream s of the current device, which must be a gfx950 part;
+// its reuse is ordered on the device.  scratch_release after the call's launches.
+int scratch_acquire(size_t need, hipStream_t s, void** ptr, void** handle);
+void scratch_release(void* handle, hipStream_t s, bool launched);
 
 // Makes `dev` the calling thread's current HIP device for a scope and restores
 // the previous one on exit, so a context call never leaves the caller's thread
@@ -63,5 +69,12 @@ struct sg_ctx {
     void* d_ws = nullptr;
     hipStream_t stream = nullptr;
     sg::RecordStaging* rec = nullptr;
+    // long messages (sg_seal_msg / sg_open_msg, sg_msg_capi.cpp): device buffers that
+    // only grow -- the message (sealed and opened in place) and its AD; the
+    // open status byte is d_key[32]
+    uint8_t* m_buf = nullptr;
+    size_t m_cap = 0;
+    uint8_t* m_ad = nullptr;
+    size_t m_ad_cap = 0;
     std::mutex mu;
 };
