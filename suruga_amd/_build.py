@@ -23,7 +23,8 @@ LIB = PKG / "libsuruga_gpu.so"
 ORACLE_DIR = ROOT / "oracle"
 ORACLE_LIB = ORACLE_DIR / "liboracle.so"
 
-HIP_SOURCES = [CSRC / "sg_kernels.hip", CSRC / "sg_wpr.hip", CSRC / "sg_pack.hip", CSRC / "sg_capi.cpp", CSRC / "sg_record.cpp",
+HIP_SOURCES = [CSRC / "sg_kernels.hip", CSRC / "sg_wpr.hip", CSRC / "sg_pack.hip", CSRC / "sg_plumb.hip",
+               CSRC / "sg_dispatch.cpp", CSRC / "sg_capi.cpp", CSRC / "sg_record.cpp",
                CSRC / "sg_keysched.cpp", CSRC / "sg_wire.cpp", CSRC / "sg_copy_pool.cpp",
                CSRC / "sg_msg.hip", CSRC / "sg_msg_capi.cpp", CSRC / "sg_msg_plan.cpp"]
 HIP_DEPS = HIP_SOURCES + [CSRC / "sg_internal.h", CSRC / "sg_device.h", CSRC / "sg_host.h", CSRC / "sg_err.h",

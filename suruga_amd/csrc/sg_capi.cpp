@@ -3,7 +3,9 @@
 // Host-side glue only: argument checking (mirroring the reference's panics /
 // errors), per-device state (stream, keying workspace cache, timing events),
 // staging for the single-record Encryptor/Decryptor calls, and the launches
-// of the gfx950 kernels in sg_kernels.hip.  There is no CPU fallback: every
+// of the gfx950 kernels through sg_internal.h's launch_* functions (uniform
+// 16 KiB batches: sg_wpr.hip; every other batch: sg_dispatch.cpp; fill,
+// compare and scrub: sg_plumb.hip).  There is no CPU fallback: every
 // seal/open goes through the HIP kernels or fails with an error code.
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,8 @@
 // sg_device.h -- device-side building blocks shared by the gfx950 kernels
 // (sg_kernels.hip: size-class kernels, keying, bucketing; sg_wpr.hip: the
-// wave-per-record kernel for full 16 KiB records).  Not part of the public ABI.
+// wave-per-record kernel for 4-16 KiB records; sg_pack.hip: the packed small
+// records of mixed batches; sg_msg.hip: long messages; sg_plumb.hip: scrub).
+// Not part of the public ABI.
 //
 //   ChaCha20 block function        klutzy/suruga src/crypto/chacha20.rs:25-135
 //   Poly1305 field arithmetic      src/crypto/poly1305.rs:25-192 (exact mod 2^130-5)
@@ -64,6 +66,11 @@ __device__ __forceinline__ void gst16(void* p, u32x4 v) {
 
 typedef u32x4 u32x4_u __attribute__((aligned(1)));
 __device__ __forceinline__ u32x4 ldu16(const void* p) { return *reinterpret_cast<const u32x4_u*>(p); }
+
+// four bytes at any alignment -> little-endian word (chacha20.rs:37-39, 45-46)
+__host__ __device__ __forceinline__ uint32_t le32(const uint8_t* b) {
+    return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
+}
 
 // LDS writes of one lane visible to the other lanes of its wave, and no
 // compiler reordering of LDS accesses across this point
@@ -297,6 +304,28 @@ __device__ __forceinline__ F26 words_to_f26(uint32_t w0, uint32_t w1, uint32_t w
     return c;
 }
 
+// x^e by square-and-multiply (mul_add outputs are valid multipliers as they stand)
+__device__ __forceinline__ F26 fpow(const F26 x, const uint32_t e) {
+    F26 acc = f26_one();
+    if (e == 0u) return acc;
+    for (int bit = 31 - __builtin_clz(e); bit >= 0; --bit) {
+        acc = fmul(acc, acc);
+        if ((e >> bit) & 1u) acc = fmul(acc, x);
+    }
+    return acc;
+}
+
+// f += f of the lane that DPP control word CTRL names (0 where there is none),
+// limb by limb: one level of a wave's sum.  row_shr:n = 0x110 + n; after the
+// row broadcasts only lane 31 / 63 holds the sum of the rows before it.
+constexpr int kDppShr1 = 0x111, kDppShr2 = 0x112, kDppShr4 = 0x114, kDppShr8 = 0x118;
+constexpr int kDppBcast15 = 0x142, kDppBcast31 = 0x143;
+template <int CTRL>
+__device__ __forceinline__ void dpp_add(F26& f) {
+    auto dpp = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, true); };
+    f.v0 += dpp(f.v0); f.v1 += dpp(f.v1); f.v2 += dpp(f.v2); f.v3 += dpp(f.v3); f.v4 += dpp(f.v4);
+}
+
 // sum_{e=1..m} x^e by binary doubling (G(2a) = G(a) + x^a G(a), G(a+1) = G(a) + x^(a+1))
 __device__ __forceinline__ F26 geo_sum(const F26 x, const uint32_t m) {
     F26 g = f26_zero(), pw = f26_one();
@@ -353,6 +382,37 @@ __device__ __forceinline__ void horner_step(H32& h, uint32_t m0, uint32_t m1, ui
     h.h4 = e4 + c;
 }
 
+// radix 2^32 -> 2^26 (h < 2^131: the bits from 2^130 up fold in as 5)
+__device__ __forceinline__ F26 h32_to_f26(const H32& h) {
+    F26 f = words_to_f26(h.h0, h.h1, h.h2, h.h3, 0u);
+    f.v4 += h.h4 << 24;
+    const uint32_t c = f.v4 >> 26;
+    f.v4 &= M26;
+    f.v0 += c * 5u;
+    return f;
+}
+
+// Poly1305 key of a record: keystream block 0 (chacha20_poly1305.rs:50,75),
+// r = clamp(pk[0..16]) (poly1305.rs:197-203) as radix-2^32 words, s = pk[16..32]
+// (chacha20_poly1305.rs:32-39)
+struct PolyKey {
+    uint32_t r0, r1, r2, r3;
+    uint32_t s[4];
+};
+__device__ __forceinline__ PolyKey poly_key(const uint32_t ks[16]) {
+    return PolyKey{ks[0] & 0x0fffffffu, ks[1] & 0x0ffffffcu, ks[2] & 0x0ffffffcu, ks[3] & 0x0ffffffcu,
+                   {ks[4], ks[5], ks[6], ks[7]}};
+}
+
+// Constant-time tag compare: diff |= a ^ b over all 16 bytes
+// (chacha20_poly1305.rs:84-87), the received and the computed tag as four
+// words each; the record's status byte, 1 = wrong mac.
+template <class A, class B>
+__device__ __forceinline__ uint8_t tag_mismatch(const A& rx, const B& tw) {
+    const uint32_t diff = (rx[0] ^ tw[0]) | (rx[1] ^ tw[1]) | (rx[2] ^ tw[2]) | (rx[3] ^ tw[3]);
+    return diff != 0u ? 1u : 0u;
+}
+
 // ---- per-record parameters ---------------------------------------------------
 struct RecKey {
     uint32_t k[8];
@@ -376,14 +436,21 @@ __device__ __forceinline__ RecKey record_key(const KParams& p, uint32_t rec) {
     } else {
         const uint8_t* nb = p.nonces + 8ull * rec;
         rk.seq = 0;
-        rk.n14 = (uint32_t)nb[0] | ((uint32_t)nb[1] << 8) | ((uint32_t)nb[2] << 16) | ((uint32_t)nb[3] << 24);
-        rk.n15 = (uint32_t)nb[4] | ((uint32_t)nb[5] << 8) | ((uint32_t)nb[6] << 16) | ((uint32_t)nb[7] << 24);
+        rk.n14 = le32(nb);
+        rk.n15 = le32(nb + 4);
     }
     return rk;
 }
 
 __device__ __forceinline__ uint32_t record_len(const KParams& p, uint32_t rec) {
     return p.len ? p.len[rec] : p.uniform_len;
+}
+// byte offset of record rec in the batch's input / output
+__device__ __forceinline__ uint64_t rec_in_off(const KParams& p, uint32_t rec) {
+    return p.in_off ? p.in_off[rec] : p.in_stride * rec;
+}
+__device__ __forceinline__ uint64_t rec_out_off(const KParams& p, uint32_t rec) {
+    return p.out_off ? p.out_off[rec] : p.out_stride * rec;
 }
 
 // AD byte i of the TLS record-layer additional data (tls.rs:103-112, 250-265):

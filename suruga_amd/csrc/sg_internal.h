@@ -1,5 +1,8 @@
-// sg_internal.h -- shared between the HIP kernels (sg_kernels.hip) and the
-// C-ABI host layer (sg_capi.cpp).  Not part of the public ABI.
+// sg_internal.h -- shared between the HIP kernel files (sg_kernels.hip,
+// sg_wpr.hip, sg_pack.hip, sg_plumb.hip), the mixed-batch dispatcher
+// (sg_dispatch.cpp) and the C-ABI host layer (sg_capi.cpp): the workspace and
+// keying-record layouts, the kernel parameters and every launch_* function.
+// Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -148,6 +151,23 @@ struct KeyJobs {
     uint32_t blk0[kNumClasses];  // first 64-record block of each job
     uint32_t njobs;
 };
+constexpr uint32_t kKeyingThreads = 64;  // records per keying workgroup
+
+// Launches of the size-class kernels (sg_kernels.hip).  Keying: `grid` blocks
+// of kKeyingThreads records over `jobs`, or every record of the batch by index.
+hipError_t launch_keying(const KParams& p, bool open, const KeyJobs& jobs, uint32_t grid, hipStream_t s);
+hipError_t launch_keying_all(const KParams& p, bool open, hipStream_t s);
+// bucket the batch into the kNumLists lists (populations and the over-long
+// count in counts); records longer than max_n get no list
+hipError_t launch_classify(const KParams& p, bool open, uint32_t* lists, uint32_t* counts, uint32_t max_n,
+                           hipStream_t s);
+// size class c: the whole batch by index (list NULL), or the listed records
+// -- n_exact: the class population when the host knows it (exact grid), or
+// UINT32_MAX for a persistent grid capped at kListGridPerCU workgroups per CU
+hipError_t launch_class(uint32_t c, const KParams& q, bool open, const uint32_t* list, const uint32_t* cnt,
+                        uint32_t n_exact, hipStream_t s);
+
+inline hipError_t mark(hipEvent_t ev, hipStream_t s) { return ev ? hipEventRecord(ev, s) : hipSuccess; }
 
 bool wpr_enabled();  // sg_set_lockstep / SG_LOCKSTEP environment switch
 int set_wpr(int enable);
@@ -170,7 +190,7 @@ const char* class_kernel_config();
 // the records longer than max_n, which are skipped (open: status 3); *over
 // receives that count when the populations are read back (not under capture).
 // ev_keyed / ev_start (may be NULL) are recorded after the keying pre-passes
-// (mixed batches: after classify, before the packed launch)
+// (mixed batches: after classify, before the packed launch)  (sg_dispatch.cpp)
 hipError_t launch_aead(const KParams& p, bool open, uint32_t max_n, bool uniform, hipStream_t s, uint32_t* over,
                        hipEvent_t ev_keyed, hipEvent_t ev_start);
 // Eligibility of one record of a mixed batch for the wave-per-record buckets:
@@ -190,6 +210,7 @@ int set_pack(int enable);
 hipError_t launch_pack(const KParams& p, bool open, const uint32_t* list, const uint32_t* cnt, uint32_t* ctr,
                        hipStream_t s);
 const char* pack_kernel_config();
+// ---- sg_plumb.hip ----
 // zero the output of every record whose open status is 1 (wrong mac)
 hipError_t launch_scrub(const KParams& p, hipStream_t s);
 // record-layer framing in HBM (sg_record.cpp zero-copy path): build the wire

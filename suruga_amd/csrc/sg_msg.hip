@@ -68,29 +68,17 @@ struct MsgKey {
 __device__ __forceinline__ MsgKey msg_key(const uint8_t* key, uint32_t n14, uint32_t n15) {
     MsgKey mk;
 #pragma unroll
-    for (int i = 0; i < 8; ++i)
-        mk.k[i] = uniform((uint32_t)key[4 * i] | ((uint32_t)key[4 * i + 1] << 8) | ((uint32_t)key[4 * i + 2] << 16) |
-                          ((uint32_t)key[4 * i + 3] << 24));
+    for (int i = 0; i < 8; ++i) mk.k[i] = uniform(le32(key + 4 * i));
     uint32_t ks[16];
     chacha_block(ks, mk.k, 0u, n14, n15);
-    mk.r0 = uniform(ks[0] & 0x0fffffffu);
-    mk.r1 = uniform(ks[1] & 0x0ffffffcu);
-    mk.r2 = uniform(ks[2] & 0x0ffffffcu);
-    mk.r3 = uniform(ks[3] & 0x0ffffffcu);
+    const PolyKey pk = poly_key(ks);
+    mk.r0 = uniform(pk.r0);
+    mk.r1 = uniform(pk.r1);
+    mk.r2 = uniform(pk.r2);
+    mk.r3 = uniform(pk.r3);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) mk.s[i] = uniform(ks[4 + i]);
+    for (int i = 0; i < 4; ++i) mk.s[i] = uniform(pk.s[i]);
     return mk;
-}
-
-// x^e by square-and-multiply (mul_add outputs are valid multipliers as they stand)
-__device__ __forceinline__ F26 fpow(const F26 x, const uint32_t e) {
-    F26 acc = f26_one();
-    if (e == 0u) return acc;
-    for (int bit = 31 - __builtin_clz(e); bit >= 0; --bit) {
-        acc = fmul(acc, acc);
-        if ((e >> bit) & 1u) acc = fmul(acc, x);
-    }
-    return acc;
 }
 
 // Sum of the 256 lanes' reduced elements, valid in lane 0 (limbs < 2^26 + 2^8).
@@ -288,13 +276,7 @@ __global__ __launch_bounds__(256) void sg_msg_kernel(const MsgParams p) {
                 }
                 horner_step(h, m.x, m.y, m.z, m.w, pad, r0, r1, r2, r3, s1, s2, s3);
             }
-            // radix 2^32 -> 2^26 (h < 2^131)
-            F26 f = words_to_f26(h.h0, h.h1, h.h2, h.h3, 0u);
-            f.v4 += h.h4 << 24;
-            const uint32_t c = f.v4 >> 26;
-            f.v4 &= M26;
-            f.v0 += c * 5u;
-            acc = fmul_add(acc, R, f);  // the lane's Horner chain over the group's tiles
+            acc = fmul_add(acc, R, h32_to_f26(h));  // the lane's Horner chain over the group's tiles
         }
         __syncthreads();  // the next tile's stores follow this tile's loads
     }
@@ -365,8 +347,8 @@ hipError_t launch_msg(const uint8_t* key, const uint8_t nonce[8], const uint8_t*
     p.n = n;
     p.adlen = adlen;
     // the nonce as two little-endian words (chacha20.rs:45-46)
-    p.n14 = (uint32_t)nonce[0] | ((uint32_t)nonce[1] << 8) | ((uint32_t)nonce[2] << 16) | ((uint32_t)nonce[3] << 24);
-    p.n15 = (uint32_t)nonce[4] | ((uint32_t)nonce[5] << 8) | ((uint32_t)nonce[6] << 16) | ((uint32_t)nonce[7] << 24);
+    p.n14 = dev::le32(nonce);
+    p.n15 = dev::le32(nonce + 4);
     p.plan = plan;
     if (open) {
         hipLaunchKernelGGL((sg_msg_kernel<true>), dim3(plan.groups), dim3(kMsgThreads), 0, s, p);

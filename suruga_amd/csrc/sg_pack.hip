@@ -20,7 +20,7 @@
 // The grid is persistent (three workgroups per CU) and takes runs from a
 // device counter until the list's population, read from the workspace, is
 // used up: the host launches it before it has read the populations back
-// (sg_kernels.hip, launch_aead_t), so the GPU runs it while the host waits.
+// (sg_dispatch.cpp, launch_aead), so the GPU runs it while the host waits.
 //
 //   setup (waves 0-1, one lane per record): keystream block 0 -> r, s
 //     (chacha20_poly1305.rs:50-52, poly1305.rs:197-203), the powers
@@ -54,6 +54,7 @@
 #include "sg_internal.h"
 #include "sg_device.h"
 #include "sg_chacha_grp.inc"  // grouped ChaCha20 double round (tools/gen_chacha_grp.py --product)
+#include "sg_env.h"
 
 // Barriers per double round of the grouped asm (generated next to the macro)
 // and a compile-time count of the macro text itself: the idle waves of a
@@ -77,7 +78,6 @@ static_assert(count_barriers(SG_CHACHA_DR_NB1_BAR1) == SG_CHACHA_DR_NB1_BAR1_BAR
 }  // namespace
 
 #include <stdint.h>
-#include <stdlib.h>
 
 namespace sg {
 namespace {
@@ -227,8 +227,8 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
         uint32_t* tb = L.tab + m0 * kTabWords;
         if (act) {
             const uint32_t len = record_len(p, rec);
-            const uint64_t io = p.in_off ? p.in_off[rec] : p.in_stride * rec;
-            const uint64_t oo = p.out_off ? p.out_off[rec] : p.out_stride * rec;
+            const uint64_t io = rec_in_off(p, rec);
+            const uint64_t oo = rec_out_off(p, rec);
             const RecKey rk = record_key(p, rec);
             const uint32_t n = OPEN ? len - 16u : len;  // listed records: 64 <= n <= 4096, n % 64 == 0
             nb = n >> 6;
@@ -238,22 +238,20 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
             SG_STAMP(0u, 8);
             uint32_t ks[16];
             chacha_block(ks, rk.k, 0u, rk.n14, rk.n15);  // block 0 -> poly key (chacha20_poly1305.rs:50,75)
-            // r = clamp(pk[0..16]) (poly1305.rs:197-203), s = pk[16..32] (chacha20_poly1305.rs:32-39)
-            const uint32_t r0 = ks[0] & 0x0fffffffu, r1 = ks[1] & 0x0ffffffcu;
-            const uint32_t r2w = ks[2] & 0x0ffffffcu, r3 = ks[3] & 0x0ffffffcu;
+            const PolyKey pk = poly_key(ks);
             SG_STAMP(0u, 9);
 #pragma unroll
             for (int i = 0; i < 8; ++i) sl[kSKey + i] = rk.k[i];
             sl[kSN14] = rk.n14;
             sl[kSN15] = rk.n15;
-            sl[kSR + 0] = r0; sl[kSR + 1] = r1; sl[kSR + 2] = r2w; sl[kSR + 3] = r3;
+            sl[kSR + 0] = pk.r0; sl[kSR + 1] = pk.r1; sl[kSR + 2] = pk.r2; sl[kSR + 3] = pk.r3;
             sl[kSIn] = (uint32_t)io; sl[kSIn + 1] = (uint32_t)(io >> 32);
             sl[kSOut] = (uint32_t)oo; sl[kSOut + 1] = (uint32_t)(oo >> 32);
-            sl[kSS + 0] = ks[4]; sl[kSS + 1] = ks[5]; sl[kSS + 2] = ks[6]; sl[kSS + 3] = ks[7];
+            sl[kSS + 0] = pk.s[0]; sl[kSS + 1] = pk.s[1]; sl[kSS + 2] = pk.s[2]; sl[kSS + 3] = pk.s[3];
             sl[kSNb] = nb;
             sl[kSRec] = rec;
             // hi[a] = r^(1 + 32 a), lo[b] = R^b (R = r^4), two product chains
-            const F26 r = words_to_f26(r0, r1, r2w, r3, 0u);
+            const F26 r = words_to_f26(pk.r0, pk.r1, pk.r2, pk.r3, 0u);
             const F26 r2 = fmul(r, r), R = fmul(r2, r2);
             F26 y = f26_one();
             uint32_t top = 0u;
@@ -433,10 +431,7 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
         if constexpr (!OPEN) {
             st16(p.out + oo + n, u32x4{tw[0], tw[1], tw[2], tw[3]});  // ct || tag (chacha20_poly1305.rs:55)
         } else {
-            // constant-time compare: diff |= a ^ b over all 16 bytes (chacha20_poly1305.rs:84-87)
-            const u32x4 rx = ld16(p.in + io + n);
-            const uint32_t diff = (rx[0] ^ tw[0]) | (rx[1] ^ tw[1]) | (rx[2] ^ tw[2]) | (rx[3] ^ tw[3]);
-            p.status[rec] = diff != 0u ? 1u : 0u;
+            p.status[rec] = tag_mismatch(ld16(p.in + io + n), tw);
         }
     }
     SG_STAMP(0u, 5);
@@ -491,21 +486,9 @@ extern "C" int sg_pack_profile_read(unsigned long long* host, size_t n) {
 }
 #endif
 
-static int g_pack = -1;  // -1: not read from the environment yet
-bool pack_enabled() {
-    if (__atomic_load_n(&g_pack, __ATOMIC_ACQUIRE) < 0) {
-        const char* e = getenv("SG_PACK");
-        int expect = -1;
-        __atomic_compare_exchange_n(&g_pack, &expect, e ? (e[0] == '1' ? 1 : 0) : 1, false,
-                                    __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE);
-    }
-    return __atomic_load_n(&g_pack, __ATOMIC_ACQUIRE) == 1;
-}
-int set_pack(int enable) {
-    const int prev = pack_enabled() ? 1 : 0;
-    if (enable >= 0) __atomic_store_n(&g_pack, enable ? 1 : 0, __ATOMIC_RELEASE);
-    return prev;
-}
+static EnvSwitch g_pack{"SG_PACK"};
+bool pack_enabled() { return g_pack.on(); }
+int set_pack(int enable) { return g_pack.set(enable); }
 
 const char* pack_kernel_config() {
     return "sg_pack_kernel v5: mixed-batch TLS records of 64 B-4 KiB (multiples of 64 B) packed 64-byte block per lane "

@@ -53,9 +53,9 @@
 #include "sg_internal.h"
 #include "sg_device.h"
 #include "sg_chacha_grp.inc"  // grouped ChaCha20 double round (tools/gen_chacha_grp.py --product)
+#include "sg_env.h"
 
 #include <stdint.h>
-#include <stdlib.h>
 
 namespace sg {
 namespace {
@@ -191,12 +191,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
         rk = record_key(p, rec);
         uint32_t ks[16];
         chacha_block(ks, rk.k, 0u, rk.n14, rk.n15);  // block 0 -> poly key (chacha20_poly1305.rs:50,75)
-        // r = clamp(pk[0..16]) (poly1305.rs:197-203), s = pk[16..32] (chacha20_poly1305.rs:32-39)
-        r = words_to_f26(ks[0] & 0x0fffffffu, ks[1] & 0x0ffffffcu, ks[2] & 0x0ffffffcu, ks[3] & 0x0ffffffcu, 0u);
-        s[0] = ks[4]; s[1] = ks[5]; s[2] = ks[6]; s[3] = ks[7];
+        const PolyKey pk = poly_key(ks);
+        r = words_to_f26(pk.r0, pk.r1, pk.r2, pk.r3, 0u);
+        s[0] = pk.s[0]; s[1] = pk.s[1]; s[2] = pk.s[2]; s[3] = pk.s[3];
         if constexpr (LIST) {  // the slot's descriptor: where the record lives, its length and nonce
-            const uint64_t io = p.in_off ? p.in_off[rec] : p.in_stride * rec;
-            const uint64_t oo = p.out_off ? p.out_off[rec] : p.out_stride * rec;
+            const uint64_t io = rec_in_off(p, rec);
+            const uint64_t oo = rec_out_off(p, rec);
             uint32_t ki = p.key_index ? p.key_index[rec] : 0u;
             ki = ki < p.num_keys ? ki : p.num_keys - 1u;  // (record_key's clamp)
             uint32_t* d = wl.desc + (uint64_t)slot * kWprDescWords;
@@ -1066,16 +1066,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         }
         F26 f = fmul(reduce_words8(xw), W);
         {  // sum the 64 lane terms into lane 63: row_shr 1, 2, 4, 8, row_bcast:15, carry, row_bcast:31
-            auto level = [&](auto dpp) {
-                f.v0 += dpp(f.v0); f.v1 += dpp(f.v1); f.v2 += dpp(f.v2); f.v3 += dpp(f.v3); f.v4 += dpp(f.v4);
-            };
-            level([](uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true); });
-            level([](uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true); });
-            level([](uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true); });
-            level([](uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true); });
-            level([](uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xf, 0xf, true); });
+            dpp_add<kDppShr1>(f);
+            dpp_add<kDppShr2>(f);
+            dpp_add<kDppShr4>(f);
+            dpp_add<kDppShr8>(f);
+            dpp_add<kDppBcast15>(f);
             f = carry1(f);
-            level([](uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xf, 0xf, true); });
+            dpp_add<kDppBcast31>(f);
         }
         auto lane63 = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, 63); };
         const F26 fs = {lane63(f.v0) + ctot.v0, lane63(f.v1) + ctot.v1, lane63(f.v2) + ctot.v2,
@@ -1086,10 +1083,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             if constexpr (!OPEN) {
                 st16(outb + n, u32x4{tw[0], tw[1], tw[2], tw[3]});  // ct || tag (chacha20_poly1305.rs:55)
             } else {
-                // constant-time compare: diff |= a ^ b over all 16 bytes (chacha20_poly1305.rs:84-87)
                 const uint32_t* rxl = reinterpret_cast<const uint32_t*>(lines + kWprRxOff);
-                const uint32_t diff = (rxl[0] ^ tw[0]) | (rxl[1] ^ tw[1]) | (rxl[2] ^ tw[2]) | (rxl[3] ^ tw[3]);
-                p.status[cd.rec] = diff != 0u ? 1u : 0u;
+                p.status[cd.rec] = tag_mismatch(rxl, tw);
             }
         }
         g = gn;
@@ -1178,8 +1173,7 @@ hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_
         hipLaunchKernelGGL((sg_wpr_keying_kernel<false, false>), dim3(kgrid), dim3(kWprKeyThreads), 0, s, p, jobs);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (ev_keyed && (e = hipEventRecord(ev_keyed, s)) != hipSuccess) return e;
-    if (ev_start && (e = hipEventRecord(ev_start, s)) != hipSuccess) return e;
+    if ((e = mark(ev_keyed, s)) != hipSuccess || (e = mark(ev_start, s)) != hipSuccess) return e;
     int cus = 0;
     if ((e = device_cus(&cus)) != hipSuccess) return e;
     const uint32_t grid = wpr_grid(cus, p.count);
@@ -1229,21 +1223,9 @@ hipError_t launch_wpr_list(const KParams& p, bool open, uint32_t J, const WprLis
     return hipGetLastError();
 }
 
-static int g_wpr = -1;  // -1: not read from the environment yet
-bool wpr_enabled() {
-    if (__atomic_load_n(&g_wpr, __ATOMIC_ACQUIRE) < 0) {
-        const char* e = getenv("SG_LOCKSTEP");
-        int expect = -1;
-        __atomic_compare_exchange_n(&g_wpr, &expect, e ? (e[0] == '1' ? 1 : 0) : 1, false,
-                                    __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE);
-    }
-    return __atomic_load_n(&g_wpr, __ATOMIC_ACQUIRE) == 1;
-}
-int set_wpr(int enable) {
-    const int prev = wpr_enabled() ? 1 : 0;
-    if (enable >= 0) __atomic_store_n(&g_wpr, enable ? 1 : 0, __ATOMIC_RELEASE);
-    return prev;
-}
+static EnvSwitch g_wpr{"SG_LOCKSTEP"};
+bool wpr_enabled() { return g_wpr.on(); }
+int set_wpr(int enable) { return g_wpr.set(enable); }
 
 const char* wpr_kernel_config() {
     return "sg_wpr_kernel v17: full 16 KiB records, one wave per record (8 per 512-thread workgroup, persistent "

@@ -17,7 +17,10 @@
 //     explicit nonce / AD bytes, each against a plain statement below;
 //   * suruga_amd/csrc/sg_copy_pool.cpp -- the framing copies' thread pool:
 //     every index exactly once, concurrent callers, and no touch of a job
-//     after its run() has returned.
+//     after its run() has returned;
+//   * suruga_amd/csrc/sg_env.h -- the EnvSwitch behind sg_set_lockstep and
+//     sg_set_packed: what the environment means, that it is read once, and the
+//     setter's return values.
 //
 // -DSG_POOL_ONLY builds the pool's checks alone (with sg_copy_pool.cpp), for
 // the ThreadSanitizer run.
@@ -37,6 +40,7 @@
 
 #include "../../include/suruga_gpu.h"
 #include "../../suruga_amd/csrc/sg_copy_pool.h"
+#include "../../suruga_amd/csrc/sg_env.h"
 #include "../../suruga_amd/csrc/sg_err.h"
 #include "../../suruga_amd/csrc/sg_wire.h"
 
@@ -368,6 +372,35 @@ static void keysched() {
     CHECK(sg_derive_keys(1, pm.data(), 65, 65, cr.data(), sr.data(), nullptr, c1.data(), s1.data(), 1) == SG_E_ARG);
 }
 
+// ---- the environment switches ------------------------------------------------
+// sg_env.h's EnvSwitch (SG_LOCKSTEP, SG_PACK): read once, unset = on, set = on
+// only for a leading '1', set(< 0) only reports.
+static void env_switch() {
+    const char* name = "SG_TEST_SWITCH";
+    unsetenv(name);
+    sg::EnvSwitch unset{name};
+    CHECK(unset.on());
+    for (const char* v : {"0", "", "2"}) {
+        setenv(name, v, 1);
+        sg::EnvSwitch off{name};
+        CHECK(!off.on());
+    }
+    setenv(name, "1", 1);
+    sg::EnvSwitch sw{name};
+    CHECK(sw.on());
+    setenv(name, "0", 1);  // a second read after setenv changes nothing
+    CHECK(sw.on());
+    CHECK(sw.set(-1) == 1 && sw.on());  // set(-1) changes nothing
+    CHECK(sw.set(0) == 1 && !sw.on());
+    CHECK(sw.set(-1) == 0 && !sw.on());
+    CHECK(sw.set(7) == 0 && sw.on());
+    setenv(name, "1", 1);  // set() reads the environment first, once
+    sg::EnvSwitch first_set{name};
+    CHECK(first_set.set(0) == 1 && !first_set.on());
+    unsetenv(name);
+    CHECK(!first_set.on() && sw.on());
+}
+
 #endif  // !SG_POOL_ONLY
 
 // ---- the copy pool -------------------------------------------------------------
@@ -424,6 +457,7 @@ int main() {
     chunk_shapes();
     explicit_meta();
     keysched();
+    env_switch();
 #endif
     copy_pool();
     if (g_fail) {

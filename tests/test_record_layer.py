@@ -551,7 +551,7 @@ def test_gpu_zero_copy_mixed_chunks(gpu, oracle):
 
 def test_frame_record_index_math():
     """sg_frame_kernel finds the wire record of destination byte b as
-    r = (b * rdiv) >> 40, rdiv = ceil(2^40 / pitch) (sg_kernels.hip), for
+    r = (b * rdiv) >> 40, rdiv = ceil(2^40 / pitch) (sg_plumb.hip), for
     images below 2^24 bytes (launch_frame's guard).  Exact for every pitch a
     wire record can have (5-byte header + 16..2^14+16 byte fragment, and any
     pitch below 2^16): the error term b (rdiv pitch - 2^40) / 2^40 stays below

@@ -12,8 +12,8 @@ restatement; run it under ASan/UBSan in this container").
    limbs aborts.
 3. The library's host-only sources -- the record header parser that takes a
    peer's bytes and the framing arithmetic (sg_wire.cpp, tls.rs:217-238), the
-   key schedule (sg_keysched.cpp) and the framing copies' thread pool
-   (sg_copy_pool.cpp) -- built with g++ -fsanitize=address,undefined into
+   key schedule (sg_keysched.cpp), the framing copies' thread pool
+   (sg_copy_pool.cpp) and the environment switch (sg_env.h) -- built with g++ -fsanitize=address,undefined into
    tests/cpp/test_host_san.cpp's corpus run.
 4. The thread pool's checks of the same program alone under ThreadSanitizer.
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static ISA census of every product kernel -> profiles/isa_<source hash>.json.
 
-Compiles the three HIP sources with the product flags and --save-temps (CPU
+Compiles the record kernels' HIP sources with the product flags and --save-temps (CPU
 only, hipcc cross-compiles gfx950), then runs tools/isa_count.py's census on
 each kernel: its record loop (the body between the loop header and its
 back-edge) for the persistent kernels, otherwise the whole function.  Per
@@ -96,7 +96,8 @@ def main():
     with tempfile.TemporaryDirectory(prefix="sg_isa_") as td:
         wd = keep or Path(td)
         kernels = {}
-        for s in (_build.CSRC / "sg_wpr.hip", _build.CSRC / "sg_pack.hip", _build.CSRC / "sg_kernels.hip"):
+        for s in (_build.CSRC / "sg_wpr.hip", _build.CSRC / "sg_pack.hip", _build.CSRC / "sg_kernels.hip",
+                  _build.CSRC / "sg_plumb.hip"):
             flags = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-mllvm",
                      "-amdgpu-atomic-optimizer-strategy=None", "--save-temps", f'-DSG_SOURCE_HASH="{src}"']
             subprocess.run([_build.hipcc(), *flags, "-c", "-o", str(wd / f"{s.stem}.o"), str(s)], cwd=wd, check=True,

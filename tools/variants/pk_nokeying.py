@@ -10,7 +10,7 @@ EDITS = [
     ("sg_pack.hip", """            uint32_t ks[16];
             chacha_block(ks, rk.k, 0u, rk.n14, rk.n15);  // block 0 -> poly key (chacha20_poly1305.rs:50,75)""",
      """            uint32_t ks[16] = {0x0a1b2c3du, 0x04050607u, 0x08090a0bu, 0x0c0d0e0fu, rk.k[0], rk.k[1], rk.k[2], rk.k[3]};"""),
-    ("sg_pack.hip", """            const F26 r = words_to_f26(r0, r1, r2w, r3, 0u);
+    ("sg_pack.hip", """            const F26 r = words_to_f26(pk.r0, pk.r1, pk.r2, pk.r3, 0u);
             const F26 r2 = fmul(r, r), R = fmul(r2, r2);
             F26 y = f26_one();
             uint32_t top = 0u;
@@ -26,7 +26,7 @@ EDITS = [
                 top |= tab_put(tb, a, z);
                 if (a < 7) z = fmul(z, R8);
             }
-            tb[kTabTop] = top;""", """            const F26 r = words_to_f26(r0, r1, r2w, r3, 0u);
+            tb[kTabTop] = top;""", """            const F26 r = words_to_f26(pk.r0, pk.r1, pk.r2, pk.r3, 0u);
             const F26 R = r;
             uint32_t top = 0u;
 #pragma unroll
