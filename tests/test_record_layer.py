@@ -566,3 +566,218 @@ def test_frame_record_index_math():
     rdiv = np.uint64(-(-(1 << 40) // pitch))
     b = np.arange(limit, dtype=np.uint64)
     assert np.array_equal((b * rdiv) >> np.uint64(40), b // np.uint64(pitch))
+
+
+# ---- GPU: the record layer writes only its own bytes ---------------------------
+# Every caller buffer is a window into a numpy array with 4096 sentinel bytes in
+# front and behind (tests/footprint.py), at byte offsets 0..3 from the array's
+# aligned start: the wire's partial first and last words (sg_frame_kernel, the
+# kernel-store form of the write), the head bytes and the funnel shift of
+# sg_copy_out_kernel and the last partial word per record of sg_unframe_kernel
+# all show in the margins if they are off by a byte.  Registered runs register
+# the whole array, margins included, so that a stray store lands in checked
+# memory.
+RL_MARGIN = 4096
+_rl_cache: dict = {}
+
+
+def _window(size, off, salt):
+    """(array, window): `size` bytes at RL_MARGIN + off of a sentinel array."""
+    import footprint as fp
+
+    base = fp.sentinel(RL_MARGIN + off + size + RL_MARGIN, salt)
+    return base, base[RL_MARGIN + off:RL_MARGIN + off + size]
+
+
+def _margins_intact(base, off, used, salt):
+    """None, or where the array differs from the sentinel outside [RL_MARGIN + off, + used)."""
+    import footprint as fp
+
+    want = fp.sentinel(base.size, salt)
+    lo, hi = RL_MARGIN + off, RL_MARGIN + off + used
+    want[lo:hi] = base[lo:hi]
+    return fp.first_diff(base, want, [(lo, hi)])
+
+
+def _registered(lib, arrays, on):
+    import contextlib
+
+    from suruga_amd import _native as N
+
+    @contextlib.contextmanager
+    def cm():
+        done = []
+        try:
+            if on:
+                for a in arrays:
+                    N.check(lib.sg_host_register(a.ctypes.data, a.nbytes))
+                    done.append(a)
+            yield
+        finally:
+            for a in done:
+                N.check(lib.sg_host_unregister(a.ctypes.data))
+
+    return cm()
+
+
+def _stream(oracle, key, seq0, lens, seed):
+    """(data, wire, wire offsets) of records of `lens` plaintext bytes: header || oracle.seal."""
+    import numpy as np
+
+    k = (key, seq0, tuple(lens), seed)
+    if k not in _rl_cache:
+        data = oracle.fill_record(seed, 2, sum(lens))
+        pieces, pos = [], 0
+        for r, n in enumerate(lens):
+            ct = oracle.seal(key, struct.pack(">Q", seq0 + r), data[pos:pos + n], oracle.tls_ad(seq0 + r, n))
+            pieces.append(bytes([23, 3, 3]) + struct.pack(">H", n + 16) + ct)
+            pos += n
+        woff = np.concatenate([[0], np.cumsum([len(p) for p in pieces])]).astype(np.int64)
+        _rl_cache[k] = (np.frombuffer(data, dtype=np.uint8), np.frombuffer(b"".join(pieces), dtype=np.uint8), woff)
+    return _rl_cache[k]
+
+
+FOOT_TOTAL = 258 * RECORD_MAX_LEN + 4321  # two chunks, the second ending in a ragged record
+FOOT_LENS = [RECORD_MAX_LEN] * 258 + [4321]
+FOOT_KEY, FOOT_SEQ0 = bytes(range(13, 45)), 11
+
+
+# the last chunk's wire image ends 1, 2 and 3 bytes into a word (FOOT_LENS ends on a word)
+FOOT_RAGGED = [[RECORD_MAX_LEN, RECORD_MAX_LEN, 4322 + k] for k in range(3)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("registered", [False, True])
+def test_gpu_write_records_footprint(gpu, oracle, registered):
+    """sg_write_records into a wire at byte offsets 0..3, from data at offsets 0 and 3:
+    every wire byte equals header || oracle.seal, everything before `wire` and from
+    wire + wire_len to the end of the array is sentinel, `data` is unchanged.  Two
+    chunks ending in a ragged record, and three short streams whose wire image ends
+    inside a word (the frame kernel's last partial word)."""
+    import ctypes as C
+
+    import numpy as np
+
+    import footprint as fp
+    from suruga_amd import ChaCha20Poly1305
+    from suruga_amd import _native as N
+
+    lib = N.load()
+    enc = ChaCha20Poly1305().new_encryptor(FOOT_KEY)
+    residues = set()
+    for lens in [FOOT_LENS] + FOOT_RAGGED:
+        total = sum(lens)
+        data, want, _ = _stream(oracle, FOOT_KEY, FOOT_SEQ0, lens, 0x71)
+        residues.add(want.size % 4)
+        cap = lib.sg_wire_bound(total)
+        assert cap >= want.size
+        for doff in (0, 3):
+            dbase, dwin = _window(total, doff, 0x21)
+            dwin[:] = data
+            dcopy = dbase.copy()
+            for woff in (0, 1, 2, 3):
+                wbase, wwin = _window(cap, woff, 0x43)
+                with _registered(lib, (dbase, wbase), registered):
+                    wl = C.c_size_t(0)
+                    nrec = N.check(lib.sg_write_records(enc._ptr, FOOT_SEQ0, 23, 3, 3, dwin.ctypes.data, total,
+                                                        wwin.ctypes.data, cap, C.byref(wl)))
+                what = f"{total} bytes, data offset {doff}, wire offset {woff}"
+                assert (nrec, wl.value) == (len(lens), want.size), what
+                assert (d := fp.first_diff(wwin[:want.size], want)) is None, f"{what}: wire {d}"
+                assert (d := _margins_intact(wbase, woff, want.size, 0x43)) is None, f"{what}: outside the wire, {d}"
+                assert np.array_equal(dbase, dcopy), f"{what}: data changed"
+    assert residues == {0, 1, 2, 3}
+
+
+def _read_footprint(lib, dec, seq0, wire, wlen_off, ooff, out_size, registered, nrec_cap):
+    """One sg_read_records of `wire` (placed at byte offset wlen_off) into a window at
+    byte offset ooff; returns (result, out array, out window, types, frag_lens)."""
+    import ctypes as C
+
+    import numpy as np
+
+    from suruga_amd import _native as N
+
+    wbase, wwin = _window(wire.size, wlen_off, 0x65)
+    wwin[:] = wire
+    wcopy = wbase.copy()
+    obase, owin = _window(out_size, ooff, 0x87)
+    types = np.full(nrec_cap + 64, 0xC3, dtype=np.uint8)
+    frags = np.full(nrec_cap + 16, 0xA5A5A5A5, dtype=np.uint32)
+    res = N.SgReadResult()
+    with _registered(lib, (wbase, obase), registered):
+        N.check(lib.sg_read_records(dec._ptr, seq0, wwin.ctypes.data, wire.size, owin.ctypes.data, out_size,
+                                    types.ctypes.data, frags.ctypes.data, nrec_cap, C.byref(res)))
+    assert np.array_equal(wbase, wcopy), "the wire changed"
+    return res, obase, owin, types, frags
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("registered", [False, True])
+def test_gpu_read_records_footprint_full_records(gpu, oracle, registered):
+    """The same stream read from a wire at offsets 0..3 into `out` at offsets 0..3:
+    `out` holds exactly the plaintext, both of its margins, and `types` / `frag_lens`
+    past `records`, are as they were."""
+    import numpy as np
+
+    from suruga_amd import ChaCha20Poly1305
+    from suruga_amd import _native as N
+
+    lib = N.load()
+    data, wire, _ = _stream(oracle, FOOT_KEY, FOOT_SEQ0, FOOT_LENS, 0x71)
+    dec = ChaCha20Poly1305().new_decryptor(FOOT_KEY)
+    nrec = len(FOOT_LENS)
+    for woff in (0, 1, 2, 3):
+        for ooff in (0, 1, 2, 3):
+            what = f"wire offset {woff}, out offset {ooff}"
+            res, obase, owin, types, frags = _read_footprint(lib, dec, FOOT_SEQ0, wire, woff, ooff, FOOT_TOTAL,
+                                                             registered, nrec)
+            assert (res.records, res.consumed, res.out_len, res.error) == (nrec, wire.size, FOOT_TOTAL, N.SG_OK), what
+            assert np.array_equal(owin, data), what
+            assert (d := _margins_intact(obase, ooff, FOOT_TOTAL, 0x87)) is None, f"{what}: outside out, {d}"
+            assert (types[:nrec] == 23).all() and (types[nrec:] == 0xC3).all(), what
+            assert frags[:nrec].tolist() == FOOT_LENS and (frags[nrec:] == 0xA5A5A5A5).all(), what
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("registered", [False, True])
+def test_gpu_read_records_footprint_odd_equal_records(gpu, oracle, registered):
+    """260 records of 1001 bytes: the second chunk's out0 = 256 * 1001 is 4-byte
+    aligned, so the offset of `out` (0..3) is what makes the destination of the
+    zero-copy read's copy kernel odd.  The full read is exact; with one record per
+    chunk corrupted the delivered bytes are exact, every byte of an undelivered
+    record is 0 or what it was, and the margins are as they were."""
+    import numpy as np
+
+    import footprint as fp
+    from suruga_amd import ChaCha20Poly1305
+    from suruga_amd import _native as N
+
+    lib = N.load()
+    n, count, seq0, key = 1001, 260, 9, bytes(range(17, 49))
+    total, pitch = n * count, 5 + n + 16
+    data, wire, _ = _stream(oracle, key, seq0, [n] * count, 0x3D)
+    dec = ChaCha20Poly1305().new_decryptor(key)
+    for woff in (0, 1, 2, 3):
+        for ooff in (0, 1, 2, 3):
+            what = f"wire offset {woff}, out offset {ooff}"
+            res, obase, owin, types, frags = _read_footprint(lib, dec, seq0, wire, woff, ooff, total, registered, count)
+            assert (res.records, res.consumed, res.out_len, res.error) == (count, wire.size, total, N.SG_OK), what
+            assert np.array_equal(owin, data), what
+            assert (d := _margins_intact(obase, ooff, total, 0x87)) is None, f"{what}: outside out, {d}"
+            assert (types[count:] == 0xC3).all() and (frags[count:] == 0xA5A5A5A5).all(), what
+            assert (frags[:count] == n).all(), what
+            for bad, pos in ((100, 7), (258, n - 1)):  # first chunk; second chunk, the last byte
+                broken = wire.copy()
+                broken[bad * pitch + 5 + pos] ^= 0x01
+                res, obase, owin, types, frags = _read_footprint(lib, dec, seq0, broken, woff, ooff, total, registered,
+                                                                 count)
+                w = f"{what}, record {bad} corrupted"
+                assert (res.records, res.out_len, res.error) == (bad, bad * n, N.SG_E_BAD_MAC), w
+                assert np.array_equal(owin[:bad * n], data[:bad * n]), w
+                before = fp.sentinel(obase.size, 0x87)[RL_MARGIN + ooff:RL_MARGIN + ooff + total]
+                rest = owin[bad * n:]
+                assert ((rest == 0) | (rest == before[bad * n:])).all(), f"{w}: bytes of undelivered records in out"
+                assert (d := _margins_intact(obase, ooff, total, 0x87)) is None, f"{w}: outside out, {d}"
+                assert (types[count:] == 0xC3).all(), w
+                assert (frags[count:] == 0xA5A5A5A5).all(), w
