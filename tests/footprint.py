@@ -24,6 +24,8 @@ import struct
 
 import numpy as np
 
+from mac_forge import size_class  # noqa: F401  (one definition; fp.size_class stays the model's name for it)
+
 MARGIN = 256
 GAPS = (0, 1, 2, 3, 5, 8, 15, 16, 17, 63)
 GAPS_ALIGNED = (0, 16, 48)
@@ -148,13 +150,6 @@ def first_diff(got: np.ndarray, want: np.ndarray, rs=()):
 # ---------------------------------------------------------------------------
 # route predicates (n: plaintext bytes of the record)
 # ---------------------------------------------------------------------------
-def size_class(n: int) -> int:
-    """sg_internal.h size_class: class c holds n <= 128 << c, class 7 the rest."""
-    if n <= 128:
-        return 0
-    return min(((n - 1) >> 7).bit_length(), 7)
-
-
 def uniform_wpr(n: int, listed: bool, in_base: int, out_base: int, in_stride: int, out_stride: int,
                 lockstep: bool = True) -> bool:
     """wpr_eligible: a uniform batch (no len / offset arrays) of full 16 KiB

@@ -50,6 +50,7 @@ def poly_key(key: bytes, nonce: bytes):
 
 
 def mac_stream(ad: bytes, ct: bytes) -> bytes:
+    """chacha20_poly1305.rs:19-42: ad || le64(|ad|) || ct || le64(|ct|), no padding."""
     return bytes(ad) + struct.pack("<Q", len(ad)) + bytes(ct) + struct.pack("<Q", len(ct))
 
 

@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 import footprint as fp
+from gpu_support import dev_u8 as to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -30,16 +31,6 @@ M = fp.MARGIN
 BASES = (0, 1, 4, 8, 15)
 COMPARE_LENGTHS = (1, 15, 16, 17, 31, 32, 33, 255, 4097, 16384)
 WRAP = range(4079, 4113)  # thread 255 of the vector loop's first pass ends at byte 4095, thread 0 goes on at 4096
-
-
-def torch_mod():
-    import torch
-
-    return torch
-
-
-def to_dev(a: np.ndarray):
-    return torch_mod().from_numpy(np.ascontiguousarray(a)).to("cuda")
 
 
 def strides_of(n: int):
@@ -81,9 +72,10 @@ class Pair:
 
     def device_adds(self, initial: int) -> int:
         """What sg_compare_records adds to a counter that starts at `initial`."""
+        import torch
+
         from suruga_amd import batch as B
 
-        torch = torch_mod()
         ctr = torch.full((3,), 0x7777, dtype=torch.int64, device="cuda")
         ctr[1] = initial
         B.compare_records(self.da[M + self.ba:], self.sa, self.db[M + self.bb:], self.sb, self.n, self.count, ctr[1:],

@@ -32,79 +32,36 @@ import pytest
 
 import footprint as fp
 import mac_forge as F
+from gpu_support import BatchCase, dev_u8 as to_dev, dev_u32, dev_u64, host_np as host, mode_of
+from gpu_support import groups, lockstep, packed  # noqa: F401  (fixtures)
+from suruga_amd._native import SG_E_ARG, SG_E_BAD_MAC, SG_E_SHORT, SG_OK
 
 pytestmark = pytest.mark.gpu
 
-SG_OK, SG_E_BAD_MAC, SG_E_SHORT, SG_E_ARG = 0, 1, 2, -1
 KEY = fp.KEY
 M = fp.MARGIN
 STATUS_PAD = 64
-
-
-def torch_mod():
-    import torch
-
-    return torch
-
-
-def to_dev(a: np.ndarray):
-    t = torch_mod().from_numpy(np.array(a, dtype=np.uint8)).to("cuda")
-    assert t.data_ptr() % 16 == 0  # the route predicates take buffer offsets for addresses
-    return t
-
-
-def dev_u64(vals):
-    return torch_mod().from_numpy(np.array(vals, dtype=np.uint64).view(np.int64)).to("cuda")
-
-
-def dev_u32(vals):
-    return torch_mod().from_numpy(np.array(vals, dtype=np.uint32).view(np.int32)).to("cuda")
-
-
-def host(t) -> np.ndarray:
-    return t.cpu().numpy()
 
 
 def u8(b: bytes) -> np.ndarray:
     return np.frombuffer(bytes(b), dtype=np.uint8)
 
 
-@pytest.fixture
-def lockstep(gpu):
-    prev = gpu.sg_set_lockstep(-1)
-    yield gpu.sg_set_lockstep
-    gpu.sg_set_lockstep(prev)
-
-
-@pytest.fixture
-def packed(gpu):
-    prev = gpu.sg_set_packed(-1)
-    yield gpu.sg_set_packed
-    gpu.sg_set_packed(prev)
-
-
-@pytest.fixture
-def groups(gpu):
-    prev = gpu.sg_set_msg_groups(-1)
-    yield gpu.sg_set_msg_groups
-    gpu.sg_set_msg_groups(prev)
-
-
 records, is_tampered = fp.records, fp.is_tampered
 
 
-def mode_kwargs(recs, mode, seq0):
-    if mode == "tls":
-        return dict(seq0=seq0)
-    stride = max(mode, 1)
-    return dict(tls=False, nonces=to_dev(u8(b"".join(r.nonce for r in recs))),
-                ads=to_dev(u8(b"".join(r.ad.ljust(stride, b"\0") for r in recs))), ad_len=mode, ad_stride=stride)
+def common_args(recs, mode, seq0) -> dict:
+    """count, keys, the mode and the NULL stream (every call here ends before it returns)."""
+    case = BatchCase(np.zeros(len(recs)), None, KEY, **mode_of(recs, mode, seq0))
+    return dict(case.common(), stream=0)
 
 
 def call(gpu, batch, open_: bool) -> int:
+    import torch
+
     cb = batch.to_c()
     rc = (gpu.sg_open_batch if open_ else gpu.sg_seal_batch)(C.byref(cb))
-    torch_mod().cuda.synchronize()
+    torch.cuda.synchronize()
     return rc
 
 
@@ -129,7 +86,6 @@ def run_listed(gpu, oracle, plan, mode, expect_routes, lockstep_on=True, packed_
 
     all_lens, count, max_n, i_short, i_long = plan.all_lens, plan.count, plan.max_n, plan.i_short, plan.i_long
     recs = records(oracle, all_lens, mode, seq0)
-    keys = to_dev(u8(KEY)).view(1, 32)
     tls = mode == "tls"
 
     # ---- seal: the short record is an ordinary 7-byte one, the long one is skipped
@@ -142,7 +98,7 @@ def run_listed(gpu, oracle, plan, mode, expect_routes, lockstep_on=True, packed_
     in_img = fp.image(in_size, 0x77, [(in_off[i], recs[i].pt) for i in range(count)])
     out_img = fp.image(out_size, salt, parts)
     d_in, d_out = to_dev(in_img), to_dev(fp.sentinel(out_size, salt))
-    common = dict(count=count, keys=keys, stream=0, **mode_kwargs(recs, mode, seq0))
+    common = common_args(recs, mode, seq0)
     rc = call(gpu, B.Batch(inp=d_in, out=d_out, lens=dev_u32(in_lens), max_len=max_n, in_off=dev_u64(in_off),
                            out_off=dev_u64(out_off), **common), False)
     assert rc == SG_E_ARG, "seal: a record longer than max_len returns SG_E_ARG"
@@ -204,8 +160,7 @@ def run_uniform(gpu, oracle, n, count, mode, gaps, bases, want_wpr, seq0=77):
     from suruga_amd import batch as B
 
     recs = records(oracle, [n] * max(count, max(fp.WPR_COUNTS) if n == fp.WPR_N else 0), mode, seq0)[:count]
-    keys = to_dev(u8(KEY)).view(1, 32)
-    common = dict(count=count, keys=keys, stream=0, **mode_kwargs(recs, mode, seq0))
+    common = common_args(recs, mode, seq0)
 
     def one(what, open_, inputs, outputs, in_len, out_len, g, b, st_want, keep=False):
         si, so = in_len + g, out_len + g
@@ -296,6 +251,8 @@ def msg_cases(r):
 
 
 def run_msg(r, off, in_place):
+    import torch
+
     from suruga_amd import msg
 
     key_t, adt = to_dev(u8(KEY)), to_dev(u8(MSG_AD))
@@ -327,7 +284,7 @@ def run_msg(r, off, in_place):
             st = host(d_st)
             assert st[0] == st_want, (what, int(st[0]))
             assert np.array_equal(st[1:], fp.sentinel(1 + STATUS_PAD, 0x51)[1:]), f"{what}: status past its byte"
-        torch_mod().cuda.synchronize()
+        torch.cuda.synchronize()
         assert (d := fp.first_diff(host(d_out), out_img, [(M + off, M + off + len(want))])) is None, f"{what}: {d}"
         if not in_place:
             assert (d := fp.first_diff(host(d_whole), in_img)) is None, f"{what}: input changed, {d}"
@@ -348,6 +305,8 @@ def test_long_message_device_form(gpu, oracle, groups, g):
 
 
 def test_long_message_short_input_touches_nothing(gpu):
+    import torch
+
     from suruga_amd import msg
 
     key_t = to_dev(u8(KEY))
@@ -355,7 +314,7 @@ def test_long_message_short_input_touches_nothing(gpu):
     d_st = to_dev(fp.sentinel(1 + STATUS_PAD, 0x51))
     for n in (0, 1, 15):
         assert msg.open_(key_t, bytes(8), d_in, d_out[M + 1:], d_st, in_len=n, stream=0) == SG_E_SHORT
-    torch_mod().cuda.synchronize()
+    torch.cuda.synchronize()
     assert np.array_equal(host(d_out), fp.sentinel(2 * M + 32, 2))
     assert np.array_equal(host(d_st), fp.sentinel(1 + STATUS_PAD, 0x51))
 

@@ -10,7 +10,7 @@ import struct
 import numpy as np
 import pytest
 
-from test_gpu_parity import KEY, SEED, dev_bytes, tls_batch, torch_mod
+from gpu_support import KEY, SEED, dev_bytes, dev_u32 as t32, dev_u64 as t64, tls_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +24,8 @@ def _threads() -> int:
 
 
 def test_c1_full_size_tag_fold(gpu, oracle):
-    torch = torch_mod()
+    import torch
+
     from suruga_amd import batch as B
 
     count, n, seq0 = 1 << 20, 16384, 3
@@ -43,7 +44,8 @@ def test_c1_full_size_tag_fold(gpu, oracle):
 
 
 def test_c2_full_size_tag_fold(gpu, oracle):
-    torch = torch_mod()
+    import torch
+
     from suruga_amd import batch as B
     from suruga_amd import workloads as W
 
@@ -51,8 +53,6 @@ def test_c2_full_size_tag_fold(gpu, oracle):
     count = lay.count
     gen = torch.Generator(device="cuda").manual_seed(11)
     pt = torch.randint(0, 256, (lay.pt_bytes,), dtype=torch.uint8, device="cuda", generator=gen)
-    t64 = lambda a: torch.from_numpy(a.view(np.int64)).to("cuda")
-    t32 = lambda a: torch.from_numpy(a.view(np.int32)).to("cuda")
     keys = dev_bytes(lay.keys).view(-1, 32)
     common = dict(count=count, keys=keys, key_index=t32(lay.key_index), seq=t64(lay.seq))
     maxl = int(lay.lens.max())

@@ -13,12 +13,11 @@ SG_BATCH_KEEP_FAILED is set.
 """
 from __future__ import annotations
 
-import struct
-
 import numpy as np
 import pytest
 
-from test_gpu_parity import dev_bytes, host, torch_mod
+from gpu_support import (BatchCase, check_opened, check_sealed, dev_bytes, filled, kernel_forms, open_, seal, slots,
+                         tamper)
 
 pytestmark = pytest.mark.gpu
 
@@ -39,92 +38,52 @@ def _lengths(rng, count, explicit):
 
 @pytest.mark.parametrize("seed", list(range(11, 27)))
 def test_random_mixed_batches(gpu, oracle, seed):
-    torch = torch_mod()
-    from suruga_amd import batch as B
-
     rng = np.random.default_rng(0xF022 + seed)
     count = int(rng.integers(700, 1500))
     explicit = seed % 2 == 0
     aligned = seed % 4 < 2
     lens = _lengths(rng, count, explicit)
-    pad = 16 if aligned else 1
-    skew_i, skew_o = (0, 0) if aligned else (3, 7)
-    step_i = (lens.astype(np.uint64) + pad - 1) // pad * pad + skew_i
-    step_o = (lens.astype(np.uint64) + 16 + pad - 1) // pad * pad + skew_o
-    in_off = np.zeros(count, dtype=np.uint64)
-    out_off = np.zeros(count, dtype=np.uint64)
-    in_off[1:] = np.cumsum(step_i[:-1])
-    out_off[1:] = np.cumsum(step_o[:-1])
-    pt_bytes, ct_bytes = int(in_off[-1] + step_i[-1]), int(out_off[-1] + step_o[-1])
+    in_off, out_off, pt_bytes, ct_bytes = slots(lens, 16) if aligned else slots(lens, 1, (3, 7))
     pt_h = rng.bytes(pt_bytes)
     keys_h = rng.bytes(8 * 32)
     kidx = rng.integers(0, 8, size=count).astype(np.uint32)
-    dev = lambda a: torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a.view(np.int32)).to("cuda")
-    keys = dev_bytes(keys_h).view(8, 32)
     if explicit:
         adlen = int(rng.integers(0, 256))
         stride = max(adlen, 1)
         nonces_h = rng.bytes(8 * count)
-        ads_h = bytearray(rng.bytes(stride * count))
-        mode = dict(tls=False, nonces=dev_bytes(nonces_h), ads=dev_bytes(bytes(ads_h)), ad_len=adlen, ad_stride=stride)
-
-        def nonce_ad(i, n, ads=ads_h):
-            return nonces_h[8 * i:8 * i + 8], bytes(ads[i * stride:i * stride + adlen])
+        mode = dict(nonces_h=nonces_h, ads_h=rng.bytes(stride * count), adlen=adlen)
     else:
         seqs = rng.integers(0, 2**63, size=count, dtype=np.uint64)
         seqs[:2] = [2**32 - 1, 2**64 - 1]
         ctype, minor = int(rng.choice([20, 21, 22, 23])), int(rng.integers(0, 4))
-        mode = dict(seq=dev(seqs), content_type=ctype, version=(3, minor))
+        mode = dict(seqs=seqs, content_type=ctype, version=(3, minor))
+    case = BatchCase(lens, pt_h, keys_h, in_off=in_off, out_off=out_off, kidx=kidx, **mode)
 
-        def nonce_ad(i, n, ads=None):
-            s = int(seqs[i])
-            return struct.pack(">Q", s), oracle.tls_ad(s, n, ctype, 3, minor)
-    common = dict(count=count, keys=keys, key_index=dev(kidx), **mode)
-
-    ct = torch.zeros(ct_bytes, dtype=torch.uint8, device="cuda")
-    B.seal(B.Batch(inp=dev_bytes(pt_h), out=ct, lens=dev(lens), max_len=int(lens.max()), in_off=dev(in_off),
-                   out_off=dev(out_off), **common))
-    torch.cuda.synchronize()
-    ct_h = bytearray(host(ct))
-    for i in range(count):
-        k = keys_h[32 * int(kidx[i]):32 * int(kidx[i]) + 32]
-        n, o, q = int(lens[i]), int(in_off[i]), int(out_off[i])
-        nonce, ad = nonce_ad(i, n)
-        assert bytes(ct_h[q:q + n + 16]) == oracle.seal(k, nonce, pt_h[o:o + n], ad), (seed, i, n)
+    ct_h = seal(case, filled(ct_bytes, 0))
+    check_sealed(case, oracle, ct_h, where=(seed,))
 
     # open: tamper ~3 % of the records (ciphertext, tag or, explicit, AD), truncate a few
-    exp_st = bytearray(count)
-    olens = (lens + 16).astype(np.uint32)
+    flips, cut = {}, {}
+    ads_in = bytearray(case.ads_h) if explicit else None
     for i in rng.choice(count, size=max(3, count // 33), replace=False):
         i, n = int(i), int(lens[i])
         where = int(rng.integers(0, 3 if explicit and adlen else 2))
         if where == 0 and n:
-            ct_h[int(out_off[i]) + int(rng.integers(0, n))] ^= 1 << int(rng.integers(0, 8))
+            flips[i] = (int(rng.integers(0, n)), 1 << int(rng.integers(0, 8)))
         elif where == 2:
-            ads_h[i * stride + int(rng.integers(0, adlen))] ^= 0x20
+            ads_in[i * stride + int(rng.integers(0, adlen))] ^= 0x20
+            flips[i] = (0, 0)  # its AD instead: status 1 all the same
         else:
-            ct_h[int(out_off[i]) + n + int(rng.integers(0, 16))] ^= 0x80
-        exp_st[i] = 1
+            flips[i] = (n + int(rng.integers(0, 16)), 0x80)
     for i in rng.choice(count, size=3, replace=False):
-        i = int(i)
-        olens[i] = int(rng.integers(0, 16))
-        exp_st[i] = 2
-    if explicit:
-        common["ads"] = dev_bytes(bytes(ads_h))
+        cut[int(i)] = int(rng.integers(0, 16))
+    exp_st, olens = tamper(case, ct_h, flips, cut)
     keep = bool(seed % 3 == 0)
-    back = torch.full((pt_bytes,), 0xEE, dtype=torch.uint8, device="cuda")
-    st = torch.full((count,), 0xFF, dtype=torch.uint8, device="cuda")
-    B.open_(B.Batch(inp=dev_bytes(bytes(ct_h)), out=back, lens=dev(olens), max_len=int(olens.max()),
-                    in_off=dev(out_off), out_off=dev(in_off), status=st, keep_failed=keep, **common))
-    torch.cuda.synchronize()
-    assert host(st) == bytes(exp_st), seed
-    back_h = host(back)
-    for i in range(count):
-        o, n = int(in_off[i]), int(lens[i])
-        if exp_st[i] == 0:
-            assert back_h[o:o + n] == pt_h[o:o + n], (seed, i, n)
-        elif exp_st[i] == 1 and not keep:
-            assert back_h[o:o + n] == bytes(n), (seed, i, n)  # nothing of a failed record is released
+    # a fresh copy of the image; 0xEE where an open writes nothing
+    back_h, st_h = open_(case, dev_bytes(bytes(ct_h)), filled(pt_bytes, 0xEE), olens=olens, ads_h=ads_in,
+                         keep_failed=keep)
+    # nothing of a failed record is released unless kept; kept and truncated ones are not looked at
+    check_opened(case, back_h, st_h, exp_st, keep=keep, where=(seed,))
 
 
 @pytest.mark.parametrize("lockstep,packed", [(0, 0), (0, 1), (1, 0)])
@@ -133,12 +92,5 @@ def test_random_mixed_batches_every_kernel_form(gpu, oracle, seed, lockstep, pac
     """The same random batches with the wave-per-record kernel and / or the
     packed kernel switched off (sg_set_lockstep / sg_set_packed): every record
     then runs on another route (size classes), bit-exact all the same."""
-    from suruga_amd import _native
-
-    lib = _native.load()
-    prev_l, prev_p = lib.sg_set_lockstep(lockstep), lib.sg_set_packed(packed)
-    try:
+    with kernel_forms(gpu, lockstep=lockstep, packed=packed):
         test_random_mixed_batches(gpu, oracle, seed)
-    finally:
-        lib.sg_set_lockstep(prev_l)
-        lib.sg_set_packed(prev_p)

@@ -31,35 +31,11 @@ import numpy as np
 import pytest
 
 import mac_forge as F
+from gpu_support import BatchCase, dev_bytes, filled, host_bytes as host, mode_of, open_, seal, slots
+from gpu_support import groups, lockstep, packed  # noqa: F401  (fixtures)
+from suruga_amd._native import SG_E_BAD_MAC, SG_OK
 
 pytestmark = pytest.mark.gpu
-
-SG_OK, SG_E_BAD_MAC = 0, 1
-
-
-def torch_mod():
-    import torch
-
-    return torch
-
-
-def dev_bytes(b: bytes):
-    torch = torch_mod()
-    if not b:
-        return torch.zeros(1, dtype=torch.uint8, device="cuda")
-    return torch.frombuffer(bytearray(b), dtype=torch.uint8).to("cuda")
-
-
-def dev_u64(vals):
-    return torch_mod().from_numpy(np.array(vals, dtype=np.uint64).view(np.int64)).to("cuda")
-
-
-def dev_u32(vals):
-    return torch_mod().from_numpy(np.array(vals, dtype=np.uint32).view(np.int32)).to("cuda")
-
-
-def host(t) -> bytes:
-    return t.cpu().numpy().tobytes()
 
 
 def bad_tag(sealed: bytes) -> bytes:
@@ -82,30 +58,6 @@ def first_diff(got: bytes, want: bytes, bounds, recs):
     return "bytes between the records"
 
 
-# ---------------------------------------------------------------------------
-# switches, restored after each test
-# ---------------------------------------------------------------------------
-@pytest.fixture
-def lockstep(gpu):
-    prev = gpu.sg_set_lockstep(-1)
-    yield gpu.sg_set_lockstep
-    gpu.sg_set_lockstep(prev)
-
-
-@pytest.fixture
-def packed(gpu):
-    prev = gpu.sg_set_packed(-1)
-    yield gpu.sg_set_packed
-    gpu.sg_set_packed(prev)
-
-
-@pytest.fixture
-def groups(gpu):
-    prev = gpu.sg_set_msg_groups(-1)
-    yield gpu.sg_set_msg_groups
-    gpu.sg_set_msg_groups(prev)
-
-
 @pytest.fixture(scope="module")
 def key_t(gpu):
     return dev_bytes(F.KEY)
@@ -114,94 +66,66 @@ def key_t(gpu):
 # ---------------------------------------------------------------------------
 # batch forms
 # ---------------------------------------------------------------------------
-def mode_args(recs, mode):
-    if mode == "tls":
-        return dict(seq=dev_u64([r.seq for r in recs]))
-    stride = max(mode, 1)
-    return dict(tls=False, nonces=dev_bytes(b"".join(r.nonce for r in recs)),
-                ads=dev_bytes(b"".join(r.ad.ljust(stride, b"\0") for r in recs)), ad_len=mode, ad_stride=stride)
+def check_batch(case, recs, ct_bytes, sealed_of, back_of):
+    """Seal, open and open with every tag off by one; whole buffers against the forged
+    records' images, so the bytes between the records count too.  sealed_of(parts) lays
+    parts out as the sealed image, back_of() is the buffer an open writes into and
+    back_of(parts) what it must hold afterwards."""
+    count = case.count
+    in_b = [(int(o), int(o) + case.n(i)) for i, o in enumerate(case.in_off)]
+    out_b = [case.out_range(i) for i in range(count)]
+    want = sealed_of([r.want for r in recs])
+    assert first_diff(bytes(seal(case, filled(ct_bytes, 0))), want, out_b, recs) is None, "seal"
+    for sealed, st_want, pt_want in ((want, bytes(count), back_of([r.pt for r in recs])),
+                                     (sealed_of([bad_tag(r.want) for r in recs]), b"\x01" * count,
+                                      back_of([bytes(len(r.pt)) for r in recs]))):
+        back_h, st_h = open_(case, dev_bytes(sealed), back_of())
+        assert st_h == st_want, ("open status", [r.case for r, a, b in zip(recs, st_h, st_want) if a != b][:3])
+        assert first_diff(back_h, pt_want, in_b, recs) is None, "open output"
 
 
 def check_uniform(recs, n, mode):
     """A uniform batch (len = NULL, strides n and n + 16: 16-byte aligned for n = 16384)."""
-    torch = torch_mod()
-    from suruga_amd import batch as B
-
     count = len(recs)
     assert all(len(r.pt) == n for r in recs)
-    pt_h, want = b"".join(r.pt for r in recs), b"".join(r.want for r in recs)
-    in_b = [(i * n, (i + 1) * n) for i in range(count)]
-    out_b = [(i * (n + 16), (i + 1) * (n + 16)) for i in range(count)]
-    common = dict(count=count, keys=dev_bytes(F.KEY).view(1, 32), **mode_args(recs, mode))
-    ct = torch.zeros(count * (n + 16), dtype=torch.uint8, device="cuda")
-    B.seal(B.Batch(inp=dev_bytes(pt_h), out=ct, uniform_len=n, in_stride=n, out_stride=n + 16, **common))
-    torch.cuda.synchronize()
-    assert first_diff(host(ct), want, out_b, recs) is None, "seal"
-    for sealed, st_want, pt_want in ((want, bytes(count), pt_h),
-                                     (b"".join(bad_tag(r.want) for r in recs), b"\x01" * count, bytes(count * n))):
-        back = torch.full((count * n,), 0xEE, dtype=torch.uint8, device="cuda")
-        st = torch.full((count,), 0xFF, dtype=torch.uint8, device="cuda")
-        B.open_(B.Batch(inp=dev_bytes(sealed), out=back, uniform_len=n + 16, in_stride=n + 16, out_stride=n, status=st,
-                        **common))
-        torch.cuda.synchronize()
-        st_h = host(st)
-        assert st_h == st_want, ("open status", [r.case for r, a, b in zip(recs, st_h, st_want) if a != b][:3])
-        assert first_diff(host(back), pt_want, in_b, recs) is None, "open output"
+    case = BatchCase(np.full(count, n), b"".join(r.pt for r in recs), F.KEY, strides=(n, n + 16), **mode_of(recs, mode))
+    check_batch(case, recs, count * (n + 16), b"".join,
+                lambda parts=None: filled(count * n, 0xEE) if parts is None else b"".join(parts))
 
 
 def check_mixed(recs):
     """A mixed TLS batch (len array, 16-byte aligned records, per-record sequence numbers)."""
-    torch = torch_mod()
-    from suruga_amd import batch as B
-
-    count = len(recs)
     lens = np.array([len(r.pt) for r in recs], dtype=np.uint64)
-    in_off, out_off = np.zeros(count, dtype=np.uint64), np.zeros(count, dtype=np.uint64)
-    in_off[1:] = np.cumsum((lens + 15) // 16 * 16)[:-1]
-    out_off[1:] = np.cumsum((lens + 16 + 15) // 16 * 16)[:-1]
+    in_off, out_off, _, _ = slots(lens, 16)
+    # its own sizes: the last record's slot is not rounded up, 16 spare bytes behind each buffer
     pt_bytes = int(in_off[-1] + lens[-1]) + 16
     ct_bytes = int(out_off[-1] + lens[-1]) + 32
-    in_b = [(int(o), int(o + n)) for o, n in zip(in_off, lens)]
-    out_b = [(int(o), int(o + n + 16)) for o, n in zip(out_off, lens)]
 
-    def lay(parts, bounds, size):
+    def lay(parts, offs, size):
         buf = bytearray(size)
-        for p, (lo, hi) in zip(parts, bounds):
-            buf[lo:hi] = p
+        for p, o in zip(parts, offs):
+            buf[int(o):int(o) + len(p)] = p
         return bytes(buf)
 
-    pt_h = lay([r.pt for r in recs], in_b, pt_bytes)
-    want = lay([r.want for r in recs], out_b, ct_bytes)
-    common = dict(count=count, keys=dev_bytes(F.KEY).view(1, 32), seq=dev_u64([r.seq for r in recs]))
-    d_in, d_out = dev_u64(in_off), dev_u64(out_off)
-    ct = torch.zeros(ct_bytes, dtype=torch.uint8, device="cuda")
-    B.seal(B.Batch(inp=dev_bytes(pt_h), out=ct, lens=dev_u32(lens), max_len=int(lens.max()), in_off=d_in,
-                   out_off=d_out, **common))
-    torch.cuda.synchronize()
-    assert first_diff(host(ct), want, out_b, recs) is None, "seal"
-    for sealed, st_want, pt_want in ((want, bytes(count), pt_h),
-                                     (lay([bad_tag(r.want) for r in recs], out_b, ct_bytes), b"\x01" * count,
-                                      bytes(pt_bytes))):
-        back = dev_bytes(lay([b"\xee" * len(r.pt) for r in recs], in_b, pt_bytes))
-        st = torch.full((count,), 0xFF, dtype=torch.uint8, device="cuda")
-        B.open_(B.Batch(inp=dev_bytes(sealed), out=back, lens=dev_u32(lens + 16), max_len=int(lens.max()) + 16,
-                        in_off=d_out, out_off=d_in, status=st, **common))
-        torch.cuda.synchronize()
-        st_h = host(st)
-        assert st_h == st_want, ("open status", [r.case for r, a, b in zip(recs, st_h, st_want) if a != b][:3])
-        assert first_diff(host(back), pt_want, in_b, recs) is None, "open output"
+    def back_of(parts=None):
+        # before the open 0xEE in the records and zero between them, so that a zeroed record shows
+        if parts is None:
+            return dev_bytes(lay([b"\xee" * len(r.pt) for r in recs], in_off, pt_bytes))
+        return lay(parts, in_off, pt_bytes)
+
+    case = BatchCase(lens, lay([r.pt for r in recs], in_off, pt_bytes), F.KEY, in_off=in_off, out_off=out_off,
+                     **mode_of(recs, "tls"))
+    check_batch(case, recs, ct_bytes, lambda parts: lay(parts, out_off, ct_bytes), back_of)
 
 
 # ---------------------------------------------------------------------------
 # the long-message forms
 # ---------------------------------------------------------------------------
 def dev_room(n: int):
-    torch = torch_mod()
-    return torch.full((max(n, 1),), 0xEE, dtype=torch.uint8, device="cuda")
+    return filled(max(n, 1), 0xEE)
 
 
 def check_msg_dev(key_t, r):
-    torch = torch_mod()
     from suruga_amd import msg
 
     n = len(r.pt)
@@ -211,7 +135,7 @@ def check_msg_dev(key_t, r):
     assert host(out)[:n + 16] == r.want, ("seal", r.case)
     for sealed, st_want, pt_want in ((r.want, SG_OK, r.pt), (bad_tag(r.want), SG_E_BAD_MAC, bytes(n))):
         back = dev_room(n)
-        st = torch.full((1,), 0xFF, dtype=torch.uint8, device="cuda")
+        st = filled(1, 0xFF)
         assert msg.open_(key_t, r.nonce, dev_bytes(sealed), back, st, ad=adt, in_len=n + 16, stream=0) == SG_OK
         assert int(st.item()) == st_want, ("open status", r.case)
         assert host(back)[:n] == pt_want, ("open output", r.case)

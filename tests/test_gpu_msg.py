@@ -15,12 +15,14 @@ import numpy as np
 import pytest
 
 from conftest import vector_pt
+from gpu_support import groups, host_bytes as host  # noqa: F401  (groups: a fixture)
+from mac_forge import tile_bytes
+from suruga_amd._native import SG_E_BAD_MAC, SG_E_SHORT, SG_OK
 
 pytestmark = pytest.mark.gpu
 
 KEY = bytes(range(32))
 NONCE = bytes([0xA0, 1, 2, 3, 4, 5, 6, 0x7F])
-SG_OK, SG_E_BAD_MAC, SG_E_SHORT = 0, 1, 2
 
 
 @functools.lru_cache(maxsize=None)
@@ -50,29 +52,11 @@ def dev(b: bytes, off: int = 0, room: int = 0):
     return t
 
 
-def host(t) -> bytes:
-    return t.cpu().numpy().tobytes()
-
-
 @pytest.fixture(scope="module")
 def key_t(gpu):
     import torch
 
     return torch.tensor(list(KEY), dtype=torch.uint8, device="cuda")
-
-
-@pytest.fixture
-def groups(gpu):
-    """Restores the sg_set_msg_groups setting after a test that changes it."""
-    prev = gpu.sg_set_msg_groups(-1)
-    yield gpu.sg_set_msg_groups
-    gpu.sg_set_msg_groups(prev)
-
-
-def tile_bytes() -> int:
-    from suruga_amd import msg
-
-    return msg.plan_for(0, 0)["tile_bytes"]
 
 
 def seal_dev(key_t, pt: bytes, ad: bytes, offs=(0, 0, 0), key=None, nonce=NONCE) -> bytes:

@@ -14,13 +14,10 @@ import hashlib
 
 import pytest
 
+from mac_forge import mac_stream
+
 P1305 = (1 << 130) - 5
 CLAMP = 0x0FFFFFFC0FFFFFFC0FFFFFFC0FFFFFFF
-
-
-def mac_stream(ad: bytes, ct: bytes) -> bytes:
-    # chacha20_poly1305.rs:19-42: ad || le64(|ad|) || ct || le64(|ct|), no padding
-    return ad + len(ad).to_bytes(8, "little") + ct + len(ct).to_bytes(8, "little")
 
 
 def tiled_tag(stream: bytes, r16: bytes, s16: bytes, plan: dict) -> bytes:
