@@ -198,8 +198,10 @@ int sg_open_batch(const sg_batch* b);
 /* ---- long messages: any data and AD length, one message over the whole chip
  * Encryptor::encrypt / Decryptor::decrypt take data and additional data of any
  * length (cipher/mod.rs:22-32, chacha20_poly1305.rs:19-94).  sg_seal, sg_open
- * and the batch calls keep their bounds (SG_MAX_AD_LEN, SG_MAX_RECORD_LEN);
- * the message calls below take one key, one nonce, n data bytes and ad_len AD
+ * and the record batch (sg_seal_batch / sg_open_batch) keep their bounds
+ * (SG_MAX_AD_LEN, SG_MAX_RECORD_LEN); the message batch further below
+ * (sg_seal_msg_batch / sg_open_msg_batch) has none but SG_MSG_MAX_LEN.
+ * The message calls below take one key, one nonce, n data bytes and ad_len AD
  * bytes, same construction, and spread the one message over a persistent grid
  * (sg_msg.hip: the MAC stream is cut into tiles whose Poly1305 partial sums
  * are combined exactly, so the tag is the sequential one bit for bit).
@@ -271,6 +273,96 @@ int sg_msg_plan_for(uint64_t n, uint64_t adlen, uint32_t groups /* 0 = automatic
  * environment SG_MSG_GROUPS, else 0.  Returns the previous setting; a negative
  * argument only queries. */
 int sg_set_msg_groups(int n);
+
+/* ---- message batch: many long messages of any length on one grid ---------
+ * The message path's decomposition applied across messages: every message of
+ * the call has its own key index, nonce, AD and lengths (data and AD each 0 to
+ * SG_MSG_MAX_LEN, any pointer alignment), one persistent grid walks the tiles
+ * of all messages and one finish launch writes (or compares) all tags
+ * (sg_msg_batch.hip).  Same construction, bit for bit the sequential tag.
+ *
+ * The items array lives in HOST memory and is consumed before the call
+ * returns; everything it points to is device memory.  Within a message
+ * out == in exactly is allowed and any other overlap of its in and out is
+ * SG_E_ARG, as in the single call.  Overlap BETWEEN messages of a call (one
+ * message's out with another's in, out or ad) is the caller's responsibility:
+ * it is not checked, and the result is undefined.
+ *
+ * Open: status[i] is SG_OK, SG_E_BAD_MAC or SG_E_SHORT and the call itself
+ * returns SG_OK.  A message with in_len < 16 gets SG_E_SHORT, its output is
+ * left untouched and the other messages proceed (as sg_open_batch per record).
+ * The decryption always runs (chacha20_poly1305.rs:80-93); a failed message's
+ * out[0, n) is zeroed on the device in the same stream unless
+ * SG_MSG_KEEP_FAILED is set.
+ *
+ * stream and workspace as in sg_msg: non-NULL stream = fully asynchronous,
+ * NULL = synchronous on the null stream; a caller workspace of
+ * sg_msg_batch_workspace_size(count) bytes, 16-byte aligned, or NULL for the
+ * library cache.  The plan and the per-message descriptors are uploaded into
+ * the workspace by a copy that a stream capture cannot record: under capture
+ * the call returns SG_E_ARG, with or without a caller workspace.
+ * count == 0 returns SG_OK and launches nothing.  NULL pointers where a
+ * length is non-zero, unknown flags, count above SG_MSG_BATCH_MAX_COUNT, a
+ * workspace too small or misaligned and key_index >= num_keys are SG_E_ARG
+ * before any GPU call. */
+#define SG_MSG_BATCH_MAX_COUNT  (1u << 20)
+
+typedef struct sg_msg_item {
+    uint32_t       key_index;  /* < num_keys                                        */
+    uint8_t        nonce[8];   /* by value                                          */
+    const uint8_t* ad;         /* device, ad_len bytes                              */
+    uint64_t       ad_len;
+    const uint8_t* in;         /* device; seal: n bytes of pt, open: n + 16 (ct||tag) */
+    uint64_t       in_len;
+    uint8_t*       out;        /* device; seal: n + 16, open: n. out == in allowed   */
+} sg_msg_item;
+
+typedef struct sg_msg_batch {
+    uint32_t           count;
+    uint32_t           flags;      /* SG_MSG_KEEP_FAILED                            */
+    const uint8_t*     keys;       /* device key table [num_keys][32], as sg_batch  */
+    uint32_t           num_keys;
+    const sg_msg_item* items;      /* HOST, count entries                           */
+    uint8_t*           status;     /* device, count bytes; required for open        */
+    void*              stream;
+    void*              workspace;
+    size_t             workspace_size;
+} sg_msg_batch;
+
+size_t sg_msg_batch_workspace_size(uint32_t count);
+int sg_seal_msg_batch(const sg_msg_batch* b);
+int sg_open_msg_batch(const sg_msg_batch* b);
+
+/* The plan of a message batch (host only, no GPU).  Message m gets exactly
+ * the geometry of sg_msg_plan_for(n[m], adlen[m], groups, &msgs[m]); only its
+ * mac_blocks, tiles, zero_blocks and tile size matter here.  The messages'
+ * tiles, in order, form one global sequence of plan->tiles tiles; group g of
+ * plan->groups workgroups owns global tiles [g * tiles_per_group,
+ * min(tiles, (g + 1) * tiles_per_group)), none empty.  A group's run is cut at
+ * message boundaries into segments: segment s is tiles [tile_begin, tile_end)
+ * of message segs[s].msg, walked by group segs[s].group; segments are in
+ * global tile order, at most groups + count - 1 of them.  group_segs[g] and
+ * msg_segs[m] are the (first, count) runs of segs that belong to group g and
+ * to message m.  groups: 0 = automatic (min(tiles, 1024)), else the wanted
+ * number (the plan may use fewer).  msgs, segs, group_segs (1024 entries) and
+ * msg_segs may each be NULL when not wanted; seg_cap is the room of segs.
+ * O(count + groups).  The kernels take exactly these tables.
+ * SG_OK, or SG_E_ARG (NULL plan, a NULL length array with count > 0, count
+ * above SG_MSG_BATCH_MAX_COUNT, a length above SG_MSG_MAX_LEN, seg_cap too
+ * small). */
+typedef struct sg_msg_seg {
+    uint32_t msg, tile_begin, tile_end, group;
+} sg_msg_seg;
+typedef struct sg_msg_span {
+    uint32_t first, count;
+} sg_msg_span;
+typedef struct sg_msg_batch_plan {
+    uint64_t tiles, tiles_per_group;
+    uint32_t groups, segments, tile_blocks, tile_bytes;
+} sg_msg_batch_plan;
+int sg_msg_batch_plan_for(const uint64_t* n, const uint64_t* adlen, uint32_t count, uint32_t groups,
+                          sg_msg_batch_plan* plan, sg_msg_plan* msgs, sg_msg_seg* segs, uint32_t seg_cap,
+                          sg_msg_span* group_segs, sg_msg_span* msg_segs);
 
 /* ---- batched record layer over host memory ------------------------------
  * The throughput form of TlsWriter / TlsReader (tls.rs:68-380): many records

@@ -42,7 +42,10 @@ EXPORTS = [
     "sg_derive_keys", "sg_finished_verify_data",
     "sg_msg_workspace_size", "sg_seal_msg_dev", "sg_open_msg_dev", "sg_seal_msg", "sg_open_msg",
     "sg_msg_plan_for", "sg_set_msg_groups",
+    "sg_msg_batch_workspace_size", "sg_seal_msg_batch", "sg_open_msg_batch", "sg_msg_batch_plan_for",
 ]
+SG_MSG_BATCH_MAX_COUNT = 1 << 20
+SG_MSG_MAX_GROUPS = 1024
 
 
 class SgBatch(C.Structure):
@@ -105,6 +108,55 @@ class SgMsgPlan(C.Structure):
     _fields_ = [("mac_blocks", C.c_uint64), ("tiles", C.c_uint64), ("zero_blocks", C.c_uint64),
                 ("tile_blocks", C.c_uint32), ("tile_bytes", C.c_uint32), ("groups", C.c_uint32),
                 ("tiles_per_group", C.c_uint32)]
+
+
+class SgMsgItem(C.Structure):
+    """Mirror of ``struct sg_msg_item``."""
+
+    _fields_ = [
+        ("key_index", C.c_uint32),
+        ("nonce", C.c_uint8 * 8),
+        ("ad", C.c_void_p),
+        ("ad_len", C.c_uint64),
+        ("in_", C.c_void_p),
+        ("in_len", C.c_uint64),
+        ("out", C.c_void_p),
+    ]
+
+
+class SgMsgBatch(C.Structure):
+    """Mirror of ``struct sg_msg_batch``."""
+
+    _fields_ = [
+        ("count", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("keys", C.c_void_p),
+        ("num_keys", C.c_uint32),
+        ("items", C.POINTER(SgMsgItem)),
+        ("status", C.c_void_p),
+        ("stream", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_size", C.c_size_t),
+    ]
+
+
+class SgMsgSeg(C.Structure):
+    """Mirror of ``struct sg_msg_seg``."""
+
+    _fields_ = [("msg", C.c_uint32), ("tile_begin", C.c_uint32), ("tile_end", C.c_uint32), ("group", C.c_uint32)]
+
+
+class SgMsgSpan(C.Structure):
+    """Mirror of ``struct sg_msg_span``."""
+
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32)]
+
+
+class SgMsgBatchPlan(C.Structure):
+    """Mirror of ``struct sg_msg_batch_plan``."""
+
+    _fields_ = [("tiles", C.c_uint64), ("tiles_per_group", C.c_uint64), ("groups", C.c_uint32),
+                ("segments", C.c_uint32), ("tile_blocks", C.c_uint32), ("tile_bytes", C.c_uint32)]
 
 
 class SgReadResult(C.Structure):
@@ -243,6 +295,16 @@ def _declare(lib: C.CDLL) -> None:
     lib.sg_msg_plan_for.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(SgMsgPlan)]
     lib.sg_set_msg_groups.restype = C.c_int
     lib.sg_set_msg_groups.argtypes = [C.c_int]
+    lib.sg_msg_batch_workspace_size.restype = C.c_size_t
+    lib.sg_msg_batch_workspace_size.argtypes = [C.c_uint32]
+    for f in (lib.sg_seal_msg_batch, lib.sg_open_msg_batch):
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(SgMsgBatch)]
+    u64p = C.POINTER(C.c_uint64)
+    lib.sg_msg_batch_plan_for.restype = C.c_int
+    lib.sg_msg_batch_plan_for.argtypes = [u64p, u64p, C.c_uint32, C.c_uint32, C.POINTER(SgMsgBatchPlan),
+                                          C.POINTER(SgMsgPlan), C.POINTER(SgMsgSeg), C.c_uint32,
+                                          C.POINTER(SgMsgSpan), C.POINTER(SgMsgSpan)]
 
 
 def load(path: Path | None = None) -> C.CDLL:

@@ -27,4 +27,41 @@ constexpr uint32_t kMsgPartialWords = 8;  // 5 radix-2^26 limbs, padded to 32 by
 
 int msg_groups();  // sg_set_msg_groups / SG_MSG_GROUPS
 
+// ---- the message batch (sg_msg_batch.hip, sg_msg_batch_capi.cpp)
+// One message as the batch kernels read it (wave-uniform loads): the host
+// resolves the key index and the nonce words.  skip: an open of fewer than 16
+// bytes -- no kernel touches its buffers, the finish kernel reports SG_E_SHORT.
+struct MsgBatchItem {
+    const uint8_t* key;
+    const uint8_t* ad;
+    const uint8_t* in;
+    uint8_t* out;
+    uint64_t n, adlen;
+    uint32_t n14, n15, skip, pad_;
+};
+static_assert(sizeof(MsgBatchItem) == 64, "device layout");
+
+// The batch's workspace, a function of count alone.  The host writes
+// [items | plans | msg_segs | segs | group_segs] (sg_msg_batch_plan_for's tables
+// as they stand) and uploads them in one copy; the partials (one per segment,
+// kMsgPartialWords words) follow and never leave the device.
+struct MsgBatchLayout {
+    size_t items, plans, msg_segs, segs, group_segs, upload_bytes, partials, total;
+    uint32_t seg_cap;
+};
+inline MsgBatchLayout msg_batch_layout(uint32_t count) {
+    auto up = [](size_t x) { return (x + 15u) & ~(size_t)15u; };
+    MsgBatchLayout l;
+    l.seg_cap = kMsgMaxGroups + count;  // >= groups + count - 1
+    l.items = 0;
+    l.plans = l.items + sizeof(MsgBatchItem) * (size_t)count;
+    l.msg_segs = l.plans + sizeof(sg_msg_plan) * (size_t)count;
+    l.segs = up(l.msg_segs + sizeof(sg_msg_span) * (size_t)count);
+    l.group_segs = l.segs + sizeof(sg_msg_seg) * (size_t)l.seg_cap;
+    l.upload_bytes = up(l.group_segs + sizeof(sg_msg_span) * (size_t)kMsgMaxGroups);
+    l.partials = l.upload_bytes;
+    l.total = l.partials + 4u * kMsgPartialWords * (size_t)l.seg_cap;
+    return l;
+}
+
 }  // namespace sg

@@ -4,7 +4,10 @@
 of any length (cipher/mod.rs:22-32).  The record paths bound a record at 32 KiB
 and its AD at 255 bytes; this module is the path beside them: one key, one
 nonce, up to ``SG_MSG_MAX_LEN`` bytes of data and of AD, sealed or opened by a
-persistent grid over all CUs (suruga_amd/csrc/sg_msg.hip).
+persistent grid over all CUs (suruga_amd/csrc/sg_msg.hip).  Many such
+messages go through one call with ``seal_msgs`` / ``open_msgs``
+(``sg_seal_msg_batch`` / ``sg_open_msg_batch``, sg_msg_batch.hip): one grid
+over the tiles of all messages, one finish launch for all tags.
 
 Tensors are torch uint8 tensors on the GPU (PyTorch is used only for device
 memory and streams); all arithmetic runs in the gfx950 kernels.
@@ -12,6 +15,8 @@ memory and streams); all arithmetic runs in the gfx950 kernels.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
+from typing import Optional
 
 from . import _native as N
 from .batch import _ptr, _stream_handle
@@ -55,6 +60,101 @@ def _msg(key, nonce: bytes, ad, inp, in_len, out, status, keep_failed, stream, w
     m.workspace = _ptr(workspace)
     m.workspace_size = int(workspace.numel()) if workspace is not None else 0
     return m
+
+
+@dataclass
+class MsgItem:
+    """One message of a batch (``struct sg_msg_item``): device tensors, an 8-byte
+    nonce, an index into the call's key table.  ``in_len`` defaults to all of
+    ``inp`` (seal: n, open: n + 16); ``out`` may be ``inp`` itself."""
+
+    key_index: int
+    nonce: bytes
+    inp: object
+    out: object
+    ad: object = None
+    in_len: Optional[int] = None
+    ad_len: Optional[int] = None
+
+
+def batch_workspace_size(count: int) -> int:
+    return int(N.load().sg_msg_batch_workspace_size(count))
+
+
+def batch_plan_for(lengths, adlens, groups: int = 0) -> dict:
+    """The plan ``sg_msg_batch_plan_for`` computes (host only, no GPU) for
+    messages of ``lengths`` data bytes and ``adlens`` AD bytes: the header
+    fields (``tiles``, ``tiles_per_group``, ``groups``, ``segments``,
+    ``tile_blocks``, ``tile_bytes``), ``msgs`` (the per-message plans, as
+    ``plan_for``), ``segs`` (dicts of msg, tile_begin, tile_end, group),
+    ``group_segs`` and ``msg_segs`` ((first, count) runs of ``segs``).  Raises
+    NativeError for a length above SG_MSG_MAX_LEN."""
+    count = len(lengths)
+    if len(adlens) != count:
+        raise ValueError("lengths and adlens differ in length")
+    n = (C.c_uint64 * max(count, 1))(*lengths)
+    a = (C.c_uint64 * max(count, 1))(*adlens)
+    plan = N.SgMsgBatchPlan()
+    msgs = (N.SgMsgPlan * max(count, 1))()
+    cap = N.SG_MSG_MAX_GROUPS + count
+    segs = (N.SgMsgSeg * cap)()
+    gsp = (N.SgMsgSpan * N.SG_MSG_MAX_GROUPS)()
+    msp = (N.SgMsgSpan * max(count, 1))()
+    rc = N.load().sg_msg_batch_plan_for(n, a, count, groups, C.byref(plan), msgs, segs, cap, gsp, msp)
+    if rc != N.SG_OK:
+        raise N.NativeError(rc, "sg_msg_batch_plan_for: a length above SG_MSG_MAX_LEN or too many messages")
+    out = {name: int(getattr(plan, name)) for name, _ in N.SgMsgBatchPlan._fields_}
+    out["msgs"] = [{name: int(getattr(msgs[i], name)) for name, _ in N.SgMsgPlan._fields_} for i in range(count)]
+    out["segs"] = [{name: int(getattr(segs[i], name)) for name, _ in N.SgMsgSeg._fields_}
+                   for i in range(out["segments"])]
+    out["group_segs"] = [(int(gsp[g].first), int(gsp[g].count)) for g in range(out["groups"])]
+    out["msg_segs"] = [(int(msp[i].first), int(msp[i].count)) for i in range(count)]
+    return out
+
+
+def _msg_batch(keys, items, status, keep_failed, stream, workspace) -> N.SgMsgBatch:
+    arr = (N.SgMsgItem * max(len(items), 1))()
+    for d, it in zip(arr, items):
+        nonce = bytes(it.nonce)
+        if len(nonce) != N.SG_NONCE_LEN:
+            raise ValueError(f"nonce must be {N.SG_NONCE_LEN} bytes, got {len(nonce)}")  # chacha20.rs:27
+        d.key_index = it.key_index
+        d.nonce[:] = nonce
+        d.ad = _ptr(it.ad)
+        d.ad_len = (int(it.ad.numel()) if it.ad is not None else 0) if it.ad_len is None else it.ad_len
+        d.in_ = _ptr(it.inp)
+        d.in_len = (int(it.inp.numel()) if it.inp is not None else 0) if it.in_len is None else it.in_len
+        d.out = _ptr(it.out)
+    b = N.SgMsgBatch()
+    b.count = len(items)
+    b.flags = N.SG_MSG_KEEP_FAILED if keep_failed else 0
+    b.keys = _ptr(keys)
+    b.num_keys = int(keys.shape[0]) if keys is not None else 0
+    b.items = arr  # (the struct keeps the array alive)
+    b.status = _ptr(status)
+    b.stream = _stream_handle(stream)
+    b.workspace = _ptr(workspace)
+    b.workspace_size = int(workspace.numel()) if workspace is not None else 0
+    return b
+
+
+def seal_msgs(keys, items, stream=None, workspace=None) -> None:
+    """``sg_seal_msg_batch``: every item's out[0, n + 16) = ct || tag under
+    keys[item.key_index] (uint8 [num_keys, 32] on the device), all messages on
+    one grid.  Messages must not overlap one another (not checked)."""
+    b = _msg_batch(keys, items, None, False, stream, workspace)
+    N.check(N.load().sg_seal_msg_batch(C.byref(b)))
+
+
+def open_msgs(keys, items, status, keep_failed=False, stream=None, workspace=None) -> None:
+    """``sg_open_msg_batch``: status[i] (device uint8, one per item) becomes 0,
+    SG_E_BAD_MAC or SG_E_SHORT (fewer than 16 input bytes: that output is left
+    untouched); a failed message's output is zeroed on the device unless
+    ``keep_failed``."""
+    if status is None:
+        raise ValueError("open needs a status tensor")
+    b = _msg_batch(keys, items, status, keep_failed, stream, workspace)
+    N.check(N.load().sg_open_msg_batch(C.byref(b)))
 
 
 def seal_msg(key, nonce: bytes, inp, out, ad=None, in_len=None, stream=None, workspace=None) -> None:

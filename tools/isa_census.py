@@ -26,6 +26,7 @@ Usage: python tools/isa_census.py [--keep DIR]
 from __future__ import annotations
 
 import json
+import re
 import subprocess
 import sys
 import tempfile
@@ -56,6 +57,18 @@ def census_file(path: Path):
             nm = l.split(":")[0]
             if "_kernel" in nm and nm not in names:
                 names.append(nm)
+    # the code object's own metadata: registers, LDS and scratch per kernel
+    # (amdhsa.kernels: one "  - .key: value" entry per kernel, keys in alphabetical order)
+    res, cur = {}, None
+    for l in lines:
+        if re.match(r"  - \.", l):
+            cur = {}
+        m = re.match(r"  [ -] \.(group_segment_fixed_size|private_segment_fixed_size|sgpr_count|vgpr_count|name):\s+(\S+)", l)
+        if m and cur is not None:
+            if m.group(1) == "name":
+                res[m.group(2)] = cur
+            else:
+                cur[m.group(1)] = int(m.group(2))
     out = {}
     for mangled, dem in zip(names, demangle(names)):
         body_all = ic.kernel_lines(str(path), mangled)
@@ -83,7 +96,8 @@ def census_file(path: Path):
         wtot = waf + war + sum(woth.values())
         out[dem]["whole"] = {"arx_full": waf, "arx_rot": war, "other_full": wof,
                              "other_half": sum(woth.values()) - wof, "valu": wtot}
-        out[dem]["clk_per_valu_whole"] = round((2 * (waf + wof) + 4 * (wtot - waf - wof)) / wtot, 4) if wtot else None
+        out[dem]["resources"] = res.get(mangled, {})
+        out[dem]["clk_per_valu_whole"] =round((2 * (waf + wof) + 4 * (wtot - waf - wof)) / wtot, 4) if wtot else None
     return out
 
 
@@ -97,7 +111,7 @@ def main():
         wd = keep or Path(td)
         kernels = {}
         for s in (_build.CSRC / "sg_wpr.hip", _build.CSRC / "sg_pack.hip", _build.CSRC / "sg_kernels.hip",
-                  _build.CSRC / "sg_plumb.hip"):
+                  _build.CSRC / "sg_plumb.hip", _build.CSRC / "sg_msg.hip", _build.CSRC / "sg_msg_batch.hip"):
             flags = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-mllvm",
                      "-amdgpu-atomic-optimizer-strategy=None", "--save-temps", f'-DSG_SOURCE_HASH="{src}"']
             subprocess.run([_build.hipcc(), *flags, "-c", "-o", str(wd / f"{s.stem}.o"), str(s)], cwd=wd, check=True,
