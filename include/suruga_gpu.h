@@ -26,7 +26,16 @@
  * Construction: draft-agl-tls-chacha20poly1305-04 as implemented by suruga
  * (64-bit nonce, 32-bit block counter in state word 12 only, Poly1305 key =
  * keystream block 0, MAC over ad || le64(|ad|) || ct || le64(|ct|) with no
- * padding).  NOT RFC 7539.
+ * padding).  NOT RFC 7539 / RFC 8439: this holds for every record call
+ * (sg_seal / sg_open, sg_seal_batch / sg_open_batch, sg_write_records /
+ * sg_read_records), which speak only the draft.
+ *
+ * The message calls (sg_*_msg*, further below) speak the draft by default and,
+ * with SG_MSG_RFC8439 or through sg_seal_msg_rfc8439 / sg_open_msg_rfc8439,
+ * RFC 8439 (= RFC 7539): 96-bit nonce in state words 13-15, MAC over
+ * ad || zeros to 16 || ct || zeros to 16 || le64(|ad|) || le64(|ct|) -- what
+ * TLS 1.2 0xCCA8, TLS 1.3, QUIC, WireGuard, libsodium's _ietf form and
+ * OpenSSL's EVP_chacha20_poly1305 compute.
  *
  * Plain C types only: no HIP or torch types cross this boundary.  Device
  * pointers are passed as plain pointers; a HIP stream as void*.
@@ -214,10 +223,23 @@ int sg_open_batch(const sg_batch* b);
 #define SG_MSG_KEEP_FAILED  0x1u            /* open: leave the unauthenticated plaintext
                                                of a failed open in `out` (default: zeroed
                                                on the device, same stream)              */
+/* RFC 8439 (sections 2.3, 2.8) instead of the draft, in sg_msg.flags and
+ * sg_msg_batch.flags (the whole batch call; there is no per-item choice):
+ *   - the 96-bit nonce is nonce_hi[0..4) || nonce[0..8): state word 13 =
+ *     le32(nonce_hi), words 14 and 15 = the two words of nonce, as in the draft;
+ *     word 12 is the 32-bit block counter, block 0 gives the Poly1305 key and
+ *     the data uses blocks 1 onward, as in the draft;
+ *   - the MAC runs over ad || zeros to a multiple of 16 || ct || zeros to a
+ *     multiple of 16 || le64(ad_len) || le64(n); nothing is padded where a
+ *     length is a multiple of 16 already, 0 included.
+ * Without the flag nonce_hi is never read (callers of before the field existed
+ * leave whatever their padding held there).  The value is not 0x2 or 0x4. */
+#define SG_MSG_RFC8439      0x100u
+#define SG_RFC8439_NONCE_LEN 12u
 
 typedef struct sg_msg {
     const uint8_t* key;        /* 32 bytes, device                                  */
-    uint8_t        nonce[8];   /* by value                                          */
+    uint8_t        nonce[8];   /* by value; RFC 8439: the nonce's last 8 bytes      */
     const uint8_t* ad;         /* device, ad_len bytes                              */
     uint64_t       ad_len;
     const uint8_t* in;         /* device; seal: n bytes of pt, open: n + 16 (ct||tag) */
@@ -225,6 +247,8 @@ typedef struct sg_msg {
     uint8_t*       out;        /* device; seal: n + 16, open: n. out == in allowed   */
     uint8_t*       status;     /* open: one device byte (SG_OK / SG_E_BAD_MAC)      */
     uint32_t       flags;      /* SG_MSG_*                                          */
+    uint8_t        nonce_hi[4]; /* SG_MSG_RFC8439: the nonce's first 4 bytes; else
+                                  never read (the struct's former padding)          */
     void*          stream;     /* as sg_batch.stream; non-NULL: fully asynchronous   */
     void*          workspace;  /* >= sg_msg_workspace_size() bytes, 16-byte aligned
                                   device memory, or NULL: library cache (not under
@@ -252,6 +276,13 @@ int sg_seal_msg(sg_ctx* ctx, const uint8_t* nonce, size_t nonce_len, const uint8
                 const uint8_t* ad, size_t adlen, uint8_t* out);
 int sg_open_msg(sg_ctx* ctx, const uint8_t* nonce, size_t nonce_len, const uint8_t* in, size_t in_len,
                 const uint8_t* ad, size_t adlen, uint8_t* out);
+/* The same two calls in RFC 8439 (SG_MSG_RFC8439 above): nonce_len must be 12
+ * (else SG_E_ARG "nonce must be 12 bytes"); sg_seal_msg / sg_open_msg keep
+ * refusing anything but 8.  Any length from 0 up, same context, same returns. */
+int sg_seal_msg_rfc8439(sg_ctx* ctx, const uint8_t* nonce, size_t nonce_len, const uint8_t* pt, size_t n,
+                        const uint8_t* ad, size_t adlen, uint8_t* out);
+int sg_open_msg_rfc8439(sg_ctx* ctx, const uint8_t* nonce, size_t nonce_len, const uint8_t* in, size_t in_len,
+                        const uint8_t* ad, size_t adlen, uint8_t* out);
 
 /* The launch geometry of a message (host only, no GPU): the MAC stream
  * ad || le64(ad_len) || ct || le64(n) has mac_blocks 16-byte blocks (the last
@@ -267,6 +298,11 @@ typedef struct sg_msg_plan {
     uint32_t tile_blocks, tile_bytes, groups, tiles_per_group; /* last group takes the rest */
 } sg_msg_plan;
 int sg_msg_plan_for(uint64_t n, uint64_t adlen, uint32_t groups /* 0 = automatic */, sg_msg_plan* out);
+/* The same for a call with `flags` (SG_MSG_*): with SG_MSG_RFC8439 the stream
+ * is the padded one, 16 * ceil(adlen / 16) + 16 * ceil(n / 16) + 16 bytes, so
+ * its last block is always full; every other rule is the same.  Flags 0 give
+ * sg_msg_plan_for, field for field.  Unknown flags: SG_E_ARG. */
+int sg_msg_plan_for_flags(uint64_t n, uint64_t adlen, uint32_t flags, uint32_t groups, sg_msg_plan* out);
 
 /* Workgroups of the message kernels: 0 = automatic, else that many (at most
  * 1024); a test and A/B switch like sg_set_lockstep.  Initial value:
@@ -309,7 +345,9 @@ int sg_set_msg_groups(int n);
 
 typedef struct sg_msg_item {
     uint32_t       key_index;  /* < num_keys                                        */
-    uint8_t        nonce[8];   /* by value                                          */
+    uint8_t        nonce[8];   /* by value; RFC 8439: the nonce's last 8 bytes      */
+    uint8_t        nonce_hi[4]; /* SG_MSG_RFC8439: the nonce's first 4 bytes; else
+                                  never read (the struct's former padding)          */
     const uint8_t* ad;         /* device, ad_len bytes                              */
     uint64_t       ad_len;
     const uint8_t* in;         /* device; seal: n bytes of pt, open: n + 16 (ct||tag) */
@@ -319,7 +357,7 @@ typedef struct sg_msg_item {
 
 typedef struct sg_msg_batch {
     uint32_t           count;
-    uint32_t           flags;      /* SG_MSG_KEEP_FAILED                            */
+    uint32_t           flags;      /* SG_MSG_KEEP_FAILED, SG_MSG_RFC8439            */
     const uint8_t*     keys;       /* device key table [num_keys][32], as sg_batch  */
     uint32_t           num_keys;
     const sg_msg_item* items;      /* HOST, count entries                           */
@@ -363,6 +401,12 @@ typedef struct sg_msg_batch_plan {
 int sg_msg_batch_plan_for(const uint64_t* n, const uint64_t* adlen, uint32_t count, uint32_t groups,
                           sg_msg_batch_plan* plan, sg_msg_plan* msgs, sg_msg_seg* segs, uint32_t seg_cap,
                           sg_msg_span* group_segs, sg_msg_span* msg_segs);
+/* The same for a call with `flags`: message m gets the geometry of
+ * sg_msg_plan_for_flags(n[m], adlen[m], flags, groups, &msgs[m]).  Flags 0
+ * give sg_msg_batch_plan_for; unknown flags: SG_E_ARG. */
+int sg_msg_batch_plan_for_flags(const uint64_t* n, const uint64_t* adlen, uint32_t count, uint32_t flags,
+                                uint32_t groups, sg_msg_batch_plan* plan, sg_msg_plan* msgs, sg_msg_seg* segs,
+                                uint32_t seg_cap, sg_msg_span* group_segs, sg_msg_span* msg_segs);
 
 /* ---- batched record layer over host memory ------------------------------
  * The throughput form of TlsWriter / TlsReader (tls.rs:68-380): many records

@@ -6,7 +6,8 @@ Layout:
   suruga_amd/csrc/           gfx950 HIP kernels + C-ABI implementation
   suruga_amd/cipher.py       mirror of suruga's Aead/Encryptor/Decryptor traits
   suruga_amd/batch.py        device-resident batch seal/open (record-layer batching)
-  suruga_amd/msg.py          one long message (any data / AD length) over the whole chip
+  suruga_amd/msg.py          one long message (any data / AD length) over the whole chip,
+                             in the draft construction or (rfc8439=True) RFC 8439
   suruga_amd/_native.py      ctypes binding of libsuruga_gpu.so
 
 The HIP library is the only compute path; importing the cipher classes works
@@ -14,10 +15,10 @@ without a GPU, calling them needs one (and fails loudly otherwise).
 """
 from . import _native
 from .cipher import (Aead, ChaCha20Poly1305, ChaCha20Poly1305Decryptor, ChaCha20Poly1305Encryptor,
-                     CipherSuite, Decryptor, Encryptor, TlsError, TlsErrorKind)
+                     ChaCha20Poly1305Rfc8439, CipherSuite, Decryptor, Encryptor, TlsError, TlsErrorKind)
 
 __all__ = [
-    "Aead", "ChaCha20Poly1305", "ChaCha20Poly1305Decryptor", "ChaCha20Poly1305Encryptor",
+    "Aead", "ChaCha20Poly1305", "ChaCha20Poly1305Decryptor", "ChaCha20Poly1305Encryptor", "ChaCha20Poly1305Rfc8439",
     "CipherSuite", "Decryptor", "Encryptor", "TlsError", "TlsErrorKind", "load_native",
 ]
 

@@ -28,6 +28,8 @@ SG_MAX_AD_LEN = 255
 SG_MAX_RECORD_LEN = 32768
 SG_MSG_MAX_LEN = 0xFFFFFFC0
 SG_MSG_KEEP_FAILED = 0x1
+SG_MSG_RFC8439 = 0x100
+SG_RFC8439_NONCE_LEN = 12
 
 # Every symbol include/suruga_gpu.h declares (checked by tests/test_abi.py).
 EXPORTS = [
@@ -41,8 +43,10 @@ EXPORTS = [
     "sg_sha256", "sg_hmac_sha256", "sg_prf_new", "sg_prf_get_bytes", "sg_prf_free",
     "sg_derive_keys", "sg_finished_verify_data",
     "sg_msg_workspace_size", "sg_seal_msg_dev", "sg_open_msg_dev", "sg_seal_msg", "sg_open_msg",
-    "sg_msg_plan_for", "sg_set_msg_groups",
+    "sg_seal_msg_rfc8439", "sg_open_msg_rfc8439",
+    "sg_msg_plan_for", "sg_msg_plan_for_flags", "sg_set_msg_groups",
     "sg_msg_batch_workspace_size", "sg_seal_msg_batch", "sg_open_msg_batch", "sg_msg_batch_plan_for",
+    "sg_msg_batch_plan_for_flags",
 ]
 SG_MSG_BATCH_MAX_COUNT = 1 << 20
 SG_MSG_MAX_GROUPS = 1024
@@ -96,6 +100,7 @@ class SgMsg(C.Structure):
         ("out", C.c_void_p),
         ("status", C.c_void_p),
         ("flags", C.c_uint32),
+        ("nonce_hi", C.c_uint8 * 4),  # SG_MSG_RFC8439 only; the struct's former padding
         ("stream", C.c_void_p),
         ("workspace", C.c_void_p),
         ("workspace_size", C.c_size_t),
@@ -116,6 +121,7 @@ class SgMsgItem(C.Structure):
     _fields_ = [
         ("key_index", C.c_uint32),
         ("nonce", C.c_uint8 * 8),
+        ("nonce_hi", C.c_uint8 * 4),  # SG_MSG_RFC8439 only; the struct's former padding
         ("ad", C.c_void_p),
         ("ad_len", C.c_uint64),
         ("in_", C.c_void_p),
@@ -287,12 +293,14 @@ def _declare(lib: C.CDLL) -> None:
     for f in (lib.sg_seal_msg_dev, lib.sg_open_msg_dev):
         f.restype = C.c_int
         f.argtypes = [C.POINTER(SgMsg)]
-    for f in (lib.sg_seal_msg, lib.sg_open_msg):
+    for f in (lib.sg_seal_msg, lib.sg_open_msg, lib.sg_seal_msg_rfc8439, lib.sg_open_msg_rfc8439):
         f.restype = C.c_int
         f.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
                       C.c_char_p, C.c_size_t, u8p]
     lib.sg_msg_plan_for.restype = C.c_int
     lib.sg_msg_plan_for.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(SgMsgPlan)]
+    lib.sg_msg_plan_for_flags.restype = C.c_int
+    lib.sg_msg_plan_for_flags.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(SgMsgPlan)]
     lib.sg_set_msg_groups.restype = C.c_int
     lib.sg_set_msg_groups.argtypes = [C.c_int]
     lib.sg_msg_batch_workspace_size.restype = C.c_size_t
@@ -305,6 +313,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.sg_msg_batch_plan_for.argtypes = [u64p, u64p, C.c_uint32, C.c_uint32, C.POINTER(SgMsgBatchPlan),
                                           C.POINTER(SgMsgPlan), C.POINTER(SgMsgSeg), C.c_uint32,
                                           C.POINTER(SgMsgSpan), C.POINTER(SgMsgSpan)]
+    lib.sg_msg_batch_plan_for_flags.restype = C.c_int
+    lib.sg_msg_batch_plan_for_flags.argtypes = [u64p, u64p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                C.POINTER(SgMsgBatchPlan), C.POINTER(SgMsgPlan), C.POINTER(SgMsgSeg),
+                                                C.c_uint32, C.POINTER(SgMsgSpan), C.POINTER(SgMsgSpan)]
 
 
 def load(path: Path | None = None) -> C.CDLL:

@@ -14,6 +14,10 @@ the parity tests read like the reference's own tests:
 * ``ChaCha20Poly1305`` (chacha20_poly1305.rs:102-135): the only suite,
   ``TLS_ECDHE_RSA_WITH_CHACHA20_POLY1305_SHA256`` (0xcc, 0x13, mod.rs:108-114),
   backed by the gfx950 kernels through the C ABI.
+* ``ChaCha20Poly1305Rfc8439``: the same traits over RFC 8439 (12-byte nonce,
+  padded MAC stream), through the message path's host forms
+  (``sg_seal_msg_rfc8439`` / ``sg_open_msg_rfc8439``).  The record calls and
+  the suite above speak only the draft.
 """
 from __future__ import annotations
 
@@ -165,6 +169,64 @@ class ChaCha20Poly1305(Aead):
 
     def new_decryptor(self, key: bytes) -> ChaCha20Poly1305Decryptor:
         return ChaCha20Poly1305Decryptor(key, self.device)
+
+
+def _check_nonce12(nonce: bytes) -> bytes:
+    nonce = bytes(nonce)
+    if len(nonce) != N.SG_RFC8439_NONCE_LEN:
+        raise ValueError(f"nonce must be {N.SG_RFC8439_NONCE_LEN} bytes, got {len(nonce)}")
+    return nonce
+
+
+class ChaCha20Poly1305Rfc8439Encryptor(_GpuCtx, Encryptor):
+    """RFC 8439 section 2.8 (AEAD_CHACHA20_POLY1305), any length."""
+
+    def encrypt(self, nonce: bytes, plain: bytes, ad: bytes) -> bytes:
+        nonce, plain, ad = _check_nonce12(nonce), bytes(plain), bytes(ad)
+        out = (C.c_uint8 * (len(plain) + N.SG_MAC_LEN))()
+        N.check(self._lib.sg_seal_msg_rfc8439(self._ptr, nonce, len(nonce), plain, len(plain), ad, len(ad), out))
+        return bytes(out)
+
+
+class ChaCha20Poly1305Rfc8439Decryptor(_GpuCtx, Decryptor):
+    def decrypt(self, nonce: bytes, encrypted: bytes, ad: bytes) -> bytes:
+        nonce, encrypted, ad = _check_nonce12(nonce), bytes(encrypted), bytes(ad)
+        n = max(len(encrypted) - N.SG_MAC_LEN, 0)
+        out = (C.c_uint8 * max(n, 1))()
+        rc = N.check(self._lib.sg_open_msg_rfc8439(self._ptr, nonce, len(nonce), encrypted, len(encrypted), ad,
+                                                   len(ad), out))
+        if rc == N.SG_E_SHORT:
+            raise TlsError(TlsErrorKind.BadRecordMac, "message too short")
+        if rc == N.SG_E_BAD_MAC:
+            raise TlsError(TlsErrorKind.BadRecordMac, "wrong mac")
+        return bytes(out)[:n]
+
+    def mac_len(self) -> int:
+        return N.SG_MAC_LEN
+
+
+class ChaCha20Poly1305Rfc8439(Aead):
+    """The ``Aead`` of RFC 8439: key 32, fixed IV 12 (RFC 7905 section 2), tag
+    16.  Nonces are the caller's 12 bytes; RFC 7905's derivation (write IV XOR
+    sequence number) is the record layer's and is not built here."""
+
+    def __init__(self, device: int = 0):
+        self.device = device
+
+    def key_size(self) -> int:
+        return N.SG_KEY_LEN
+
+    def fixed_iv_len(self) -> int:
+        return N.SG_RFC8439_NONCE_LEN
+
+    def mac_len(self) -> int:
+        return N.SG_MAC_LEN
+
+    def new_encryptor(self, key: bytes) -> ChaCha20Poly1305Rfc8439Encryptor:
+        return ChaCha20Poly1305Rfc8439Encryptor(key, self.device)
+
+    def new_decryptor(self, key: bytes) -> ChaCha20Poly1305Rfc8439Decryptor:
+        return ChaCha20Poly1305Rfc8439Decryptor(key, self.device)
 
 
 class CipherSuite(enum.Enum):

@@ -110,14 +110,16 @@ __device__ __forceinline__ uint32_t sbswap32(uint32_t x) {
 constexpr uint32_t kSigma0 = 0x61707865u, kSigma1 = 0x3320646eu, kSigma2 = 0x79622d32u, kSigma3 = 0x6b206574u;
 
 // One keystream block (chacha20.rs:25-51 state, :53-109 round20).  k[8] key
-// words, ctr = state word 12 (word 13 is always 0: chacha20.rs:114-121),
-// n14/n15 = nonce words.  ks[i] = round20(state)[i] (little-endian words).
-__device__ __forceinline__ void chacha_block(uint32_t ks[16], const uint32_t k[8], uint32_t ctr, uint32_t n14,
-                                             uint32_t n15) {
+// words, ctr = state word 12, n13 = state word 13, n14/n15 = nonce words.
+// ks[i] = round20(state)[i] (little-endian words).  Word 13 is 0 in the draft
+// construction (chacha20.rs:114-121) and the first nonce word in RFC 8439
+// (section 2.3), which only the message kernels speak.
+__device__ __forceinline__ void chacha_block(uint32_t ks[16], const uint32_t k[8], uint32_t ctr, uint32_t n13,
+                                             uint32_t n14, uint32_t n15) {
     uint32_t x0 = kSigma0, x1 = kSigma1, x2 = kSigma2, x3 = kSigma3;
     uint32_t x4 = k[0], x5 = k[1], x6 = k[2], x7 = k[3];
     uint32_t x8 = k[4], x9 = k[5], x10 = k[6], x11 = k[7];
-    uint32_t x12 = ctr, x13 = 0u, x14 = n14, x15 = n15;
+    uint32_t x12 = ctr, x13 = n13, x14 = n14, x15 = n15;
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         SG_QR(x0, x4, x8, x12) SG_QR(x1, x5, x9, x13) SG_QR(x2, x6, x10, x14) SG_QR(x3, x7, x11, x15)
@@ -126,7 +128,12 @@ __device__ __forceinline__ void chacha_block(uint32_t ks[16], const uint32_t k[8
     ks[0] = x0 + kSigma0; ks[1] = x1 + kSigma1; ks[2] = x2 + kSigma2; ks[3] = x3 + kSigma3;
     ks[4] = x4 + k[0]; ks[5] = x5 + k[1]; ks[6] = x6 + k[2]; ks[7] = x7 + k[3];
     ks[8] = x8 + k[4]; ks[9] = x9 + k[5]; ks[10] = x10 + k[6]; ks[11] = x11 + k[7];
-    ks[12] = x12 + ctr; ks[13] = x13; ks[14] = x14 + n14; ks[15] = x15 + n15;
+    ks[12] = x12 + ctr; ks[13] = x13 + n13; ks[14] = x14 + n14; ks[15] = x15 + n15;
+}
+// the draft's form: word 13 is always 0
+__device__ __forceinline__ void chacha_block(uint32_t ks[16], const uint32_t k[8], uint32_t ctr, uint32_t n14,
+                                             uint32_t n15) {
+    chacha_block(ks, k, ctr, 0u, n14, n15);
 }
 
 // ---- uniform-record variant: the counter-free part of round 1 on the SALU ----
@@ -142,18 +149,22 @@ struct ChaChaPre {
     uint32_t x[16];  // state after the counter-free part of round 1 (x12 unused)
 };
 
-// k, n14, n15 must be wave-uniform.
-__device__ __forceinline__ ChaChaPre chacha_pre(const uint32_t k[8], uint32_t n14, uint32_t n15) {
+// k, n13, n14, n15 must be wave-uniform.
+__device__ __forceinline__ ChaChaPre chacha_pre(const uint32_t k[8], uint32_t n13, uint32_t n14, uint32_t n15) {
     uint32_t x1 = 0x3320646eu, x2 = 0x79622d32u, x3 = 0x6b206574u;
     uint32_t x5 = k[1], x6 = k[2], x7 = k[3], x9 = k[5], x10 = k[6], x11 = k[7];
-    uint32_t x13 = 0u, x14 = n14, x15 = n15;
+    uint32_t x13 = n13, x14 = n14, x15 = n15;
     SG_QR_S(x1, x5, x9, x13) SG_QR_S(x2, x6, x10, x14) SG_QR_S(x3, x7, x11, x15)
     return ChaChaPre{{0x61707865u + k[0], x1, x2, x3, k[0], x5, x6, x7, k[4], x9, x10, x11, 0u, x13, x14, x15}};
 }
+__device__ __forceinline__ ChaChaPre chacha_pre(const uint32_t k[8], uint32_t n14, uint32_t n15) {
+    return chacha_pre(k, 0u, n14, n15);
+}
 
-// Same result as chacha_block(ks, k, ctr, n14, n15), starting from chacha_pre.
+// Same result as chacha_block(ks, k, ctr, n13, n14, n15), starting from
+// chacha_pre(k, n13, n14, n15).
 __device__ __forceinline__ void chacha_block_pre(uint32_t ks[16], const ChaChaPre& P, const uint32_t k[8],
-                                                 uint32_t ctr, uint32_t n14, uint32_t n15) {
+                                                 uint32_t ctr, uint32_t n13, uint32_t n14, uint32_t n15) {
     uint32_t x0 = P.x[0], x1 = P.x[1], x2 = P.x[2], x3 = P.x[3];
     uint32_t x4 = P.x[4], x5 = P.x[5], x6 = P.x[6], x7 = P.x[7];
     uint32_t x8 = P.x[8], x9 = P.x[9], x10 = P.x[10], x11 = P.x[11];
@@ -172,7 +183,11 @@ __device__ __forceinline__ void chacha_block_pre(uint32_t ks[16], const ChaChaPr
     ks[0] = x0 + 0x61707865u; ks[1] = x1 + 0x3320646eu; ks[2] = x2 + 0x79622d32u; ks[3] = x3 + 0x6b206574u;
     ks[4] = x4 + k[0]; ks[5] = x5 + k[1]; ks[6] = x6 + k[2]; ks[7] = x7 + k[3];
     ks[8] = x8 + k[4]; ks[9] = x9 + k[5]; ks[10] = x10 + k[6]; ks[11] = x11 + k[7];
-    ks[12] = x12 + ctr; ks[13] = x13; ks[14] = x14 + n14; ks[15] = x15 + n15;
+    ks[12] = x12 + ctr; ks[13] = x13 + n13; ks[14] = x14 + n14; ks[15] = x15 + n15;
+}
+__device__ __forceinline__ void chacha_block_pre(uint32_t ks[16], const ChaChaPre& P, const uint32_t k[8],
+                                                 uint32_t ctr, uint32_t n14, uint32_t n15) {
+    chacha_block_pre(ks, P, k, ctr, 0u, n14, n15);
 }
 
 // ---- Poly1305 field arithmetic, radix 2^26 ---------------------------------

@@ -1,10 +1,17 @@
 // sg_msg.hip -- gfx950 kernels of the long-message path: one message (one key,
-// one 8-byte nonce, n data bytes, adlen AD bytes, any lengths up to
-// SG_MSG_MAX_LEN) sealed or opened by a persistent grid over the whole chip.
-// Same construction as every other path of the library
-// (chacha20_poly1305.rs:19-94): Poly1305 key = keystream block 0, data byte i
-// XORed with keystream block 1 + i / 64, counter in state word 12 only, MAC
-// over ad || le64(adlen) || ct || le64(n) without padding.
+// one nonce, n data bytes, adlen AD bytes, any lengths up to SG_MSG_MAX_LEN)
+// sealed or opened by a persistent grid over the whole chip.  Two
+// constructions, chosen at compile time by the MsgLayout parameter:
+//   * the draft, as every other path of the library
+//     (chacha20_poly1305.rs:19-94): 8-byte nonce, Poly1305 key = keystream
+//     block 0, data byte i XORed with keystream block 1 + i / 64, counter in
+//     state word 12 only, MAC over ad || le64(adlen) || ct || le64(n) without
+//     padding;
+//   * RFC 8439 (SG_MSG_RFC8439): 12-byte nonce whose first word is state word
+//     13, the same counters, MAC over ad || zeros to 16 || ct || zeros to 16 ||
+//     le64(adlen) || le64(n).
+// The text below describes the draft's stream; DESIGN.md section 4.8 says what
+// the RFC layout changes (where the bytes lie; every block is a full block).
 //
 // ChaCha20 is position-addressable.  Poly1305 is one Horner chain
 // (poly1305.rs:213-228); it is cut into independent pieces and put back
@@ -56,39 +63,41 @@ struct MsgParams {
     uint64_t n, adlen;
     uint32_t n14, n15;
     sg_msg_plan plan;
+    uint32_t n13;  // RFC 8439 only (behind the plan: the draft's argument offsets stay)
 };
 
 namespace {
 
-template <bool OPEN>
+template <bool OPEN, MsgLayout LAY>
 __global__ __launch_bounds__(256) void sg_msg_kernel(const MsgParams p) {
     __shared__ __attribute__((aligned(64))) uint8_t lds[kLdsBytes];
     const uint32_t lane = threadIdx.x;
-    const MsgKey mk = msg_key(p.key, p.n14, p.n15);
+    const uint32_t n13 = LAY == MsgLayout::kRfc8439 ? p.n13 : 0u;
+    const MsgKey mk = msg_key(p.key, n13, p.n14, p.n15);
     const MsgR rr = msg_r(mk);
     const F26 r = words_to_f26(mk.r0, mk.r1, mk.r2, mk.r3, 0u);
     const F26 R = fpow(r, p.plan.tile_blocks);
     const F26 Pl = msg_lane_power(r, lane);
-    const ChaChaPre pre = chacha_pre(mk.k, p.n14, p.n15);
-    const MsgStream m = msg_stream(p.ad, p.in, p.out, p.n14, p.n15, p.n, p.adlen, p.plan.mac_blocks,
-                                   p.plan.zero_blocks, p.plan.tile_blocks, p.plan.tile_bytes);
+    const ChaChaPre pre = chacha_pre(mk.k, n13, p.n14, p.n15);
+    const MsgStream m = msg_stream<LAY>(p.ad, p.in, p.out, n13, p.n14, p.n15, p.n, p.adlen, p.plan.mac_blocks,
+                                        p.plan.zero_blocks, p.plan.tile_blocks, p.plan.tile_bytes);
 
     const uint64_t t0 = (uint64_t)blockIdx.x * p.plan.tiles_per_group;
     uint64_t t1 = t0 + p.plan.tiles_per_group;
     if (t1 > p.plan.tiles) t1 = p.plan.tiles;
 
     F26 acc = f26_zero();
-    for (uint64_t t = t0; t < t1; ++t) msg_tile<OPEN>(lds, lane, m, mk, pre, rr, R, t, acc);
+    for (uint64_t t = t0; t < t1; ++t) msg_tile<OPEN, LAY>(lds, lane, m, mk, pre, rr, R, t, acc);
     // ---- the group's partial: sum of the lanes' chains, each at its place in a tile
     const F26 Hg = block_sum(fmul(acc, Pl), reinterpret_cast<uint32_t*>(lds), lane);
     if (lane == 0u) store_f26(p.ws + (uint64_t)blockIdx.x * kMsgPartialWords, Hg);
 }
 
-template <bool OPEN>
+template <bool OPEN, MsgLayout LAY>
 __global__ __launch_bounds__(256) void sg_msg_finish_kernel(const MsgParams p) {
     __shared__ uint32_t red[5u * (256u + 16u)];
     const uint32_t lane = threadIdx.x;
-    const MsgKey mk = msg_key(p.key, p.n14, p.n15);
+    const MsgKey mk = msg_key(p.key, LAY == MsgLayout::kRfc8439 ? p.n13 : 0u, p.n14, p.n15);
     const F26 R = fpow(words_to_f26(mk.r0, mk.r1, mk.r2, mk.r3, 0u), p.plan.tile_blocks);
     F26 sum = f26_zero();
     for (uint32_t g = lane; g < p.plan.groups; g += 256u) {  // <= 4 terms per lane
@@ -111,9 +120,32 @@ __global__ __launch_bounds__(256) void sg_msg_scrub_kernel(uint8_t* out, const u
 
 }  // namespace
 
-hipError_t launch_msg(const uint8_t* key, const uint8_t nonce[8], const uint8_t* ad, uint64_t adlen, const uint8_t* in,
-                      uint8_t* out, uint64_t n, uint8_t* status, uint32_t* ws, const sg_msg_plan& plan, bool open,
-                      bool scrub, hipStream_t s) {
+namespace {
+
+template <MsgLayout LAY>
+void launch_msg_kernels(const MsgParams& p, bool open, bool scrub, hipStream_t s) {
+    const sg_msg_plan& plan = p.plan;
+    if (open) {
+        hipLaunchKernelGGL((sg_msg_kernel<true, LAY>), dim3(plan.groups), dim3(kMsgThreads), 0, s, p);
+        hipLaunchKernelGGL((sg_msg_finish_kernel<true, LAY>), dim3(1), dim3(256), 0, s, p);
+        if (scrub && p.n) {
+            const uint64_t blocks = (p.n / 16u + 1023u) / 1024u;
+            const uint32_t grid = blocks < 1u ? 1u : (blocks > 4096u ? 4096u : (uint32_t)blocks);
+            hipLaunchKernelGGL(sg_msg_scrub_kernel, dim3(grid), dim3(256), 0, s, p.out, p.n, (const uint8_t*)p.status);
+        }
+    } else {
+        hipLaunchKernelGGL((sg_msg_kernel<false, LAY>), dim3(plan.groups), dim3(kMsgThreads), 0, s, p);
+        hipLaunchKernelGGL((sg_msg_finish_kernel<false, LAY>), dim3(1), dim3(256), 0, s, p);
+    }
+}
+
+}  // namespace
+
+// nonce_hi: NULL = the draft (word 13 is 0), else the first four bytes of the
+// RFC 8439 nonce; the plan is the one of that layout (sg_msg_plan_for_flags)
+hipError_t launch_msg(const uint8_t* key, const uint8_t nonce[8], const uint8_t* nonce_hi, const uint8_t* ad,
+                      uint64_t adlen, const uint8_t* in, uint8_t* out, uint64_t n, uint8_t* status, uint32_t* ws,
+                      const sg_msg_plan& plan, bool open, bool scrub, hipStream_t s) {
     if (plan.tile_blocks != kMsgTileBlocks || plan.groups == 0u || plan.groups > kMsgMaxGroups)
         return hipErrorInvalidValue;
     MsgParams p;
@@ -125,22 +157,15 @@ hipError_t launch_msg(const uint8_t* key, const uint8_t nonce[8], const uint8_t*
     p.ws = ws;
     p.n = n;
     p.adlen = adlen;
-    // the nonce as two little-endian words (chacha20.rs:45-46)
+    // the nonce as little-endian words (chacha20.rs:45-46; RFC 8439 section 2.3)
+    p.n13 = nonce_hi ? dev::le32(nonce_hi) : 0u;
     p.n14 = dev::le32(nonce);
     p.n15 = dev::le32(nonce + 4);
     p.plan = plan;
-    if (open) {
-        hipLaunchKernelGGL((sg_msg_kernel<true>), dim3(plan.groups), dim3(kMsgThreads), 0, s, p);
-        hipLaunchKernelGGL((sg_msg_finish_kernel<true>), dim3(1), dim3(256), 0, s, p);
-        if (scrub && n) {
-            const uint64_t blocks = (n / 16u + 1023u) / 1024u;
-            const uint32_t grid = blocks < 1u ? 1u : (blocks > 4096u ? 4096u : (uint32_t)blocks);
-            hipLaunchKernelGGL(sg_msg_scrub_kernel, dim3(grid), dim3(256), 0, s, out, n, (const uint8_t*)status);
-        }
-    } else {
-        hipLaunchKernelGGL((sg_msg_kernel<false>), dim3(plan.groups), dim3(kMsgThreads), 0, s, p);
-        hipLaunchKernelGGL((sg_msg_finish_kernel<false>), dim3(1), dim3(256), 0, s, p);
-    }
+    if (nonce_hi)
+        launch_msg_kernels<MsgLayout::kRfc8439>(p, open, scrub, s);
+    else
+        launch_msg_kernels<MsgLayout::kDraft>(p, open, scrub, s);
     return hipGetLastError();
 }
 

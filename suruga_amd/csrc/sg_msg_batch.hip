@@ -1,6 +1,7 @@
 // sg_msg_batch.hip -- gfx950 kernels of the message batch: many messages, each
 // with its own key, nonce, AD and lengths (any, up to SG_MSG_MAX_LEN), sealed
-// or opened by one persistent grid.  The decomposition of one message is that
+// or opened by one persistent grid, the whole call in the draft construction or
+// (SG_MSG_RFC8439) in RFC 8439.  The decomposition of one message is that
 // of sg_msg.hip, tile for tile (the tile body, the keying and the finish are
 // the shared code of sg_msg_device.h); here it is applied across messages:
 //
@@ -54,16 +55,17 @@ __device__ __forceinline__ T* uload(T* const* p) {
 }
 
 // data bytes [d0, d1) of tiles [a, b) of a message: the tile body's own cut
+template <MsgLayout LAY>
 __device__ __forceinline__ void seg_data_range(const uint64_t zero_blocks, const uint64_t n, const uint64_t adlen,
                                                const uint32_t a, const uint32_t b, int64_t* d0, int64_t* d1) {
-    const int64_t P = (int64_t)adlen + 8;
+    const int64_t P = msg_ct_offset<LAY>((int64_t)adlen);
     const int64_t s0 = (int64_t)a * (int64_t)kMsgTileBytes - 16 * (int64_t)zero_blocks;
     const int64_t s1 = (int64_t)b * (int64_t)kMsgTileBytes - 16 * (int64_t)zero_blocks;
     *d0 = s0 - P > 0 ? s0 - P : 0;
     *d1 = s1 - P < (int64_t)n ? s1 - P : (int64_t)n;
 }
 
-template <bool OPEN>
+template <bool OPEN, MsgLayout LAY>
 __global__ __launch_bounds__(256) void sg_msg_batch_kernel(const MsgBatchParams p) {
     __shared__ __attribute__((aligned(64))) uint8_t lds[kLdsBytes];
     const uint32_t lane = threadIdx.x;
@@ -76,19 +78,20 @@ __global__ __launch_bounds__(256) void sg_msg_batch_kernel(const MsgBatchParams 
         const MsgBatchItem* it = p.items + mi;
         if (uload(&it->skip) != 0u) continue;  // an open of fewer than 16 bytes: nothing is touched
         const uint32_t n14 = uload(&it->n14), n15 = uload(&it->n15);
+        const uint32_t n13 = LAY == MsgLayout::kRfc8439 ? uload(&it->n13) : 0u;
         // ---- the message's keying, as sg_msg_kernel's
-        const MsgKey mk = msg_key(uload(&it->key), n14, n15);
+        const MsgKey mk = msg_key(uload(&it->key), n13, n14, n15);
         const MsgR rr = msg_r(mk);
         const F26 r = words_to_f26(mk.r0, mk.r1, mk.r2, mk.r3, 0u);
         const F26 R = fpow(r, kMsgTileBlocks);
         const F26 Pl = msg_lane_power(r, lane);
-        const ChaChaPre pre = chacha_pre(mk.k, n14, n15);
+        const ChaChaPre pre = chacha_pre(mk.k, n13, n14, n15);
         const sg_msg_plan* pl = p.plans + mi;
-        const MsgStream m = msg_stream(uload(&it->ad), uload(&it->in), uload(&it->out), n14, n15, uload(&it->n),
-                                       uload(&it->adlen), uload(&pl->mac_blocks), uload(&pl->zero_blocks),
-                                       kMsgTileBlocks, kMsgTileBytes);
+        const MsgStream m = msg_stream<LAY>(uload(&it->ad), uload(&it->in), uload(&it->out), n13, n14, n15,
+                                            uload(&it->n), uload(&it->adlen), uload(&pl->mac_blocks),
+                                            uload(&pl->zero_blocks), kMsgTileBlocks, kMsgTileBytes);
         F26 acc = f26_zero();
-        for (uint64_t t = ta; t < tb; ++t) msg_tile<OPEN>(lds, lane, m, mk, pre, rr, R, t, acc);
+        for (uint64_t t = ta; t < tb; ++t) msg_tile<OPEN, LAY>(lds, lane, m, mk, pre, rr, R, t, acc);
         // ---- the segment's partial: sum of the lanes' chains, each at its place in a tile
         const F26 Hs = block_sum(fmul(acc, Pl), reinterpret_cast<uint32_t*>(lds), lane);
         if (lane == 0u) store_f26(p.partials + (uint64_t)sgi * kMsgPartialWords, Hs);
@@ -117,7 +120,7 @@ __device__ __forceinline__ F26 wave_sum(const F26 x, uint32_t* red, const uint32
 
 constexpr uint32_t kFinishWaves = 4;  // messages per workgroup of the finish kernel
 
-template <bool OPEN>
+template <bool OPEN, MsgLayout LAY>
 __global__ __launch_bounds__(256) void sg_msg_batch_finish_kernel(const MsgBatchParams p) {
     __shared__ uint32_t red[kFinishWaves][5u * (64u + 4u)];
     const uint32_t wave = threadIdx.x >> 6, wl = threadIdx.x & 63u;
@@ -129,7 +132,8 @@ __global__ __launch_bounds__(256) void sg_msg_batch_finish_kernel(const MsgBatch
             if (wl == 0u) p.status[mi] = (uint8_t)SG_E_SHORT;  // chacha20_poly1305.rs:68-70
         return;
     }
-    const MsgKey mk = msg_key(uload(&it->key), uload(&it->n14), uload(&it->n15));
+    const MsgKey mk = msg_key(uload(&it->key), LAY == MsgLayout::kRfc8439 ? uload(&it->n13) : 0u, uload(&it->n14),
+                              uload(&it->n15));
     const F26 R = fpow(words_to_f26(mk.r0, mk.r1, mk.r2, mk.r3, 0u), kMsgTileBlocks);
     const uint32_t tiles = (uint32_t)uload(&p.plans[mi].tiles);  // < 2^30
     const uint32_t first = uload(&p.msg_segs[mi].first), cnt = uload(&p.msg_segs[mi].count);
@@ -148,6 +152,7 @@ __global__ __launch_bounds__(256) void sg_msg_batch_finish_kernel(const MsgBatch
 // A failed open hands out no plaintext (chacha20_poly1305.rs:89-93): the grid
 // of the batch kernel again, every segment zeroing its own data bytes of a
 // message whose status says SG_E_BAD_MAC.
+template <MsgLayout LAY>
 __global__ __launch_bounds__(256) void sg_msg_batch_scrub_kernel(const MsgBatchParams p) {
     const uint32_t first = uload(&p.group_segs[blockIdx.x].first);
     const uint32_t end = first + uload(&p.group_segs[blockIdx.x].count);
@@ -158,16 +163,31 @@ __global__ __launch_bounds__(256) void sg_msg_batch_scrub_kernel(const MsgBatchP
         const MsgBatchItem* it = p.items + mi;
         const uint64_t n = uload(&it->n);
         int64_t d0, d1;
-        seg_data_range(uload(&p.plans[mi].zero_blocks), n, uload(&it->adlen), uload(&sg->tile_begin),
-                       uload(&sg->tile_end), &d0, &d1);
+        seg_data_range<LAY>(uload(&p.plans[mi].zero_blocks), n, uload(&it->adlen), uload(&sg->tile_begin),
+                            uload(&sg->tile_end), &d0, &d1);
         if (d1 > d0) msg_zero(uload(&it->out) + d0, (uint64_t)(d1 - d0), threadIdx.x, 256u);
+    }
+}
+
+template <MsgLayout LAY>
+void launch_msg_batch_kernels(const MsgBatchParams& p, uint32_t groups, bool open, bool scrub, hipStream_t s) {
+    const dim3 fin((p.count + kFinishWaves - 1u) / kFinishWaves);
+    if (open) {
+        hipLaunchKernelGGL((sg_msg_batch_kernel<true, LAY>), dim3(groups), dim3(kMsgThreads), 0, s, p);
+        hipLaunchKernelGGL((sg_msg_batch_finish_kernel<true, LAY>), fin, dim3(256), 0, s, p);
+        if (scrub) hipLaunchKernelGGL(sg_msg_batch_scrub_kernel<LAY>, dim3(groups), dim3(256), 0, s, p);
+    } else {
+        hipLaunchKernelGGL((sg_msg_batch_kernel<false, LAY>), dim3(groups), dim3(kMsgThreads), 0, s, p);
+        hipLaunchKernelGGL((sg_msg_batch_finish_kernel<false, LAY>), fin, dim3(256), 0, s, p);
     }
 }
 
 }  // namespace
 
+// rfc8439: the whole call speaks RFC 8439 (the items carry n13, the plans are
+// those of that layout); else the draft
 hipError_t launch_msg_batch(const MsgBatchLayout& l, void* ws, uint32_t count, uint32_t groups, uint8_t* status,
-                            bool open, bool scrub, hipStream_t s) {
+                            bool open, bool scrub, bool rfc8439, hipStream_t s) {
     if (count == 0u || groups == 0u || groups > kMsgMaxGroups) return hipErrorInvalidValue;
     uint8_t* w = (uint8_t*)ws;
     MsgBatchParams p;
@@ -179,15 +199,10 @@ hipError_t launch_msg_batch(const MsgBatchLayout& l, void* ws, uint32_t count, u
     p.partials = (uint32_t*)(w + l.partials);
     p.status = status;
     p.count = count;
-    const dim3 fin((count + kFinishWaves - 1u) / kFinishWaves);
-    if (open) {
-        hipLaunchKernelGGL((sg_msg_batch_kernel<true>), dim3(groups), dim3(kMsgThreads), 0, s, p);
-        hipLaunchKernelGGL((sg_msg_batch_finish_kernel<true>), fin, dim3(256), 0, s, p);
-        if (scrub) hipLaunchKernelGGL(sg_msg_batch_scrub_kernel, dim3(groups), dim3(256), 0, s, p);
-    } else {
-        hipLaunchKernelGGL((sg_msg_batch_kernel<false>), dim3(groups), dim3(kMsgThreads), 0, s, p);
-        hipLaunchKernelGGL((sg_msg_batch_finish_kernel<false>), fin, dim3(256), 0, s, p);
-    }
+    if (rfc8439)
+        launch_msg_batch_kernels<MsgLayout::kRfc8439>(p, groups, open, scrub, s);
+    else
+        launch_msg_batch_kernels<MsgLayout::kDraft>(p, groups, open, scrub, s);
     return hipGetLastError();
 }
 

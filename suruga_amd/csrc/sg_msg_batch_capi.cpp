@@ -7,6 +7,7 @@
 // CPU path.
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -15,12 +16,19 @@
 #include "sg_host.h"
 #include "sg_msg_plan.h"
 
+// nonce_hi lies in what was padding: every size and offset is the one the
+// header compiled to before the field existed
+static_assert(sizeof(sg_msg_item) == 56 && offsetof(sg_msg_item, nonce) == 4 && offsetof(sg_msg_item, nonce_hi) == 12 &&
+                  offsetof(sg_msg_item, ad) == 16,
+              "sg_msg_item layout (SG_ABI_VERSION 1)");
+static_assert(sizeof(sg_msg_batch) == 64 && offsetof(sg_msg_batch, stream) == 40, "sg_msg_batch layout (SG_ABI_VERSION 1)");
+
 namespace sg {
 // sg_msg_batch.hip: the batch kernel, the finish kernel and (open, scrub) the
 // zeroing of the failed messages' outputs, all on stream s, reading the tables
 // at the front of ws
 hipError_t launch_msg_batch(const MsgBatchLayout& l, void* ws, uint32_t count, uint32_t groups, uint8_t* status,
-                            bool open, bool scrub, hipStream_t s);
+                            bool open, bool scrub, bool rfc8439, hipStream_t s);
 }  // namespace sg
 
 namespace {
@@ -87,7 +95,8 @@ void staging_release(Staging* st, hipStream_t s, bool copied) {
 
 int run_msg_batch(const sg_msg_batch* b, bool open) {
     if (!b) return fail(SG_E_ARG, "batch is NULL%s");
-    if (b->flags & ~SG_MSG_KEEP_FAILED) return fail(SG_E_ARG, "unknown flags%s");
+    if (b->flags & ~sg::kMsgKnownFlags) return fail(SG_E_ARG, "unknown flags%s");
+    const bool rfc = (b->flags & SG_MSG_RFC8439) != 0u;  // the whole call; else no nonce_hi is read
     if (b->count > SG_MSG_BATCH_MAX_COUNT) return fail(SG_E_ARG, "count exceeds SG_MSG_BATCH_MAX_COUNT%s");
     if (b->count == 0) return SG_OK;
     if (!b->keys || b->num_keys == 0 || !b->items) return fail(SG_E_ARG, "keys and items must be non-NULL%s");
@@ -151,16 +160,19 @@ int run_msg_batch(const sg_msg_batch* b, bool open) {
         d.out = m.out;
         d.n = n[i];
         d.adlen = adlen[i];
-        // the nonce as two little-endian words (chacha20.rs:45-46)
+        // the nonce as little-endian words (chacha20.rs:45-46); RFC 8439
+        // (section 2.3): nonce_hi in front of them, in state word 13
         d.n14 = (uint32_t)m.nonce[0] | (uint32_t)m.nonce[1] << 8 | (uint32_t)m.nonce[2] << 16 | (uint32_t)m.nonce[3] << 24;
         d.n15 = (uint32_t)m.nonce[4] | (uint32_t)m.nonce[5] << 8 | (uint32_t)m.nonce[6] << 16 | (uint32_t)m.nonce[7] << 24;
         d.skip = open && m.in_len < SG_MAC_LEN ? 1u : 0u;
-        d.pad_ = 0u;
+        d.n13 = rfc ? (uint32_t)m.nonce_hi[0] | (uint32_t)m.nonce_hi[1] << 8 | (uint32_t)m.nonce_hi[2] << 16 |
+                          (uint32_t)m.nonce_hi[3] << 24
+                    : 0u;
     }
     sg_msg_batch_plan plan;
-    rc = sg_msg_batch_plan_for(n, adlen, count, (uint32_t)sg::msg_groups(), &plan, (sg_msg_plan*)(h + lay.plans),
-                               (sg_msg_seg*)(h + lay.segs), lay.seg_cap, (sg_msg_span*)(h + lay.group_segs),
-                               (sg_msg_span*)(h + lay.msg_segs));
+    rc = sg_msg_batch_plan_for_flags(n, adlen, count, b->flags & SG_MSG_RFC8439, (uint32_t)sg::msg_groups(), &plan,
+                                     (sg_msg_plan*)(h + lay.plans), (sg_msg_seg*)(h + lay.segs), lay.seg_cap,
+                                     (sg_msg_span*)(h + lay.group_segs), (sg_msg_span*)(h + lay.msg_segs));
     if (rc != SG_OK) {
         staging_release(st, s, false);
         if (cached) sg::scratch_release(cached, s, false);
@@ -170,7 +182,7 @@ int run_msg_batch(const sg_msg_batch* b, bool open) {
     staging_release(st, s, he == hipSuccess);
     if (he == hipSuccess)
         he = sg::launch_msg_batch(lay, ws, count, plan.groups, b->status, open,
-                                  open && !(b->flags & SG_MSG_KEEP_FAILED), s);
+                                  open && !(b->flags & SG_MSG_KEEP_FAILED), rfc, s);
     if (cached) sg::scratch_release(cached, s, true);
     rc = he == hipSuccess ? SG_OK : sg::hip_fail(he, "message batch launch");
     if (!b->stream) {

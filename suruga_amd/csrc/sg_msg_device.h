@@ -15,8 +15,29 @@ namespace {
 
 using namespace dev;
 
-// tile bytes at [kLdsFront + A, + kMsgTileBytes), A < 64; the 16-byte chunks the
-// tile's edges cut are stored whole: up to 15 bytes before and behind the tile
+// The MAC stream's layout, a compile-time parameter of the tile body and of
+// the kernels built on it:
+//   kDraft    ad || le64(adlen) || ct || le64(n), no padding
+//             (chacha20_poly1305.rs:19-42); state word 13 is 0
+//   kRfc8439  ad || zeros to 16 || ct || zeros to 16 || le64(adlen) || le64(n)
+//             (RFC 8439 section 2.8); state word 13 is the first nonce word
+// The ciphertext starts at stream offset P and the stream is L bytes long.
+enum class MsgLayout { kDraft, kRfc8439 };
+
+template <MsgLayout LAY>
+__host__ __device__ constexpr int64_t msg_ct_offset(int64_t adlen) {
+    return LAY == MsgLayout::kRfc8439 ? (adlen + 15) / 16 * 16 : adlen + 8;
+}
+template <MsgLayout LAY>
+__host__ __device__ constexpr int64_t msg_stream_bytes(int64_t adlen, int64_t n) {
+    return LAY == MsgLayout::kRfc8439 ? msg_ct_offset<LAY>(adlen) + (n + 15) / 16 * 16 + 16
+                                      : msg_ct_offset<LAY>(adlen) + n + 8;
+}
+
+// tile bytes at [kLdsFront + A, + kMsgTileBytes), A = (s0 - P) & 63 < 64; the
+// 16-byte chunks the tile's edges cut are stored whole: up to 15 bytes before
+// and behind the tile.  RFC 8439: P and s0 are multiples of 16, so A is 0, 16,
+// 32 or 48 and no chunk is cut by a tile's edge: the same room bounds it.
 constexpr uint32_t kLdsFront = 64;
 constexpr uint32_t kLdsBytes = kLdsFront + 64u + kMsgTileBytes + 16u;
 static_assert(kLdsBytes >= 5u * 4u * (256u + 16u), "reduction space");
@@ -28,13 +49,14 @@ struct MsgKey {
 };
 
 // key bytes at any alignment -> little-endian words (chacha20.rs:37-39), block
-// 0 -> Poly1305 key (chacha20_poly1305.rs:50); everything wave-uniform
-__device__ __forceinline__ MsgKey msg_key(const uint8_t* key, uint32_t n14, uint32_t n15) {
+// 0 -> Poly1305 key (chacha20_poly1305.rs:50; RFC 8439 section 2.6, with the
+// nonce's first word n13 in state word 13); everything wave-uniform
+__device__ __forceinline__ MsgKey msg_key(const uint8_t* key, uint32_t n13, uint32_t n14, uint32_t n15) {
     MsgKey mk;
 #pragma unroll
     for (int i = 0; i < 8; ++i) mk.k[i] = uniform(le32(key + 4 * i));
     uint32_t ks[16];
-    chacha_block(ks, mk.k, 0u, n14, n15);
+    chacha_block(ks, mk.k, 0u, n13, n14, n15);
     const PolyKey pk = poly_key(ks);
     mk.r0 = uniform(pk.r0);
     mk.r1 = uniform(pk.r1);
@@ -70,7 +92,7 @@ struct MsgStream {
     const uint8_t* ad;
     const uint8_t* in;
     uint8_t* out;
-    uint32_t n14, n15;
+    uint32_t n13, n14, n15;
     int64_t n, adlen;
     int64_t P;       // stream offset of the ciphertext
     int64_t L;       // stream length
@@ -81,24 +103,27 @@ struct MsgStream {
     uint32_t rem;    // its bytes, 1..16
 };
 
-__device__ __forceinline__ MsgStream msg_stream(const uint8_t* ad, const uint8_t* in, uint8_t* out, uint32_t n14,
-                                                uint32_t n15, uint64_t n, uint64_t adlen, uint64_t mac_blocks,
-                                                uint64_t zero_blocks, uint32_t tile_blocks, uint32_t tile_bytes) {
+template <MsgLayout LAY>
+__device__ __forceinline__ MsgStream msg_stream(const uint8_t* ad, const uint8_t* in, uint8_t* out, uint32_t n13,
+                                                uint32_t n14, uint32_t n15, uint64_t n, uint64_t adlen,
+                                                uint64_t mac_blocks, uint64_t zero_blocks, uint32_t tile_blocks,
+                                                uint32_t tile_bytes) {
     MsgStream m;
     m.ad = ad;
     m.in = in;
     m.out = out;
+    m.n13 = n13;
     m.n14 = n14;
     m.n15 = n15;
     m.n = (int64_t)n;
     m.adlen = (int64_t)adlen;
-    m.P = m.adlen + 8;
-    m.L = m.P + m.n + 8;
+    m.P = msg_ct_offset<LAY>(m.adlen);
+    m.L = msg_stream_bytes<LAY>(m.adlen, m.n);
     m.TB = (int64_t)tile_bytes;
     m.tile_blocks = tile_blocks;
     m.z = zero_blocks;
     m.last = m.z + mac_blocks - 1u;
-    m.rem = (uint32_t)(m.L - 16 * ((int64_t)mac_blocks - 1));
+    m.rem = (uint32_t)(m.L - 16 * ((int64_t)mac_blocks - 1));  // RFC 8439: always 16
     return m;
 }
 
@@ -115,7 +140,7 @@ __device__ __forceinline__ MsgR msg_r(const MsgKey& mk) {
 // MAC stream out in LDS and step the lane's four blocks from h = 0 into the
 // lane's chain acc = acc R + f.  Ends behind a barrier: the next tile's stores
 // follow this tile's loads.
-template <bool OPEN>
+template <bool OPEN, MsgLayout LAY>
 __device__ __forceinline__ void msg_tile(uint8_t* lds, const uint32_t lane, const MsgStream& p, const MsgKey& mk,
                                          const ChaChaPre& pre, const MsgR& rr, const F26& R, const uint64_t t,
                                          F26& acc) {
@@ -161,7 +186,7 @@ __device__ __forceinline__ void msg_tile(uint8_t* lds, const uint32_t lane, cons
                 }
             }
             uint32_t ks[16];
-            chacha_block_pre(ks, pre, mk.k, (uint32_t)cb + 1u, p.n14, p.n15);  // data uses blocks 1.. (:52)
+            chacha_block_pre(ks, pre, mk.k, (uint32_t)cb + 1u, p.n13, p.n14, p.n15);  // data uses blocks 1.. (:52)
             if (full) {
                 // every fetched chunk is consumed ahead of the first store: one
                 // wait for the loads, none between the stores
@@ -215,14 +240,27 @@ __device__ __forceinline__ void msg_tile(uint8_t* lds, const uint32_t lane, cons
     // ---- framing bytes of the tile: ad || le64(adlen) in front, le64(n) and
     // the zeros that fill the final block behind (chacha20_poly1305.rs:24-30)
     // (the block lanes above store nothing into these bytes, so no order is needed)
+    // RFC 8439 (section 2.8): ad || zeros [adlen, P) in front; behind the data
+    // the zeros [P + n, P + 16 ceil(n / 16)), then le64(adlen), then le64(n)
     if (s0 < P || s1e > P + n) {  // uniform
         int64_t a = s0 > 0 ? s0 : 0, b = s1e < P ? s1e : P;
-        for (int64_t s = a + lane; s < b; s += kMsgThreads)
-            tl[s - s0] = s < adlen ? p.ad[s] : (uint8_t)((uint64_t)adlen >> (8 * (s - adlen)));
+        for (int64_t s = a + lane; s < b; s += kMsgThreads) {
+            if constexpr (LAY == MsgLayout::kRfc8439)
+                tl[s - s0] = s < adlen ? p.ad[s] : (uint8_t)0;
+            else
+                tl[s - s0] = s < adlen ? p.ad[s] : (uint8_t)((uint64_t)adlen >> (8 * (s - adlen)));
+        }
         a = s0 > P + n ? s0 : P + n;
         for (int64_t s = a + lane; s < s1e; s += kMsgThreads) {
             const int64_t i = s - (P + n);
-            tl[s - s0] = i < 8 ? (uint8_t)((uint64_t)n >> (8 * i)) : (uint8_t)0;
+            if constexpr (LAY == MsgLayout::kRfc8439) {
+                const int64_t q = i - ((16 - (n & 15)) & 15);  // place in the length block
+                tl[s - s0] = q < 0 || q >= 16 ? (uint8_t)0
+                             : q < 8 ? (uint8_t)((uint64_t)adlen >> (8 * q))
+                                     : (uint8_t)((uint64_t)n >> (8 * (q - 8)));
+            } else {
+                tl[s - s0] = i < 8 ? (uint8_t)((uint64_t)n >> (8 * i)) : (uint8_t)0;
+            }
         }
     }
     __syncthreads();
@@ -240,7 +278,7 @@ __device__ __forceinline__ void msg_tile(uint8_t* lds, const uint32_t lane, cons
             if (vb < z) {  // virtual: value 0, no pad bit
                 m = u32x4{0u, 0u, 0u, 0u};
                 pad = 0u;
-            } else if (vb == p.last && p.rem < 16u) {
+            } else if (LAY == MsgLayout::kDraft && vb == p.last && p.rem < 16u) {
                 // a short final block carries its pad bit at its own length
                 // (poly1305.rs:216-225; the bytes behind the stream are zero)
                 const uint32_t fb = 1u << (8u * (p.rem & 3u));

@@ -1,7 +1,8 @@
 // sg_msg_plan.cpp -- the launch geometry of one long message (host only, no
-// HIP): how the MAC stream ad || le64(|ad|) || ct || le64(|ct|)
-// (chacha20_poly1305.rs:19-42) is cut into tiles and the tiles into
-// workgroups.  The kernels of sg_msg.hip take the struct computed here as a
+// HIP): how the MAC stream -- ad || le64(|ad|) || ct || le64(|ct|)
+// (chacha20_poly1305.rs:19-42), or with SG_MSG_RFC8439 the padded stream of
+// RFC 8439 section 2.8 (msg_stream_len) -- is cut into tiles and the tiles
+// into workgroups.  The kernels of sg_msg.hip take the struct computed here as a
 // kernel argument, so the plan the tests check is the plan that runs.  The
 // batch plan (sg_msg_batch_plan_for, for sg_msg_batch.hip) applies the same
 // geometry per message and cuts the messages' tiles into the groups' segments.
@@ -25,10 +26,10 @@ int msg_groups() { return groups_setting().load(); }
 
 extern "C" {
 
-int sg_msg_plan_for(uint64_t n, uint64_t adlen, uint32_t groups, sg_msg_plan* out) {
-    if (!out || n > SG_MSG_MAX_LEN || adlen > SG_MSG_MAX_LEN) return SG_E_ARG;
+int sg_msg_plan_for_flags(uint64_t n, uint64_t adlen, uint32_t flags, uint32_t groups, sg_msg_plan* out) {
+    if (!out || n > SG_MSG_MAX_LEN || adlen > SG_MSG_MAX_LEN || (flags & ~sg::kMsgKnownFlags)) return SG_E_ARG;
     // both lengths < 2^32: the stream length stays far below 2^64
-    const uint64_t L = adlen + 16u + n;
+    const uint64_t L = sg::msg_stream_len(n, adlen, flags);
     const uint64_t B = (L + 15u) / 16u;  // >= 1
     const uint64_t K = sg::kMsgTileBlocks;
     const uint64_t T = (B + K - 1u) / K;  // >= 1
@@ -47,19 +48,24 @@ int sg_msg_plan_for(uint64_t n, uint64_t adlen, uint32_t groups, sg_msg_plan* ou
     return SG_OK;
 }
 
+int sg_msg_plan_for(uint64_t n, uint64_t adlen, uint32_t groups, sg_msg_plan* out) {
+    return sg_msg_plan_for_flags(n, adlen, 0u, groups, out);
+}
+
 // The batch plan: every message keeps its own tile geometry, the tiles of all
 // messages form one sequence, the groups take equal contiguous runs of it and
 // a run is cut where a message ends.  One pass over the messages with the
 // group boundary moving along: O(count + groups).
-int sg_msg_batch_plan_for(const uint64_t* n, const uint64_t* adlen, uint32_t count, uint32_t groups,
-                          sg_msg_batch_plan* plan, sg_msg_plan* msgs, sg_msg_seg* segs, uint32_t seg_cap,
-                          sg_msg_span* group_segs, sg_msg_span* msg_segs) {
-    if (!plan || count > SG_MSG_BATCH_MAX_COUNT || (count && (!n || !adlen))) return SG_E_ARG;
+int sg_msg_batch_plan_for_flags(const uint64_t* n, const uint64_t* adlen, uint32_t count, uint32_t flags,
+                                uint32_t groups, sg_msg_batch_plan* plan, sg_msg_plan* msgs, sg_msg_seg* segs,
+                                uint32_t seg_cap, sg_msg_span* group_segs, sg_msg_span* msg_segs) {
+    if (!plan || count > SG_MSG_BATCH_MAX_COUNT || (count && (!n || !adlen)) || (flags & ~sg::kMsgKnownFlags))
+        return SG_E_ARG;
     const uint64_t K = sg::kMsgTileBlocks;
     uint64_t TT = 0;
     for (uint32_t m = 0; m < count; ++m) {
         sg_msg_plan one;
-        if (sg_msg_plan_for(n[m], adlen[m], groups, &one) != SG_OK) return SG_E_ARG;
+        if (sg_msg_plan_for_flags(n[m], adlen[m], flags, groups, &one) != SG_OK) return SG_E_ARG;
         if (msgs) msgs[m] = one;
         TT += one.tiles;  // < 2^20 * 2^19
     }
@@ -78,7 +84,7 @@ int sg_msg_batch_plan_for(const uint64_t* n, const uint64_t* adlen, uint32_t cou
     uint64_t g = 0;       // the group that owns global tile `base + a`
     uint64_t base = 0;    // global index of the message's tile 0
     for (uint32_t m = 0; m < count; ++m) {
-        const uint64_t B = (adlen[m] + 16u + n[m] + 15u) / 16u;
+        const uint64_t B = (sg::msg_stream_len(n[m], adlen[m], flags) + 15u) / 16u;
         const uint64_t T = (B + K - 1u) / K;
         const uint32_t first = S;
         for (uint64_t a = 0; a < T;) {
@@ -101,6 +107,12 @@ int sg_msg_batch_plan_for(const uint64_t* n, const uint64_t* adlen, uint32_t cou
     }
     plan->segments = S;
     return SG_OK;
+}
+
+int sg_msg_batch_plan_for(const uint64_t* n, const uint64_t* adlen, uint32_t count, uint32_t groups,
+                          sg_msg_batch_plan* plan, sg_msg_plan* msgs, sg_msg_seg* segs, uint32_t seg_cap,
+                          sg_msg_span* group_segs, sg_msg_span* msg_segs) {
+    return sg_msg_batch_plan_for_flags(n, adlen, count, 0u, groups, plan, msgs, segs, seg_cap, group_segs, msg_segs);
 }
 
 int sg_set_msg_groups(int n) {

@@ -27,17 +27,30 @@ constexpr uint32_t kMsgPartialWords = 8;  // 5 radix-2^26 limbs, padded to 32 by
 
 int msg_groups();  // sg_set_msg_groups / SG_MSG_GROUPS
 
+// Bytes of a message's MAC stream: ad || le64(adlen) || ct || le64(n) in the
+// draft; with SG_MSG_RFC8439 ad and ct are each padded with zeros to a
+// multiple of 16 and one block le64(adlen) || le64(n) follows (RFC 8439
+// section 2.8).  Both lengths <= SG_MSG_MAX_LEN: far below 2^64.
+inline uint64_t msg_stream_len(uint64_t n, uint64_t adlen, uint32_t flags) {
+    if (flags & SG_MSG_RFC8439) return (adlen + 15u) / 16u * 16u + (n + 15u) / 16u * 16u + 16u;
+    return adlen + 16u + n;
+}
+// the flags the plan functions and the message calls know
+constexpr uint32_t kMsgKnownFlags = SG_MSG_KEEP_FAILED | SG_MSG_RFC8439;
+
 // ---- the message batch (sg_msg_batch.hip, sg_msg_batch_capi.cpp)
 // One message as the batch kernels read it (wave-uniform loads): the host
-// resolves the key index and the nonce words.  skip: an open of fewer than 16
-// bytes -- no kernel touches its buffers, the finish kernel reports SG_E_SHORT.
+// resolves the key index and the nonce words (n13: state word 13, the first
+// word of an RFC 8439 nonce; 0 and never read in the draft).  skip: an open of
+// fewer than 16 bytes -- no kernel touches its buffers, the finish kernel
+// reports SG_E_SHORT.
 struct MsgBatchItem {
     const uint8_t* key;
     const uint8_t* ad;
     const uint8_t* in;
     uint8_t* out;
     uint64_t n, adlen;
-    uint32_t n14, n15, skip, pad_;
+    uint32_t n14, n15, skip, n13;
 };
 static_assert(sizeof(MsgBatchItem) == 64, "device layout");
 

@@ -12,11 +12,17 @@ Per size (1 MiB, 64 MiB, 1 GiB of device-resident data, 13 bytes of AD):
   as n / 16,384 uniform 16 KiB TLS records with sg_set_lockstep(0) (size-class
   kernels) and sg_set_lockstep(1) (wave-per-record kernel).
 
+With ``--rfc8439`` a second message leg, ``msg_rfc_seal`` / ``msg_rfc_open``
+(SG_MSG_RFC8439: 12-byte nonce, padded MAC stream), runs beside the draft leg
+at the same sizes, checked once per size against OpenSSL's
+EVP "ChaCha20-Poly1305" where libcrypto loads (``rfc_check``), and
+``rfc_vs_draft_*`` is its time over the draft leg's.
+
 The legs alternate launch by launch in one process, so they share the clock
 the board holds.  ``spread`` of a leg is (max - min) / median over its repeats:
 the yardstick for "no slower than the lockstep-0 leg" at 1 GiB.
 
-    python tools/msg_bench.py [--sizes 1048576,67108864,1073741824] [--reps 25] [--groups 0]
+    python tools/msg_bench.py [--sizes 1048576,67108864,1073741824] [--reps 25] [--groups 0] [--rfc8439]
 """
 from __future__ import annotations
 
@@ -34,6 +40,7 @@ sys.path.insert(0, str(ROOT / "tests"))
 HBM_BYTES_PER_S = 8e12
 REC = 16384
 ADLEN = 13
+NONCE12 = bytes([0xC1, 0x52, 0xE3, 0x74, 9, 8, 7, 6, 5, 4, 3, 2])
 
 
 def summary(ms: list, n: int, traffic: int) -> dict:
@@ -43,7 +50,7 @@ def summary(ms: list, n: int, traffic: int) -> dict:
             "hbm_fraction": round(traffic / (med * 1e-3) / HBM_BYTES_PER_S, 4), "launches": len(ms)}
 
 
-def run_size(n: int, reps: int, warmup: int) -> dict:
+def run_size(n: int, reps: int, warmup: int, rfc8439: bool = False) -> dict:
     import torch
 
     from suruga_amd import _native as N
@@ -88,6 +95,18 @@ def run_size(n: int, reps: int, warmup: int) -> dict:
         "batch_ls0_open": (lockstep(0), lambda: B.open_(open_b)),
         "batch_ls1_open": (lockstep(1), lambda: B.open_(open_b)),
     }
+    if rfc8439:
+        ct_r = torch.empty(n + 16, dtype=torch.uint8, device="cuda")
+        back_r = torch.empty(n, dtype=torch.uint8, device="cuda")
+        st_r = torch.zeros(1, dtype=torch.uint8, device="cuda")
+        legs["msg_rfc_seal"] = (None, lambda: msg.seal_msg(key_t, NONCE12, pt, ct_r, ad=ad_t, workspace=ws,
+                                                            rfc8439=True))
+        legs["msg_rfc_open"] = (None, lambda: msg.open_(key_t, NONCE12, ct_r, back_r, st_r, ad=ad_t, workspace=ws,
+                                                        rfc8439=True))
+        # every leg once per round, the two message legs side by side
+        order = ("msg_seal", "msg_rfc_seal", "batch_ls0_seal", "batch_ls1_seal",
+                 "msg_open", "msg_rfc_open", "batch_ls0_open", "batch_ls1_open")
+        legs = {k: legs[k] for k in order}
     prev = lib.sg_set_lockstep(-1)
     times = {k: [] for k in legs}
     try:
@@ -107,12 +126,16 @@ def run_size(n: int, reps: int, warmup: int) -> dict:
     torch.cuda.synchronize()
     assert int(st.item()) == 0 and int(st_b.sum().item()) == 0, "open status"
     assert torch.equal(back, pt) and torch.equal(back_b, pt), "round trip"
+    if rfc8439:
+        assert int(st_r.item()) == 0 and torch.equal(back_r, pt), "RFC 8439 round trip"
 
     out = {"n": n, "adlen": ADLEN, "plan": msg.plan_for(n, ADLEN, max(msg.set_groups(-1), 0))}
     for name, ms in times.items():
         out[name] = summary(ms, n, 2 * n + 16 + ADLEN)
     for d in ("seal", "open"):
         out[f"msg_vs_ls0_{d}"] = round(out[f"msg_{d}"]["ms"] / out[f"batch_ls0_{d}"]["ms"], 4)
+        if rfc8439:
+            out[f"rfc_vs_draft_{d}"] = round(out[f"msg_rfc_{d}"]["ms"] / out[f"msg_{d}"]["ms"], 4)
     return out
 
 
@@ -141,6 +164,34 @@ def check_size(n: int) -> dict:
     return res
 
 
+def check_size_rfc8439(n: int) -> dict:
+    """One RFC 8439 seal of the size's message against OpenSSL (every byte and the tag)."""
+    import torch
+
+    import rfc8439_ref
+    from suruga_amd import batch as B
+    from suruga_amd import msg
+
+    ossl = rfc8439_ref.openssl()
+    if ossl is None:
+        return {"openssl": None}
+    key, ad = bytes(range(32)), bytes(range(ADLEN))
+    key_t = torch.tensor(list(key), dtype=torch.uint8, device="cuda")
+    ad_t = torch.tensor(list(ad), dtype=torch.uint8, device="cuda")
+    pt = torch.empty(n, dtype=torch.uint8, device="cuda")
+    B.fill_records(pt, REC, REC, n // REC, 0x6D7367)
+    ct = torch.empty(n + 16, dtype=torch.uint8, device="cuda")
+    msg.seal_msg(key_t, NONCE12, pt, ct, ad=ad_t, rfc8439=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    want = ossl.seal(key, NONCE12, pt.cpu().numpy().tobytes(), ad)
+    secs = time.perf_counter() - t0
+    got = ct.cpu().numpy().tobytes()
+    res = {"openssl": ossl.version, "openssl_s": round(secs, 2), "tag_ok": got[-16:] == want[-16:], "ct_ok": got == want}
+    assert res["tag_ok"] and res["ct_ok"], "RFC 8439 message differs from OpenSSL"
+    return res
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--sizes", default="1048576,67108864,1073741824")
@@ -148,6 +199,7 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--groups", type=int, default=None, help="sg_set_msg_groups (default: leave the setting)")
     ap.add_argument("--no-check", action="store_true", help="skip the oracle comparison")
+    ap.add_argument("--rfc8439", action="store_true", help="add the RFC 8439 message leg beside the draft leg")
     args = ap.parse_args()
     if args.reps < 20:
         ap.error("--reps must be at least 20")
@@ -173,13 +225,15 @@ def main() -> None:
         sampler = devmon.Sampler(bus, period=0.002).start() if n == max(sizes) else None
         t0 = time.perf_counter()
         # the oracle check runs apart from the sampled, timed legs
-        r = run_size(n, args.reps, args.warmup)
+        r = run_size(n, args.reps, args.warmup, args.rfc8439)
         if sampler:
             clk = sampler.stop(t0, time.perf_counter())
             res["clock"] = {"sclk_mhz": clk["sclk_mhz"], "board_power_w": clk["board_power_w"],
                             "power_cap_w": clk.get("power_cap_w")}
         if not args.no_check:
             r.update(check_size(n))
+            if args.rfc8439:
+                r["rfc_check"] = check_size_rfc8439(n)
         res["sizes"].append(r)
     print(json.dumps(res))
 
