@@ -204,6 +204,33 @@ size_t sg_workspace_size(uint32_t count);
 int sg_seal_batch(const sg_batch* b);
 int sg_open_batch(const sg_batch* b);
 
+/* The record batch in RFC 8439 (section 2.8; the construction SG_MSG_RFC8439
+ * names further below): the suites deployed peers negotiate -- TLS 1.2
+ * 0xCCA8 / 0xCCA9 (RFC 7905), TLS 1.3 and QUIC records -- where the two calls
+ * above speak draft-agl-04 (0xCC13).  `b` is the unchanged sg_batch and means
+ * what it means above (flags, statuses, SG_E_SHORT, SG_STATUS_SKIPPED, the
+ * scrub, workspace, stream and capture rules, SG_MAX_RECORD_LEN,
+ * SG_MAX_AD_LEN), except for the nonce:
+ *   explicit mode: nonce_i = nonces + 12*i, 12 bytes (SG_RFC8439_NONCE_LEN);
+ *     state words 13-15 are its three little-endian words.  ads / ad_len /
+ *     ad_stride as above.  A TLS 1.3 or QUIC caller passes its 5-byte header
+ *     as AD and its own nonces.
+ *   SG_BATCH_TLS (RFC 7905 section 2): nonce_i = ivs[key_i] XOR
+ *     (00 00 00 00 || be64(seq_i)), key_i the record's (clamped) key index;
+ *     the AD is the 13 bytes be64(seq) || type || major || minor || be16(n).
+ * SG_E_ARG, before any GPU work: x NULL, x->flags non-zero, ivs not 4-byte
+ * aligned, ivs NULL in TLS mode, unknown b->flags, and whatever the draft
+ * calls reject.  Uniform 16 KiB batches run on the wave-per-record kernel and
+ * every other batch on the size classes (the packed kernel and the 4-16 KiB
+ * buckets of mixed draft batches are not built for this construction). */
+typedef struct sg_batch_rfc8439 {
+    const uint8_t* ivs;   /* device, [num_keys][12], 4-byte aligned: TLS mode only */
+    uint32_t       flags; /* 0; anything else SG_E_ARG */
+    uint32_t       _pad;
+} sg_batch_rfc8439;
+int sg_seal_batch_rfc8439(const sg_batch* b, const sg_batch_rfc8439* x);
+int sg_open_batch_rfc8439(const sg_batch* b, const sg_batch_rfc8439* x);
+
 /* ---- long messages: any data and AD length, one message over the whole chip
  * Encryptor::encrypt / Decryptor::decrypt take data and additional data of any
  * length (cipher/mod.rs:22-32, chacha20_poly1305.rs:19-94).  sg_seal, sg_open
@@ -522,6 +549,14 @@ void sg_prf_free(sg_prf* prf);
 int  sg_derive_keys(uint32_t count, const uint8_t* pre_master, size_t pm_len, size_t pm_stride,
                     const uint8_t* client_random, const uint8_t* server_random, uint8_t* master_secret,
                     uint8_t* client_write_keys, uint8_t* server_write_keys, int threads);
+/* The same with the write IVs of RFC 7905 section 2 ([count][12] each): the key
+ * block is 88 bytes, the two 32-byte keys (as above, the same bytes) and then
+ * client_write_IV and server_write_IV (RFC 5246 section 6.3 with no MAC keys).
+ * The IVs feed sg_batch_rfc8439.ivs. */
+int  sg_derive_keys_ivs(uint32_t count, const uint8_t* pre_master, size_t pm_len, size_t pm_stride,
+                        const uint8_t* client_random, const uint8_t* server_random, uint8_t* master_secret,
+                        uint8_t* client_write_keys, uint8_t* server_write_keys, uint8_t* client_write_ivs,
+                        uint8_t* server_write_ivs, int threads);
 /* client.rs:184-192 (server = 0, "client finished") / :213-221 (server = 1,
  * "server finished"): PRF(master_secret, label || handshake_hash)[0..12]. */
 int  sg_finished_verify_data(const uint8_t master_secret[48], int server,

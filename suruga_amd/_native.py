@@ -35,13 +35,13 @@ SG_RFC8439_NONCE_LEN = 12
 EXPORTS = [
     "sg_key_size", "sg_fixed_iv_len", "sg_mac_len", "sg_abi_version",
     "sg_ctx_new", "sg_ctx_free", "sg_seal", "sg_open",
-    "sg_workspace_size", "sg_seal_batch", "sg_open_batch",
+    "sg_workspace_size", "sg_seal_batch", "sg_open_batch", "sg_seal_batch_rfc8439", "sg_open_batch_rfc8439",
     "sg_fill_records", "sg_compare_records",
     "sg_last_error", "sg_build_info", "sg_source_hash", "sg_set_timing", "sg_timing_read", "sg_set_lockstep", "sg_set_packed",
     "sg_wire_bound", "sg_write_records", "sg_read_records", "sg_parse_records", "sg_record_timing",
     "sg_host_register", "sg_host_unregister",
     "sg_sha256", "sg_hmac_sha256", "sg_prf_new", "sg_prf_get_bytes", "sg_prf_free",
-    "sg_derive_keys", "sg_finished_verify_data",
+    "sg_derive_keys", "sg_derive_keys_ivs", "sg_finished_verify_data",
     "sg_msg_workspace_size", "sg_seal_msg_dev", "sg_open_msg_dev", "sg_seal_msg", "sg_open_msg",
     "sg_seal_msg_rfc8439", "sg_open_msg_rfc8439",
     "sg_msg_plan_for", "sg_msg_plan_for_flags", "sg_set_msg_groups",
@@ -85,6 +85,12 @@ class SgBatch(C.Structure):
         ("workspace", C.c_void_p),
         ("workspace_size", C.c_size_t),
     ]
+
+
+class SgBatchRfc8439(C.Structure):
+    """Mirror of ``struct sg_batch_rfc8439``."""
+
+    _fields_ = [("ivs", C.c_void_p), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
 
 
 class SgMsg(C.Structure):
@@ -237,6 +243,9 @@ def _declare(lib: C.CDLL) -> None:
     for f in (lib.sg_seal_batch, lib.sg_open_batch):
         f.restype = C.c_int
         f.argtypes = [C.POINTER(SgBatch)]
+    for f in (lib.sg_seal_batch_rfc8439, lib.sg_open_batch_rfc8439):
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(SgBatch), C.POINTER(SgBatchRfc8439)]
     lib.sg_fill_records.restype = C.c_int
     lib.sg_fill_records.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64,
                                     C.c_uint64, C.c_void_p]
@@ -286,6 +295,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.sg_prf_free.argtypes = [vp]
     lib.sg_derive_keys.restype = C.c_int
     lib.sg_derive_keys.argtypes = [C.c_uint32, vp, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp, C.c_int]
+    lib.sg_derive_keys_ivs.restype = C.c_int
+    lib.sg_derive_keys_ivs.argtypes = [C.c_uint32, vp, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, C.c_int]
     lib.sg_finished_verify_data.restype = C.c_int
     lib.sg_finished_verify_data.argtypes = [vp, C.c_int, vp, vp]
     lib.sg_msg_workspace_size.restype = C.c_size_t

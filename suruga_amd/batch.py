@@ -7,6 +7,10 @@ This is the batched form of the record layer's hot loop: ``TlsWriter``'s
 (tls.rs:105-112 / 250-265) are built on the device from the sequence number,
 so a call carries only record bytes, lengths and keys.
 
+With ``rfc8439=True`` the same batch runs through ``sg_seal_batch_rfc8439`` /
+``sg_open_batch_rfc8439``: RFC 8439 with 12-byte nonces, and in TLS mode the
+RFC 7905 nonce (the key's write IV in ``ivs`` XOR the sequence number).
+
 Tensors are torch tensors on the GPU (PyTorch is used here only for device
 memory and streams); all arithmetic runs in the gfx950 kernels.
 """
@@ -67,6 +71,14 @@ class Batch:
     workspace: object = None          # uint8 [>= workspace_size(count)] device, or None
     stream: object = None             # torch.cuda.Stream / raw handle (0: the NULL stream) / None = current stream
     keep_failed: bool = False         # open: keep the unauthenticated plaintext of BAD_MAC records
+    rfc8439: bool = False             # RFC 8439 / RFC 7905 (explicit mode: nonces are uint8 [count, 12])
+    ivs: object = None                # rfc8439 TLS mode: uint8 [num_keys, 12] device, the write IVs
+
+    def to_c_rfc8439(self) -> N.SgBatchRfc8439:
+        x = N.SgBatchRfc8439()
+        x.ivs = _ptr(self.ivs)
+        x.flags = 0
+        return x
 
     def to_c(self) -> N.SgBatch:
         b = N.SgBatch()
@@ -107,6 +119,12 @@ def workspace_size(count: int) -> int:
 def seal(batch: Batch) -> None:
     """Seal every record: out_i = ct_i || tag_i (chacha20_poly1305.rs:48-59)."""
     cb = batch.to_c()
+    if batch.rfc8439:
+        xb = batch.to_c_rfc8439()
+        N.check(N.load().sg_seal_batch_rfc8439(C.byref(cb), C.byref(xb)))
+        return
+    if batch.ivs is not None:
+        raise ValueError("ivs belong to rfc8439=True")
     N.check(N.load().sg_seal_batch(C.byref(cb)))
 
 
@@ -116,6 +134,12 @@ def open_(batch: Batch) -> None:
     if batch.status is None:
         raise ValueError("open needs a status tensor")
     cb = batch.to_c()
+    if batch.rfc8439:
+        xb = batch.to_c_rfc8439()
+        N.check(N.load().sg_open_batch_rfc8439(C.byref(cb), C.byref(xb)))
+        return
+    if batch.ivs is not None:
+        raise ValueError("ivs belong to rfc8439=True")
     N.check(N.load().sg_open_batch(C.byref(cb)))
 
 

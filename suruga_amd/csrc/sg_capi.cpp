@@ -156,8 +156,16 @@ void ws_release(CachedWs* w, hipStream_t s, bool launched) {
     w->held = false;
 }
 
-int validate(const sg_batch* b, bool open) {
+// x: the extension of the RFC 8439 calls (NULL: the draft calls)
+int validate(const sg_batch* b, bool open, const sg_batch_rfc8439* x) {
     if (!b) return fail(SG_E_ARG, "batch is NULL%s");
+    if (x) {
+        if (x->flags) return fail(SG_E_ARG, "sg_batch_rfc8439.flags must be 0%s");
+        if (((uintptr_t)x->ivs & 3u) != 0) return fail(SG_E_ARG, "IV table must be 4-byte aligned%s");
+        if (b->flags & ~(SG_BATCH_TLS | SG_BATCH_KEEP_FAILED)) return fail(SG_E_ARG, "unknown flags%s");
+        if ((b->flags & SG_BATCH_TLS) && !x->ivs)
+            return fail(SG_E_ARG, "RFC 7905 TLS mode needs the write IVs (sg_batch_rfc8439.ivs)%s");
+    }
     if (b->count == 0) return SG_OK;
     if (!b->keys || !b->in || !b->out) return fail(SG_E_ARG, "keys/in/out must be non-NULL%s");
     if (((uintptr_t)b->keys & 3u) != 0) return fail(SG_E_ARG, "key table must be 4-byte aligned%s");
@@ -181,6 +189,7 @@ int validate(const sg_batch* b, bool open) {
 // The wave-per-record kernel (sg_wpr.hip) takes uniform batches of full
 // 16 KiB records in a 16-byte aligned strided layout; everything else runs on
 // the size-class kernels.
+// (RFC 8439 explicit mode reads its 12-byte nonces as three dwords: the same alignment)
 bool wpr_eligible(const sg_batch* b, bool open) {
     if (!sg::wpr_enabled() || b->len || b->in_off || b->out_off) return false;
     if (b->uniform_len != (open ? sg::kWprN + SG_MAC_LEN : sg::kWprN)) return false;
@@ -191,7 +200,7 @@ bool wpr_eligible(const sg_batch* b, bool open) {
 }
 
 // Keying + AEAD launches of one batch on stream s with workspace ws.
-int launch_batch(const sg_batch* b, bool open, hipStream_t s, void* ws) {
+int launch_batch(const sg_batch* b, const sg_batch_rfc8439* x, bool open, hipStream_t s, void* ws) {
     sg::KParams p;
     std::memset(&p, 0, sizeof p);
     p.keys = b->keys;
@@ -216,6 +225,8 @@ int launch_batch(const sg_batch* b, bool open, hipStream_t s, void* ws) {
     p.ad_len = p.tls ? 13u : b->ad_len;
     p.ad_stride = b->ad_stride;
     p.tls_hdr = (uint32_t)b->content_type | ((uint32_t)b->ver_major << 8) | ((uint32_t)b->ver_minor << 16);
+    p.rfc = x ? 1u : 0u;
+    p.ivs = x ? x->ivs : nullptr;
     const uint32_t maxl = b->len ? b->max_len : b->uniform_len;
     const uint32_t max_n = open ? (maxl >= 16u ? maxl - 16u : 0u) : maxl;
     const bool uniform = !b->len || sg::size_class(max_n) == 0u;
@@ -225,7 +236,9 @@ int launch_batch(const sg_batch* b, bool open, hipStream_t s, void* ws) {
     // on the populations read back), and the per-record arrays are read as
     // dwords by the bucket kernels
     // (the packed kernel, sg_pack.hip, likewise takes the 64 B-4 KiB ones)
-    if (!wpr && !uniform && p.tls && ((sg::wpr_enabled() && max_n > 4096u) || (sg::pack_enabled() && max_n >= 64u))) {
+    // (RFC 8439: the packed kernel and the buckets are not built; a mixed batch
+    // runs on the size classes alone)
+    if (!wpr && !uniform && p.tls && !p.rfc && ((sg::wpr_enabled() && max_n > 4096u) || (sg::pack_enabled() && max_n >= 64u))) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         SG_HIP(hipStreamIsCapturing(s, &cap));
         const bool ok = cap == hipStreamCaptureStatusNone &&
@@ -272,8 +285,8 @@ int launch_batch(const sg_batch* b, bool open, hipStream_t s, void* ws) {
     return SG_OK;
 }
 
-int run_batch(const sg_batch* b, bool open) {
-    int rc = validate(b, open);
+int run_batch(const sg_batch* b, bool open, const sg_batch_rfc8439* x = nullptr) {
+    int rc = validate(b, open, x);
     if (rc != SG_OK || b->count == 0) return rc;
 
     int dev = 0;
@@ -302,7 +315,7 @@ int run_batch(const sg_batch* b, bool open) {
         if ((rc = ws_acquire(d, need, s, &cws)) != SG_OK) return rc;
         ws = cws->ptr;
     }
-    rc = launch_batch(b, open, s, ws);
+    rc = launch_batch(b, x, open, s, ws);
     if (cws) ws_release(cws, s, true);
     // NULL stream: the call returns when the batch is done, whatever it returns
     if (!b->stream) {
@@ -489,6 +502,13 @@ int sg_open(sg_ctx* c, const uint8_t* nonce, size_t nonce_len, const uint8_t* in
 
 int sg_seal_batch(const sg_batch* b) { return run_batch(b, false); }
 int sg_open_batch(const sg_batch* b) { return run_batch(b, true); }
+
+static int run_batch_rfc8439(const sg_batch* b, const sg_batch_rfc8439* x, bool open) {
+    if (!x) return fail(SG_E_ARG, "sg_batch_rfc8439 is NULL%s");
+    return run_batch(b, open, x);
+}
+int sg_seal_batch_rfc8439(const sg_batch* b, const sg_batch_rfc8439* x) { return run_batch_rfc8439(b, x, false); }
+int sg_open_batch_rfc8439(const sg_batch* b, const sg_batch_rfc8439* x) { return run_batch_rfc8439(b, x, true); }
 
 int sg_fill_records(uint8_t* buf, uint64_t stride, uint32_t len, uint32_t count, uint64_t seed, uint64_t j0,
                     void* stream) {

@@ -113,7 +113,7 @@ constexpr uint32_t kSigma0 = 0x61707865u, kSigma1 = 0x3320646eu, kSigma2 = 0x796
 // words, ctr = state word 12, n13 = state word 13, n14/n15 = nonce words.
 // ks[i] = round20(state)[i] (little-endian words).  Word 13 is 0 in the draft
 // construction (chacha20.rs:114-121) and the first nonce word in RFC 8439
-// (section 2.3), which only the message kernels speak.
+// (section 2.3): the message kernels and the RecLayout::kRfc8439 record kernels.
 __device__ __forceinline__ void chacha_block(uint32_t ks[16], const uint32_t k[8], uint32_t ctr, uint32_t n13,
                                              uint32_t n14, uint32_t n15) {
     uint32_t x0 = kSigma0, x1 = kSigma1, x2 = kSigma2, x3 = kSigma3;
@@ -457,6 +457,47 @@ __device__ __forceinline__ RecKey record_key(const KParams& p, uint32_t rec) {
     return rk;
 }
 
+// The same for the RFC 8439 record batch: a 12-byte nonce in state words 13-15
+// (RFC 8439 section 2.3).  TLS mode is RFC 7905 section 2: the key's 12-byte
+// write IV XOR (00 00 00 00 || be64(seq)); explicit mode reads 12 bytes per record.
+struct RecKeyRfc {
+    uint32_t k[8];
+    uint32_t n13, n14, n15;
+    uint64_t seq;
+};
+__device__ __forceinline__ RecKeyRfc record_key_rfc(const KParams& p, uint32_t rec) {
+    RecKeyRfc rk;
+    uint32_t ki = p.key_index ? p.key_index[rec] : 0u;
+    ki = ki < p.num_keys ? ki : p.num_keys - 1u;  // (record_key's clamp: the IV table has num_keys rows too)
+    const uint32_t* kw = reinterpret_cast<const uint32_t*>(p.keys + 32u * ki);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) rk.k[i] = kw[i];
+    if (p.tls) {
+        const uint32_t* iv = reinterpret_cast<const uint32_t*>(p.ivs + 12u * ki);
+        rk.seq = p.seq ? p.seq[rec] : p.seq0 + rec;
+        rk.n13 = iv[0];
+        rk.n14 = iv[1] ^ bswap32((uint32_t)(rk.seq >> 32));
+        rk.n15 = iv[2] ^ bswap32((uint32_t)rk.seq);
+    } else {
+        const uint8_t* nb = p.nonces + 12ull * rec;
+        rk.seq = 0;
+        rk.n13 = le32(nb);
+        rk.n14 = le32(nb + 4);
+        rk.n15 = le32(nb + 8);
+    }
+    return rk;
+}
+// record_key in the shape of the layout: the draft's word 13 is 0
+template <RecLayout LAY>
+__device__ __forceinline__ RecKeyRfc record_key_of(const KParams& p, uint32_t rec) {
+    if constexpr (LAY == RecLayout::kRfc8439) {
+        return record_key_rfc(p, rec);
+    } else {
+        const RecKey d = record_key(p, rec);
+        return RecKeyRfc{{d.k[0], d.k[1], d.k[2], d.k[3], d.k[4], d.k[5], d.k[6], d.k[7]}, 0u, d.n14, d.n15, d.seq};
+    }
+}
+
 __device__ __forceinline__ uint32_t record_len(const KParams& p, uint32_t rec) {
     return p.len ? p.len[rec] : p.uniform_len;
 }
@@ -483,6 +524,12 @@ __device__ __forceinline__ uint8_t prefix_byte(const KParams& p, uint32_t rec, u
                                                uint32_t i) {
     if (i < adlen) return p.tls ? tls_ad_byte(seq, p.tls_hdr, n, i) : p.ads[(uint64_t)p.ad_stride * rec + i];
     return (uint8_t)((uint64_t)adlen >> (8u * (i - adlen)));
+}
+// Byte i (< 16 ceil(adlen / 16)) of the RFC 8439 prefix: ad, then its zero padding.
+__device__ __forceinline__ uint8_t prefix_byte_rfc(const KParams& p, uint32_t rec, uint64_t seq, uint32_t n,
+                                                   uint32_t adlen, uint32_t i) {
+    if (i < adlen) return p.tls ? tls_ad_byte(seq, p.tls_hdr, n, i) : p.ads[(uint64_t)p.ad_stride * rec + i];
+    return 0u;
 }
 
 }  // namespace dev

@@ -75,7 +75,19 @@ struct KParams {
     uint32_t lds_rec_bytes;  // LDS bytes per record slot of the launched size class
     uint32_t wpr_mix;        // mixed batch: route eligible records to the wave-per-record buckets
     uint32_t pack_mix;       // mixed batch: route eligible small records to the packed kernel (sg_pack.hip)
+    // RFC 8439 record batch (sg_*_batch_rfc8439); at the end: the offsets above stay
+    const uint8_t* ivs;      // TLS mode under rfc: write IVs [num_keys][12] (RFC 7905), 4-byte aligned
+    uint32_t rfc;            // 1 = RFC 8439 construction (RecLayout::kRfc8439 kernels), 0 = the draft
 };
+
+// The construction a record kernel computes, chosen at compile time (as
+// MsgLayout in sg_msg_device.h): the draft (8-byte nonce, state word 13 = 0,
+// MAC stream ad || le64(|ad|) || ct || le64(|ct|)) or RFC 8439 section 2.8
+// (12-byte nonce in words 13-15, MAC stream ad || 0.. || ct || 0.. ||
+// le64(|ad|) || le64(|ct|), every block full).  The size classes and the
+// uniform 16 KiB wave-per-record launch exist in both; the packed kernel and
+// the J = 2..4 buckets are draft only (KParams.wpr_mix / pack_mix stay 0 under rfc).
+enum class RecLayout { kDraft, kRfc8439 };
 
 // Size classes of the AEAD kernel: class c (0..7) holds records of
 // n <= 128 << c bytes (class 7: the rest, up to SG_MAX_RECORD_LEN) and gives
@@ -104,6 +116,9 @@ __host__ __device__ constexpr uint32_t class_mac_lanes(uint32_t c) { return clas
 __host__ __device__ constexpr uint32_t class_max(uint32_t c) { return c < 7u ? 128u << c : 0xffffffffu; }
 // LDS bytes of one record slot: virtual-block space (16 bytes x max virtual blocks
 // 2*PL) | ad || le64 (16-rounded) | ct (64-rounded) | le64(n) + zeros
+// The RFC 8439 stream fits the same slot: its AD region 16 ceil(adlen / 16)
+// is <= 16 ceil((adlen + 8) / 16), and behind the ciphertext it writes at most
+// 15 zeros and the 16-byte length block, 31 <= 64 bytes.
 __host__ __device__ inline uint32_t lds_rec_bytes(uint32_t cls, uint32_t adlen, uint32_t max_n) {
     const uint32_t PL = class_mac_lanes(cls);
     return 32u * PL + ((adlen + 8u + 15u) & ~15u) + ((max_n + 63u) & ~63u) + 64u;

@@ -31,6 +31,14 @@
 // All Poly1305 arithmetic is exact mod p = 2^130 - 5, so the tag equals the
 // reference's sequential Horner result bit for bit.
 //
+// The keying and AEAD kernels take the construction as a template parameter
+// (RecLayout, sg_internal.h).  RecLayout::kRfc8439 (sg_*_batch_rfc8439) differs
+// in three places: the 12-byte nonce fills state words 13-15 (record_key_rfc,
+// sg_device.h: explicit, or the RFC 7905 write IV XOR the sequence number), the
+// MAC stream is framed in LDS as ad || 0.. || ct || 0.. || le64(|ad|) ||
+// le64(|ct|), and mac_geom's stream length counts the padding (every block is
+// full).  The draft instantiations compile to what they were before the parameter.
+//
 // The launchers at the end are what the rest of the library sees of this file
 // (sg_internal.h); the dispatcher of a batch is sg_dispatch.cpp.
 #include "sg_internal.h"
@@ -54,9 +62,13 @@ using namespace dev;
 struct MacGeom {
     uint32_t L, B, k, z;
 };
+// (RFC 8439: ad and ct are each zero-padded to 16 bytes and one block
+// le64(adlen) || le64(n) closes the stream, so every block is full)
+template <RecLayout LAY>
 __device__ __forceinline__ MacGeom mac_geom(uint32_t adlen, uint32_t n, uint32_t PL) {
     MacGeom g;
-    g.L = adlen + 16u + n;
+    if constexpr (LAY == RecLayout::kRfc8439) g.L = ((adlen + 15u) & ~15u) + ((n + 15u) & ~15u) + 16u;
+    else g.L = adlen + 16u + n;
     g.B = (g.L + 15u) >> 4;
     g.k = (g.B + PL - 1u) / PL;
     g.k |= 1u;
@@ -100,7 +112,7 @@ __device__ __forceinline__ bool rec_pack(const KParams& p, uint32_t rec, uint32_
 // KeyJobs (sg_internal.h): njobs == 0 keys every record of the batch by
 // index; otherwise the records of up to kNumClasses lists (mixed batches key
 // only their size-class records here), job i on blocks [blk0[i], blk0[i+1]).
-template <bool OPEN>
+template <bool OPEN, RecLayout LAY>
 __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const KeyJobs jobs) {
     constexpr uint32_t kKeyLdsStride = kKeyRecWords + 1;
     __shared__ uint32_t stage[kKeyingThreads * kKeyLdsStride];
@@ -125,9 +137,9 @@ __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const Ke
     const uint32_t n = OPEN ? (len >= 16u ? len - 16u : 0u) : len;
     out[kKeyRecWords] = 0u;  // nothing to write unless keyed below
     if (act) {
-        const RecKey rk = record_key(p, rec);
+        const RecKeyRfc rk = record_key_of<LAY>(p, rec);
         uint32_t ks[16];
-        chacha_block(ks, rk.k, 0u, rk.n14, rk.n15);  // block 0 -> poly key (chacha20_poly1305.rs:50)
+        chacha_block(ks, rk.k, 0u, rk.n13, rk.n14, rk.n15);  // block 0 -> poly key (chacha20_poly1305.rs:50)
         const PolyKey pk = poly_key(ks);
         out[kR32Off + 0] = pk.r0;
         out[kR32Off + 1] = pk.r1;
@@ -138,7 +150,7 @@ __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const Ke
         out[kSOff + 2] = pk.s[2];
         out[kSOff + 3] = pk.s[3];
         const uint32_t adlen = p.tls ? 13u : p.ad_len;
-        const MacGeom g = mac_geom(adlen, n, mac_lanes(n));
+        const MacGeom g = mac_geom<LAY>(adlen, n, mac_lanes(n));
         const F26 r = words_to_f26(pk.r0, pk.r1, pk.r2, pk.r3, 0u);
         // R = r^k by square-and-multiply; then R^0..R^7 and R^0, R^8, .., R^56.
         // mul_add outputs are valid multipliers as they stand (limb 1 may exceed
@@ -187,7 +199,7 @@ __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const Ke
 // otherwise); PL = min(L, 64) of them run the MAC.  Per record, in LDS:
 //   [0, S) virtual-block space | S: ad | le64(adlen) | A: ct (n) | le64(n) | zeros
 // ---------------------------------------------------------------------------
-template <bool OPEN, uint32_t L>
+template <bool OPEN, uint32_t L, RecLayout LAY>
 __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec, const bool active,
                                             uint8_t* lds, const uint32_t t) {
     constexpr uint32_t PL = L < 64u ? L : 64u;
@@ -207,21 +219,23 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
     }
     const uint8_t* in = nullptr;
     uint8_t* out = nullptr;
-    RecKey rk = {};
+    constexpr bool RFC = LAY == RecLayout::kRfc8439;
+    RecKeyRfc rk = {};
     const uint32_t adlen = p.tls ? 13u : p.ad_len;
-    const uint32_t A = Z + ((adlen + 8u + 15u) & ~15u);
-    const uint32_t S = A - adlen - 8u;  // stream start, >= Z
+    // RFC 8439: [Z, A) ad and its zero padding | A: ct (n) | zeros to 16 | le64(adlen) le64(n)
+    const uint32_t A = Z + (RFC ? (adlen + 15u) & ~15u : (adlen + 8u + 15u) & ~15u);
+    const uint32_t S = RFC ? Z : A - adlen - 8u;  // stream start, >= Z
     uint8_t* ct_lds = lds + A;
     if (work) {
         in = p.in + rec_in_off(p, rec);
         out = p.out + rec_out_off(p, rec);
-        rk = record_key(p, rec);
+        rk = record_key_of<LAY>(p, rec);
 
         // ---- phase 1: keystream XOR, 64 bytes per lane-block ----------------
         const bool vec_ok = (((uintptr_t)in | (uintptr_t)out) & 15u) == 0u;
         const uint32_t nblocks = (n + 63u) >> 6;
         ChaChaPre pre;
-        if constexpr (L >= 64u) pre = chacha_pre(rk.k, rk.n14, rk.n15);
+        if constexpr (L >= 64u) pre = chacha_pre(rk.k, rk.n13, rk.n14, rk.n15);
         for (uint32_t b = t; b < nblocks; b += L) {
             const uint32_t off = b << 6;
             if (vec_ok && off + 64u <= n) {
@@ -229,8 +243,8 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
                 const u32x4 d2 = ld16(in + off + 32), d3 = ld16(in + off + 48);
                 uint32_t ks[16];
                 // data uses blocks 1.. (chacha20_poly1305.rs:52)
-                if constexpr (L >= 64u) chacha_block_pre(ks, pre, rk.k, b + 1u, rk.n14, rk.n15);
-                else chacha_block(ks, rk.k, b + 1u, rk.n14, rk.n15);
+                if constexpr (L >= 64u) chacha_block_pre(ks, pre, rk.k, b + 1u, rk.n13, rk.n14, rk.n15);
+                else chacha_block(ks, rk.k, b + 1u, rk.n13, rk.n14, rk.n15);
                 const u32x4 r0 = d0 ^ u32x4{ks[0], ks[1], ks[2], ks[3]};
                 const u32x4 r1 = d1 ^ u32x4{ks[4], ks[5], ks[6], ks[7]};
                 const u32x4 r2 = d2 ^ u32x4{ks[8], ks[9], ks[10], ks[11]};
@@ -253,8 +267,8 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
             } else {
                 // partial last block or misaligned record: byte granular
                 uint32_t ks[16];
-                if constexpr (L >= 64u) chacha_block_pre(ks, pre, rk.k, b + 1u, rk.n14, rk.n15);
-                else chacha_block(ks, rk.k, b + 1u, rk.n14, rk.n15);
+                if constexpr (L >= 64u) chacha_block_pre(ks, pre, rk.k, b + 1u, rk.n13, rk.n14, rk.n15);
+                else chacha_block(ks, rk.k, b + 1u, rk.n13, rk.n14, rk.n15);
 #pragma unroll
                 for (uint32_t w = 0; w < 16; ++w) {
 #pragma unroll
@@ -272,7 +286,23 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
         }
 
         // ---- MAC stream framing: ad || le64(|ad|) || ct || le64(|ct|) --------
-        if (t < PL) {
+        if (RFC && t < PL) {
+            // ad || 0.. (to 16) || ct || 0.. (to 16) || le64(|ad|) || le64(|ct|)  (RFC 8439 section 2.8)
+            for (uint32_t i = t; i < A - Z; i += PL) {
+                uint8_t v = 0u;
+                if (i < adlen)
+                    v = p.tls ? tls_ad_byte(rk.seq, p.tls_hdr, n, i) : p.ads[(uint64_t)p.ad_stride * rec + i];
+                lds[S + i] = v;
+            }
+            const uint32_t zp = (0u - n) & 15u;  // zeros to the end of the last ciphertext block
+            for (uint32_t i = t; i < zp + 16u; i += PL) {
+                const uint32_t e = i - zp;  // byte of the length block
+                uint8_t v = 0u;
+                if (i >= zp) v = e < 8u ? (uint8_t)((uint64_t)adlen >> (8u * e)) : (uint8_t)((uint64_t)n >> (8u * (e - 8u)));
+                ct_lds[n + i] = v;
+            }
+        }
+        if (!RFC && t < PL) {
             for (uint32_t i = t; i < adlen + 8u; i += PL) {
                 uint8_t v;
                 if (i < adlen)
@@ -289,7 +319,7 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
     if (!work || t >= PL) return;
 
     // ---- phase 2: Poly1305 on PL lanes -----------------------------------------
-    const MacGeom g = mac_geom(adlen, n, PL);
+    const MacGeom g = mac_geom<LAY>(adlen, n, PL);
     const uint32_t* kr = p.ws + (uint64_t)rec * kKeyRecWords;
     uint32_t r0 = kr[kR32Off + 0], r1 = kr[kR32Off + 1], r2 = kr[kR32Off + 2], r3 = kr[kR32Off + 3];
     if constexpr (PL == 64u) {  // one record per wave: keep the key in SGPRs
@@ -315,7 +345,7 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
 
     // lane t: virtual blocks [t*k, t*k + k); virtual block v is real iff v >= z
     const uint32_t v0 = t * g.k;
-    const uint32_t rem = g.L - 16u * (g.B - 1u);  // bytes in the final block, 1..16
+    const uint32_t rem = g.L - 16u * (g.B - 1u);  // bytes in the final block, 1..16 (RFC 8439: always 16)
     H32 h = {0u, 0u, 0u, 0u, 0u};
     // Every block is stepped with the 2^128 pad bit; the virtual blocks (the
     // first z of the record, all in lanes t <= tp = z / k) are then discarded
@@ -449,13 +479,13 @@ __device__ __forceinline__ uint32_t group_of_thread() {
 }
 
 // Direct launch: workgroup w serves records w*RPW .. w*RPW + RPW - 1.
-template <bool OPEN, uint32_t L>
+template <bool OPEN, uint32_t L, RecLayout LAY>
 __global__ __launch_bounds__(256) void sg_aead_kernel(const KParams p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     constexpr uint32_t RPW = 256u / L;
     const uint32_t g = group_of_thread<L>(), t = threadIdx.x % L;
     const uint32_t rec = blockIdx.x * RPW + g;
-    aead_record<OPEN, L>(p, rec, rec < p.count, lds + g * p.lds_rec_bytes, t);
+    aead_record<OPEN, L, LAY>(p, rec, rec < p.count, lds + g * p.lds_rec_bytes, t);
 }
 
 // Bucketed launch: records listed by sg_classify_kernel for this size class.
@@ -465,7 +495,7 @@ __global__ __launch_bounds__(256) void sg_aead_kernel(const KParams p) {
 // MAC).  PERSIST = true (stream capture, where the host cannot wait): a fixed
 // grid walks the list; the barrier closing each iteration makes waves 1-3
 // wait for wave 0's MAC, ~30 % slower per byte (tools/exp_list.py).
-template <bool OPEN, uint32_t L, bool PERSIST>
+template <bool OPEN, uint32_t L, bool PERSIST, RecLayout LAY>
 __global__ __launch_bounds__(256) void sg_aead_list_kernel(const KParams p, const uint32_t* __restrict__ list,
                                                            const uint32_t* __restrict__ list_count) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -483,7 +513,7 @@ __global__ __launch_bounds__(256) void sg_aead_list_kernel(const KParams p, cons
         const bool active = slot < cnt;
         uint32_t rec = active ? list[slot] : 0u;
         if constexpr (L >= 64u) rec = __builtin_amdgcn_readfirstlane(rec);
-        aead_record<OPEN, L>(p, rec, active, lds + g * p.lds_rec_bytes, t);
+        aead_record<OPEN, L, LAY>(p, rec, active, lds + g * p.lds_rec_bytes, t);
         if constexpr (!PERSIST) break;
         __syncthreads();  // LDS is reused by the next iteration
     }
@@ -556,10 +586,10 @@ __global__ __launch_bounds__(1024) void sg_classify_kernel(const KParams p, uint
 
 hipError_t launch_keying(const KParams& p, bool open, const KeyJobs& jobs, uint32_t grid, hipStream_t s) {
     if (grid == 0) return hipSuccess;
-    if (open)
-        hipLaunchKernelGGL((sg_keying_kernel<true>), dim3(grid), dim3(kKeyingThreads), 0, s, p, jobs);
-    else
-        hipLaunchKernelGGL((sg_keying_kernel<false>), dim3(grid), dim3(kKeyingThreads), 0, s, p, jobs);
+    constexpr RecLayout D = RecLayout::kDraft, R = RecLayout::kRfc8439;
+    const auto kernel = p.rfc ? (open ? sg_keying_kernel<true, R> : sg_keying_kernel<false, R>)
+                              : (open ? sg_keying_kernel<true, D> : sg_keying_kernel<false, D>);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kKeyingThreads), 0, s, p, jobs);
     return hipGetLastError();
 }
 
@@ -584,7 +614,9 @@ template <uint32_t L>
 static hipError_t launch_direct(const KParams& p, bool open, hipStream_t s) {
     constexpr uint32_t RPW = 256u / L;
     const uint32_t grid = (p.count + RPW - 1u) / RPW;
-    const auto kernel = open ? sg_aead_kernel<true, L> : sg_aead_kernel<false, L>;
+    constexpr RecLayout D = RecLayout::kDraft, R = RecLayout::kRfc8439;
+    const auto kernel = p.rfc ? (open ? sg_aead_kernel<true, L, R> : sg_aead_kernel<false, L, R>)
+                              : (open ? sg_aead_kernel<true, L, D> : sg_aead_kernel<false, L, D>);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), RPW * p.lds_rec_bytes, s, p);
     return hipGetLastError();
 }
@@ -596,16 +628,21 @@ static hipError_t launch_list(const KParams& p, bool open, const uint32_t* list,
                               hipStream_t s) {
     constexpr uint32_t RPW = 256u / L;
     const size_t lds = RPW * p.lds_rec_bytes;
+    constexpr RecLayout D = RecLayout::kDraft, R = RecLayout::kRfc8439;
     if (n_exact != 0xffffffffu) {
         if (n_exact == 0) return hipSuccess;
-        const auto kernel = open ? sg_aead_list_kernel<true, L, false> : sg_aead_list_kernel<false, L, false>;
+        const auto kernel =
+            p.rfc ? (open ? sg_aead_list_kernel<true, L, false, R> : sg_aead_list_kernel<false, L, false, R>)
+                  : (open ? sg_aead_list_kernel<true, L, false, D> : sg_aead_list_kernel<false, L, false, D>);
         hipLaunchKernelGGL(kernel, dim3((n_exact + RPW - 1u) / RPW), dim3(kThreads), lds, s, p, list, cnt);
         return hipGetLastError();
     }
     uint32_t grid = (p.count + RPW - 1u) / RPW;
     const uint32_t cap = kListGridPerCU * 256u;
     if (grid > cap) grid = cap;
-    const auto kernel = open ? sg_aead_list_kernel<true, L, true> : sg_aead_list_kernel<false, L, true>;
+    const auto kernel =
+        p.rfc ? (open ? sg_aead_list_kernel<true, L, true, R> : sg_aead_list_kernel<false, L, true, R>)
+              : (open ? sg_aead_list_kernel<true, L, true, D> : sg_aead_list_kernel<false, L, true, D>);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, s, p, list, cnt);
     return hipGetLastError();
 }

@@ -148,8 +148,10 @@ struct Prf {
 namespace {
 constexpr size_t kMaxHmacKey = 64;
 
+// cwiv / swiv (both or neither): the 12-byte write IVs that follow the keys in
+// the key block (RFC 5246 section 6.3 with no MAC keys, RFC 7905 section 2)
 void derive_one(const uint8_t* pm, size_t pm_len, const uint8_t* cr, const uint8_t* sr, uint8_t* ms_out,
-                uint8_t* cwk, uint8_t* swk) {
+                uint8_t* cwk, uint8_t* swk, uint8_t* cwiv = nullptr, uint8_t* swiv = nullptr) {
     // client.rs:130-137: master_secret = PRF(pre_master, "master secret" || client_random || server_random)[..48]
     uint8_t seed[13 + 64];
     std::memcpy(seed, "master secret", 13);
@@ -165,6 +167,10 @@ void derive_one(const uint8_t* pm, size_t pm_len, const uint8_t* cr, const uint8
     Prf kb(ms, 48, seed, 77);
     kb.get_bytes(cwk, SG_KEY_LEN);
     kb.get_bytes(swk, SG_KEY_LEN);
+    if (cwiv) {
+        kb.get_bytes(cwiv, 12);
+        kb.get_bytes(swiv, 12);
+    }
     if (ms_out) std::memcpy(ms_out, ms, 48);
 }
 }  // namespace
@@ -203,9 +209,10 @@ int sg_prf_get_bytes(sg_prf* prf, uint8_t* out, size_t n) {
 
 void sg_prf_free(sg_prf* prf) { delete reinterpret_cast<sg::Prf*>(prf); }
 
-int sg_derive_keys(uint32_t count, const uint8_t* pre_master, size_t pm_len, size_t pm_stride,
-                   const uint8_t* client_random, const uint8_t* server_random, uint8_t* master_secret,
-                   uint8_t* client_write_keys, uint8_t* server_write_keys, int threads) {
+static int derive_keys(uint32_t count, const uint8_t* pre_master, size_t pm_len, size_t pm_stride,
+                       const uint8_t* client_random, const uint8_t* server_random, uint8_t* master_secret,
+                       uint8_t* client_write_keys, uint8_t* server_write_keys, uint8_t* client_write_ivs,
+                       uint8_t* server_write_ivs, int threads) {
     if (!count) return SG_OK;
     if (!pre_master || !client_random || !server_random || !client_write_keys || !server_write_keys)
         return fail(SG_E_ARG, "NULL argument%s");
@@ -215,7 +222,9 @@ int sg_derive_keys(uint32_t count, const uint8_t* pre_master, size_t pm_len, siz
         for (uint32_t i = t; i < count; i += nt)
             sg::derive_one(pre_master + (size_t)pm_stride * i, pm_len, client_random + 32ull * i,
                            server_random + 32ull * i, master_secret ? master_secret + 48ull * i : nullptr,
-                           client_write_keys + 32ull * i, server_write_keys + 32ull * i);
+                           client_write_keys + 32ull * i, server_write_keys + 32ull * i,
+                           client_write_ivs ? client_write_ivs + 12ull * i : nullptr,
+                           client_write_ivs ? server_write_ivs + 12ull * i : nullptr);
     };
     if (nt == 1) {
         work(0);
@@ -225,6 +234,22 @@ int sg_derive_keys(uint32_t count, const uint8_t* pre_master, size_t pm_len, siz
         for (auto& th : pool) th.join();
     }
     return SG_OK;
+}
+
+int sg_derive_keys(uint32_t count, const uint8_t* pre_master, size_t pm_len, size_t pm_stride,
+                   const uint8_t* client_random, const uint8_t* server_random, uint8_t* master_secret,
+                   uint8_t* client_write_keys, uint8_t* server_write_keys, int threads) {
+    return derive_keys(count, pre_master, pm_len, pm_stride, client_random, server_random, master_secret,
+                       client_write_keys, server_write_keys, nullptr, nullptr, threads);
+}
+
+int sg_derive_keys_ivs(uint32_t count, const uint8_t* pre_master, size_t pm_len, size_t pm_stride,
+                       const uint8_t* client_random, const uint8_t* server_random, uint8_t* master_secret,
+                       uint8_t* client_write_keys, uint8_t* server_write_keys, uint8_t* client_write_ivs,
+                       uint8_t* server_write_ivs, int threads) {
+    if (count && (!client_write_ivs || !server_write_ivs)) return fail(SG_E_ARG, "NULL argument%s");
+    return derive_keys(count, pre_master, pm_len, pm_stride, client_random, server_random, master_secret,
+                       client_write_keys, server_write_keys, client_write_ivs, server_write_ivs, threads);
 }
 
 int sg_finished_verify_data(const uint8_t master_secret[48], int server, const uint8_t handshake_hash[32],

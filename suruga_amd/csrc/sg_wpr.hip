@@ -50,6 +50,17 @@
 // is exact arithmetic mod p, so tags equal the reference's bit for bit
 // (tests/test_wpr_mac_model.py pins this decomposition against the CPU
 // restatement of poly1305.rs).
+//
+// RecLayout::kRfc8439 (the uniform launch only; sg_*_batch_rfc8439): in the RFC
+// 8439 stream ad || 0.. || ct || 0.. || le64(|ad|) || le64(n) the ciphertext
+// starts on a block boundary, which is the sigma = 0 case above for every AD
+// length, so the MFMA body is the draft's.  The keying kernel's constant term
+// changes (wpr_geom: o = 16 ceil(|ad| / 16), B = beta + m + 1, rem = 16,
+// delta = 0; the prefix is ad and its zero padding, the suffix the one full
+// length block at weight r), block 0 and the rounds take the nonce's first word
+// in state word 13 (u[13] on the SALU, x[13] + n13 in the feed-forward), and
+// the TLS nonce is the key's write IV XOR the byte-swapped sequence number (RFC
+// 7905), on the SALU.  tests/test_wpr_mac_model_rfc8439.py pins the constant term.
 #include "sg_internal.h"
 #include "sg_device.h"
 #include "sg_chacha_grp.inc"  // grouped ChaCha20 double round (tools/gen_chacha_grp.py --product)
@@ -91,8 +102,22 @@ constexpr uint32_t kWprKeyThreads = 64;
 struct WprGeom {
     uint32_t o, sigma, beta, B, rem, delta, m;
 };
+// RFC 8439 (ad || 0.. || ct || 0.. || le64(|ad|) || le64(n)): the ciphertext
+// starts on a block boundary, o = 16 ceil(adlen / 16), sigma = 0, and one full
+// block closes the stream: B = beta + m + 1, rem = 16, delta = 0.
+template <RecLayout LAY>
 __device__ __forceinline__ WprGeom wpr_geom(uint32_t adlen, uint32_t n) {
     WprGeom g;
+    if constexpr (LAY == RecLayout::kRfc8439) {
+        g.o = (adlen + 15u) & ~15u;
+        g.sigma = 0u;
+        g.beta = g.o >> 4;
+        g.m = n >> 4;
+        g.B = g.beta + g.m + 1u;
+        g.rem = 16u;
+        g.delta = 0u;
+        return g;
+    }
     g.o = adlen + 8u;
     g.sigma = g.o & 15u;
     g.beta = g.o >> 4;
@@ -157,9 +182,11 @@ struct WprKeyJobs {
 };
 
 // (compiled for two waves per SIMD: four and more spill to scratch)
-template <bool OPEN, bool LIST>
+template <bool OPEN, bool LIST, RecLayout LAY>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg_wpr_keying_kernel(
     const KParams p, const WprKeyJobs jobs) {
+    constexpr bool RFC = LAY == RecLayout::kRfc8439;
+    static_assert(!(RFC && LIST), "the buckets are draft only");
     const uint32_t lane = threadIdx.x;
     WprList wl = jobs.b[0];
     uint32_t b0 = 0;
@@ -182,15 +209,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
     const uint32_t rec = LIST ? (act ? wl.list[slot] : 0u) : slot;
     uint32_t n = kWprN;
     if constexpr (LIST) n = act ? p.len[rec] - (OPEN ? 16u : 0u) : kWprN;
-    const WprGeom G = wpr_geom(adlen, n);
+    const WprGeom G = wpr_geom<LAY>(adlen, n);
 
     F26 r = f26_zero();
     uint32_t s[4] = {0u, 0u, 0u, 0u};
-    RecKey rk = {};
+    RecKeyRfc rk = {};
     if (act) {
-        rk = record_key(p, rec);
+        rk = record_key_of<LAY>(p, rec);
         uint32_t ks[16];
-        chacha_block(ks, rk.k, 0u, rk.n14, rk.n15);  // block 0 -> poly key (chacha20_poly1305.rs:50,75)
+        chacha_block(ks, rk.k, 0u, rk.n13, rk.n14, rk.n15);  // block 0 -> poly key (chacha20_poly1305.rs:50,75)
         const PolyKey pk = poly_key(ks);
         r = words_to_f26(pk.r0, pk.r1, pk.r2, pk.r3, 0u);
         s[0] = pk.s[0]; s[1] = pk.s[1]; s[2] = pk.s[2]; s[3] = pk.s[3];
@@ -317,15 +344,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
             uint32_t w[4] = {0u, 0u, 0u, 0u};
             for (uint32_t i = 0; i < 16u; ++i) {
                 const uint32_t pos = 16u * b + i;
-                if (pos < G.o) w[i >> 2] |= (uint32_t)prefix_byte(p, rec, rk.seq, n, adlen, pos) << (8u * (i & 3u));
+                if constexpr (RFC) {  // ad and its zero padding (block beta is empty: sigma = 0)
+                    if (pos < G.o) w[i >> 2] |= (uint32_t)prefix_byte_rfc(p, rec, rk.seq, n, adlen, pos) << (8u * (i & 3u));
+                } else {
+                    if (pos < G.o) w[i >> 2] |= (uint32_t)prefix_byte(p, rec, rk.seq, n, adlen, pos) << (8u * (i & 3u));
+                }
             }
             hp = fmul_add(hp, r, words_to_f26(w[0], w[1], w[2], w[3], 0u));
         }
     }
     const F26 prefix = fmul(fmul(hp, rm), rd0);
     // suffix le64(n) at stream offset o + n = 16 (beta + m) + sigma: n 2^(8 sigma) split at 2^128
+    // (RFC 8439: the single full block le64(adlen) || le64(n), the stream's last, at weight r)
     F26 suffix;
-    {
+    if constexpr (RFC) {
+        suffix = fmul(words_to_f26(adlen, 0u, n, 0u, 0u), r);
+    } else {
         const uint32_t wi = G.sigma >> 2, bs = 8u * (G.sigma & 3u);
         const uint64_t v = (uint64_t)n << bs;
         uint32_t w[5] = {0u, 0u, 0u, 0u, 0u};
@@ -477,12 +511,15 @@ struct RecDesc {
     uint32_t n;         // plaintext length
     uint32_t rec;       // record index (status, key index, sequence number)
     uint32_t ki, n14, n15;
+    uint32_t n13;       // RFC 8439 only (the draft's word 13 is 0)
 };
 
-template <bool OPEN, bool TLS, uint32_t J, bool LIST>
+template <bool OPEN, bool TLS, uint32_t J, bool LIST, RecLayout LAY>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void sg_wpr_kernel(const KParams p,
                                                                                                const WprList wl) {
     static_assert(J >= 1u && J <= 4u && (LIST || J == 4u), "uniform launches are full 16 KiB records");
+    constexpr bool RFC = LAY == RecLayout::kRfc8439;
+    static_assert(!(RFC && LIST), "the buckets are draft only");
     constexpr uint32_t j0 = 4u - J;  // the first chunk of the right-aligned record in the 16 KiB frame
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const uint32_t wave = uniform(threadIdx.x >> 6), lane = threadIdx.x & 63u;
@@ -494,7 +531,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const uint32_t lds_rxs = uniform(lds_lines + kWprRxOff);
     const uint32_t hh = lane >> 5, q = lane & 31u;
     const uint32_t adlen = TLS ? 13u : p.ad_len;
-    const uint32_t sigma = (adlen + 8u) & 15u;
+    const uint32_t sigma = RFC ? 0u : (adlen + 8u) & 15u;  // RFC 8439: the ciphertext starts a block
     // T fragment byte a' comes from the V window for a' < 16 - sigma, else from P
     const uint32_t nv = 16u - sigma;
     const u32x4 vmask = {~bytes_from(0u, nv), ~bytes_from(1u, nv), ~bytes_from(2u, nv), ~bytes_from(3u, nv)};
@@ -530,6 +567,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     // bucket launches from the descriptor the keying kernel wrote.
     auto desc_of_slot = [&](uint32_t slot) {
         RecDesc d;
+        d.n13 = 0u;
         if constexpr (LIST) {
             const uint32_t* dw = wl.desc + (uint64_t)slot * kWprDescWords;
             d.io = (uint64_t)cload(dw, 0) | ((uint64_t)cload(dw, 1) << 32);
@@ -547,7 +585,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             d.ki = p.key_index ? cload(p.key_index, slot) : 0u;
             d.ki = d.ki < p.num_keys ? d.ki : p.num_keys - 1u;  // (record_key's clamp)
             // nonce (chacha20.rs:25-51; TLS: be64(seq), tls.rs:103)
-            if constexpr (TLS) {
+            if constexpr (RFC && TLS) {  // RFC 7905: the key's write IV XOR (0^32 || be64(seq)), on the SALU
+                uint64_t seq = p.seq0 + slot;
+                if (p.seq) seq = (uint64_t)cload(p.seq, 2ull * slot) | ((uint64_t)cload(p.seq, 2ull * slot + 1u) << 32);
+                d.n13 = cload(p.ivs, 3ull * d.ki);
+                d.n14 = cload(p.ivs, 3ull * d.ki + 1u) ^ sbswap32((uint32_t)(seq >> 32));
+                d.n15 = cload(p.ivs, 3ull * d.ki + 2u) ^ sbswap32((uint32_t)seq);
+            } else if constexpr (RFC) {  // explicit 12-byte nonces
+                d.n13 = cload(p.nonces, 3ull * slot);
+                d.n14 = cload(p.nonces, 3ull * slot + 1u);
+                d.n15 = cload(p.nonces, 3ull * slot + 2u);
+            } else if constexpr (TLS) {
                 uint64_t seq = p.seq0 + slot;
                 if (p.seq) seq = (uint64_t)cload(p.seq, 2ull * slot) | ((uint64_t)cload(p.seq, 2ull * slot + 1u) << 32);
                 d.n14 = sbswap32((uint32_t)(seq >> 32));  // (on the SALU: the chain below stays scalar)
@@ -563,6 +611,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     auto desc_from_lds = [&]() {
         const uint32_t* dl = reinterpret_cast<const uint32_t*>(lines + kWprDescOff);
         RecDesc d;
+        d.n13 = 0u;
         d.io = (uint64_t)uniform(dl[0]) | ((uint64_t)uniform(dl[1]) << 32);
         d.oo = (uint64_t)uniform(dl[2]) | ((uint64_t)uniform(dl[3]) << 32);
         d.n = uniform(dl[4]);
@@ -661,11 +710,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
         for (uint32_t i = 0; i < 8u; ++i) kw[i] = cload(p.keys, 8ull * cd.ki + i);
         const uint32_t n14 = cd.n14, n15 = cd.n15;
+        const uint32_t n13 = RFC ? cd.n13 : 0u;  // RFC 8439 section 2.3: the nonce's first word
         // The column quarter rounds 1-3 of the first double round see no block
         // counter (word 13 is 0, chacha20.rs:114-121): the same for every lane
         // and chunk of the record, so they run once per record on the SALU.
         uint32_t u[16] = {kSigma0, kSigma1, kSigma2, kSigma3, kw[0], kw[1], kw[2], kw[3],
-                          kw[4],   kw[5],   kw[6],   kw[7],   0u,    0u,    n14,   n15};
+                          kw[4],   kw[5],   kw[6],   kw[7],   0u,    n13,   n14,   n15};
         SG_QR_S(u[1], u[5], u[9], u[13]) SG_QR_S(u[2], u[6], u[10], u[14]) SG_QR_S(u[3], u[7], u[11], u[15])
         // and the steps of the double round whose operands are all uniform
         // (tools/gen_chacha_grp.py, SG_CHACHA_DR1S_*; tests/test_chacha_asm_model.py)
@@ -728,7 +778,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             d[4] = ((uint32_t)(t >> 32) + 0x80u + c) ^ 0x80u;
             uint8_t* ln = lines + kWprLineBytes * lane;
             const u32x4 z = zero4();
-            if constexpr (TLS) {
+            if constexpr (RFC) {
+                // sigma = 0: line byte b = digit 47 - b (b = 31..47), the byte-reversed
+                // digit words R[k] = bswap(d[4 - k]) laid from byte 28 on
+                uint32_t R[5];
+#pragma unroll
+                for (int k = 0; k < 5; ++k) R[k] = __builtin_bswap32(d[4 - k]);
+                st16(ln, z);
+                st16(ln + 16, u32x4{0u, 0u, 0u, R[0]});
+                st16(ln + 32, u32x4{R[1], R[2], R[3], R[4]});
+            } else if constexpr (TLS) {
                 // sigma = 5: line byte b = digit 42 - b (b = 26..42), i.e. the
                 // byte-reversed digit words R[k] = bswap(d[4 - k]) (digits 19 - 4k
                 // .. 16 - 4k, 17..19 zero) laid from byte 23 on: three 16-byte
@@ -777,7 +836,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             const uint32_t off = 480u * ((3u - jj) & 1u) + 48u * (4u - i);
             const lu32p pb = (jj >= 2u ? mac_lo : mac_hi) + off / 4u;
             const lu32p vb = pb + 16;
-            if constexpr (TLS) {
+            if constexpr (RFC) {  // sigma = 0: every byte from the V window
+#pragma unroll
+                for (int t = 0; t < 5; ++t) R.v[t] = vb[t];
+            } else if constexpr (TLS) {
 #pragma unroll
                 for (int t = 0; t < 4; ++t) R.v[t] = vb[t];
 #pragma unroll
@@ -792,7 +854,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         };
         auto mac_frag = [&](const MacRaw& R) -> u32x4 {
             u32x4 f;
-            if constexpr (TLS) {  // bytes 0-10 from V, 11-15 from P
+            if constexpr (RFC) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) f[t] = __builtin_amdgcn_alignbyte(R.v[t + 1], R.v[t], mac_shift);
+            } else if constexpr (TLS) {  // bytes 0-10 from V, 11-15 from P
                 f[0] = __builtin_amdgcn_alignbyte(R.v[1], R.v[0], mac_shift);
                 f[1] = __builtin_amdgcn_alignbyte(R.v[2], R.v[1], mac_shift);
                 const uint32_t v2 = __builtin_amdgcn_alignbyte(R.v[3], R.v[2], mac_shift);
@@ -1017,7 +1082,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             O[0] = D[0] ^ u32x4{x[0] + kSigma0, x[1] + kSigma1, x[2] + kSigma2, x[3] + kSigma3};
             O[1] = D[1] ^ u32x4{x[4] + kw[0], x[5] + kw[1], x[6] + kw[2], x[7] + kw[3]};
             O[2] = D[2] ^ u32x4{x[8] + kw[4], x[9] + kw[5], x[10] + kw[6], x[11] + kw[7]};
-            O[3] = D[3] ^ u32x4{x[12] + bctr, x[13], x[14] + n14, x[15] + n15};
+            if constexpr (RFC) O[3] = D[3] ^ u32x4{x[12] + bctr, x[13] + n13, x[14] + n14, x[15] + n15};
+            else O[3] = D[3] ^ u32x4{x[12] + bctr, x[13], x[14] + n14, x[15] + n15};
             // the MAC reads the ciphertext: received (open) or just produced (seal);
             // the lanes of the frame before the record contribute nothing (i8 0)
 #pragma unroll
@@ -1167,17 +1233,21 @@ hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_
     jobs.b[0] = wl;
     jobs.njobs = 1;
     const uint32_t kgrid = (p.count + kWprKeyThreads - 1u) / kWprKeyThreads;
-    if (open)
-        hipLaunchKernelGGL((sg_wpr_keying_kernel<true, false>), dim3(kgrid), dim3(kWprKeyThreads), 0, s, p, jobs);
-    else
-        hipLaunchKernelGGL((sg_wpr_keying_kernel<false, false>), dim3(kgrid), dim3(kWprKeyThreads), 0, s, p, jobs);
+    constexpr RecLayout D = RecLayout::kDraft, R = RecLayout::kRfc8439;
+    const auto keying = p.rfc ? (open ? sg_wpr_keying_kernel<true, false, R> : sg_wpr_keying_kernel<false, false, R>)
+                              : (open ? sg_wpr_keying_kernel<true, false, D> : sg_wpr_keying_kernel<false, false, D>);
+    hipLaunchKernelGGL(keying, dim3(kgrid), dim3(kWprKeyThreads), 0, s, p, jobs);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if ((e = mark(ev_keyed, s)) != hipSuccess || (e = mark(ev_start, s)) != hipSuccess) return e;
     int cus = 0;
     if ((e = device_cus(&cus)) != hipSuccess) return e;
     const uint32_t grid = wpr_grid(cus, p.count);
-#define SG_WPR_LAUNCH(O, T) hipLaunchKernelGGL((sg_wpr_kernel<O, T, 4, false>), dim3(grid), dim3(512), kWprWgLds, s, p, wl)
+#define SG_WPR_LAUNCH(O, T)                                                                                          \
+    do {                                                                                                            \
+        if (p.rfc) hipLaunchKernelGGL((sg_wpr_kernel<O, T, 4, false, R>), dim3(grid), dim3(512), kWprWgLds, s, p, wl); \
+        else hipLaunchKernelGGL((sg_wpr_kernel<O, T, 4, false, D>), dim3(grid), dim3(512), kWprWgLds, s, p, wl);    \
+    } while (0)
     if (open) {
         if (p.tls) SG_WPR_LAUNCH(true, true); else SG_WPR_LAUNCH(true, false);
     } else {
@@ -1188,7 +1258,7 @@ hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_
 }
 
 hipError_t launch_wpr_keying_lists(const KParams& p, bool open, const WprList* wl, hipStream_t s) {
-    if (!p.tls) return hipErrorInvalidValue;  // buckets are TLS records
+    if (!p.tls || p.rfc) return hipErrorInvalidValue;  // buckets are TLS records of the draft
     WprKeyJobs jobs = {};
     uint32_t grid = 0;
     for (uint32_t b = 0; b < kWprBuckets; ++b) {
@@ -1200,20 +1270,20 @@ hipError_t launch_wpr_keying_lists(const KParams& p, bool open, const WprList* w
     }
     if (grid == 0) return hipSuccess;
     if (open)
-        hipLaunchKernelGGL((sg_wpr_keying_kernel<true, true>), dim3(grid), dim3(kWprKeyThreads), 0, s, p, jobs);
+        hipLaunchKernelGGL((sg_wpr_keying_kernel<true, true, RecLayout::kDraft>), dim3(grid), dim3(kWprKeyThreads), 0, s, p, jobs);
     else
-        hipLaunchKernelGGL((sg_wpr_keying_kernel<false, true>), dim3(grid), dim3(kWprKeyThreads), 0, s, p, jobs);
+        hipLaunchKernelGGL((sg_wpr_keying_kernel<false, true, RecLayout::kDraft>), dim3(grid), dim3(kWprKeyThreads), 0, s, p, jobs);
     return hipGetLastError();
 }
 
 hipError_t launch_wpr_list(const KParams& p, bool open, uint32_t J, const WprList& wl, hipStream_t s) {
     if (wl.count == 0) return hipSuccess;
-    if (!p.tls || J < kWprMinJ || J > 4u) return hipErrorInvalidValue;  // buckets are TLS records of 2..4 chunks
+    if (!p.tls || p.rfc || J < kWprMinJ || J > 4u) return hipErrorInvalidValue;  // buckets are TLS records of 2..4 chunks
     hipError_t e;
     int cus = 0;
     if ((e = device_cus(&cus)) != hipSuccess) return e;
     const uint32_t grid = wpr_grid(cus, wl.count);
-#define SG_WPR_LAUNCH(O, JJ) hipLaunchKernelGGL((sg_wpr_kernel<O, true, JJ, true>), dim3(grid), dim3(512), kWprWgLds, s, p, wl)
+#define SG_WPR_LAUNCH(O, JJ) hipLaunchKernelGGL((sg_wpr_kernel<O, true, JJ, true, RecLayout::kDraft>), dim3(grid), dim3(512), kWprWgLds, s, p, wl)
     switch (J) {
         case 2: if (open) SG_WPR_LAUNCH(true, 2); else SG_WPR_LAUNCH(false, 2); break;
         case 3: if (open) SG_WPR_LAUNCH(true, 3); else SG_WPR_LAUNCH(false, 3); break;

@@ -65,6 +65,28 @@ def derive_keys(pre_master, client_random, server_random, threads: int = 8, with
     return (cw, sw, ms) if with_master else (cw, sw)
 
 
+def derive_keys_ivs(pre_master, client_random, server_random, threads: int = 8, with_master: bool = False):
+    """derive_keys with the write IVs of RFC 7905 (sg_derive_keys_ivs): returns
+    (client_write_keys, server_write_keys, client_write_ivs, server_write_ivs[, master_secrets]),
+    the IVs as uint8 [count, 12] -- the 88-byte key block of RFC 5246 section 6.3
+    with no MAC keys; the keys are derive_keys' bytes."""
+    pm = np.ascontiguousarray(pre_master, dtype=np.uint8)
+    cr = np.ascontiguousarray(client_random, dtype=np.uint8)
+    sr = np.ascontiguousarray(server_random, dtype=np.uint8)
+    count = pm.shape[0]
+    if cr.shape != (count, 32) or sr.shape != (count, 32):
+        raise ValueError("randoms must be [count, 32]")
+    cw = np.empty((count, 32), dtype=np.uint8)
+    sw = np.empty((count, 32), dtype=np.uint8)
+    ci = np.empty((count, 12), dtype=np.uint8)
+    si = np.empty((count, 12), dtype=np.uint8)
+    ms = np.empty((count, 48), dtype=np.uint8) if with_master else None
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+    N.check(N.load().sg_derive_keys_ivs(count, p(pm), pm.shape[1], pm.shape[1], p(cr), p(sr), p(ms), p(cw), p(sw),
+                                        p(ci), p(si), threads))
+    return (cw, sw, ci, si, ms) if with_master else (cw, sw, ci, si)
+
+
 def verify_data(master_secret: bytes, server: bool, handshake_hash: bytes) -> bytes:  # client.rs:184-221
     out = (C.c_uint8 * 12)()
     N.check(N.load().sg_finished_verify_data(master_secret, int(server), handshake_hash, out))

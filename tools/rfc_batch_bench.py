@@ -1,0 +1,226 @@
+#!/usr/bin/env python3
+"""Rate of the RFC 8439 record batch (sg_seal_batch_rfc8439 / sg_open_batch_rfc8439)
+beside the draft calls on the same records.  Prints one JSON line.
+
+Two batches, both device-resident TLS records:
+
+* ``uniform``: ``--records`` (default 2^18) records of 16 KiB, one key, sequential
+  seq -- the wave-per-record kernel in both constructions;
+* ``mixed``: ``--mixed-records`` records of the C2 Zipf layout (64 B-16 KiB, 256
+  connection keys, suruga_amd.workloads.c2_layout) -- the draft runs it on the
+  packed kernel, the buckets and the size classes, RFC 8439 on the size classes
+  alone, so ``rfc_vs_draft_*`` here prices that route.
+
+The draft and RFC legs alternate launch by launch in one process (draft seal, RFC
+seal, draft open, RFC open per round), so they share the clock the board holds.
+Each leg reports the median of ``--reps`` launches after ``--warmup`` from HIP
+events, GiB/s of payload, and ``spread`` = (max - min) / median.
+``rfc_vs_draft_*`` is RFC time over draft time.  ``timing`` splits each
+construction's launches into keying pre-pass and record kernel
+(sg_timing_read), from a separate short pass.  A sample of sealed records of each
+batch is compared with tests/rfc8439_ref.py, every byte and the tag.
+
+    python tools/rfc_batch_bench.py [--records 262144] [--mixed-records 262144] [--reps 25]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import struct
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+
+REC = 16384
+SEED = 0x7266635F
+SAMPLE = 24
+
+
+def summary(ms: list, payload: int) -> dict:
+    med = statistics.median(ms)
+    return {"ms": round(med, 5), "min_ms": round(min(ms), 5), "max_ms": round(max(ms), 5),
+            "spread": round((max(ms) - min(ms)) / med, 4), "gib_s": round(payload / 2**30 / (med * 1e-3), 1),
+            "launches": len(ms)}
+
+
+def tls_nonce(iv: bytes, seq: int) -> bytes:
+    return bytes(a ^ b for a, b in zip(iv, bytes(4) + struct.pack(">Q", seq)))
+
+
+def make_uniform(count: int):
+    import torch
+
+    from suruga_amd import batch as B
+
+    key = bytes(range(32))
+    iv = bytes(range(0x80, 0x8C))
+    keys = torch.tensor(list(key), dtype=torch.uint8, device="cuda").view(1, 32)
+    ivs = torch.tensor(list(iv), dtype=torch.uint8, device="cuda").view(1, 12)
+    pt = torch.empty(count * REC, dtype=torch.uint8, device="cuda")
+    B.fill_records(pt, REC, REC, count, SEED)
+    cs = REC + 128  # 128-byte aligned slots, as bench.py's C1
+    back = torch.empty(count * REC, dtype=torch.uint8, device="cuda")
+    ws = torch.empty(B.workspace_size(count), dtype=torch.uint8, device="cuda")
+    legs, cts, sts = {}, {}, {}
+    for name, extra in (("draft", {}), ("rfc", dict(rfc8439=True, ivs=ivs))):
+        ct = torch.empty(count * cs, dtype=torch.uint8, device="cuda")
+        st = torch.zeros(count, dtype=torch.uint8, device="cuda")
+        legs[name] = (B.Batch(count=count, keys=keys, inp=pt, out=ct, uniform_len=REC, in_stride=REC, out_stride=cs,
+                              seq0=7, workspace=ws, **extra),
+                      B.Batch(count=count, keys=keys, inp=ct, out=back, uniform_len=REC + 16, in_stride=cs,
+                              out_stride=REC, seq0=7, status=st, workspace=ws, **extra))
+        cts[name], sts[name] = ct, st
+
+    def record(i):  # (key, nonce, ad, pt, sealed) of record i of the RFC leg
+        seq = 7 + i
+        ad = struct.pack(">QBBBH", seq, 23, 3, 3, REC)
+        return (key, tls_nonce(iv, seq), ad, pt[i * REC:(i + 1) * REC].cpu().numpy().tobytes(),
+                cts["rfc"][i * cs:i * cs + REC + 16].cpu().numpy().tobytes())
+
+    return dict(count=count, payload=count * REC, legs=legs, pt=pt, back=back, sts=sts, record=record,
+                desc=f"{count} x {REC} B TLS records, one key")
+
+
+def make_mixed(count: int):
+    import numpy as np
+    import torch
+
+    from suruga_amd import batch as B
+    from suruga_amd import workloads as W
+
+    lay = W.c2_layout(count)
+    t64 = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).to("cuda")  # noqa: E731
+    t32 = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).to("cuda")  # noqa: E731
+    keys_h = bytes(lay.keys)
+    num_keys = len(keys_h) // 32
+    ivs_h = np.random.default_rng(7905).integers(0, 256, 12 * num_keys, dtype=np.uint8).tobytes()
+    keys = torch.tensor(list(keys_h), dtype=torch.uint8, device="cuda").view(-1, 32)
+    ivs = torch.tensor(list(ivs_h), dtype=torch.uint8, device="cuda").view(-1, 12)
+    pt = torch.empty(lay.pt_bytes, dtype=torch.uint8, device="cuda")
+    B.fill_records(pt, 0, lay.pt_bytes, 1, SEED)
+    back = torch.empty(lay.pt_bytes, dtype=torch.uint8, device="cuda")
+    ws = torch.empty(B.workspace_size(count), dtype=torch.uint8, device="cuda")
+    lens, olens = t32(lay.lens), t32(lay.lens + 16)
+    in_off, out_off, kidx, seqs = t64(lay.in_off), t64(lay.out_off), t32(lay.key_index), t64(lay.seq)
+    maxl = int(lay.lens.max())
+    legs, cts, sts = {}, {}, {}
+    for name, extra in (("draft", {}), ("rfc", dict(rfc8439=True, ivs=ivs))):
+        ct = torch.empty(lay.ct_bytes, dtype=torch.uint8, device="cuda")
+        st = torch.zeros(count, dtype=torch.uint8, device="cuda")
+        legs[name] = (B.Batch(count=count, keys=keys, inp=pt, out=ct, lens=lens, max_len=maxl, in_off=in_off,
+                              out_off=out_off, key_index=kidx, seq=seqs, workspace=ws, **extra),
+                      B.Batch(count=count, keys=keys, inp=ct, out=back, lens=olens, max_len=maxl + 16, in_off=out_off,
+                              out_off=in_off, key_index=kidx, seq=seqs, status=st, workspace=ws, **extra))
+        cts[name], sts[name] = ct, st
+
+    def record(i):
+        n, k, seq = int(lay.lens[i]), int(lay.key_index[i]), int(lay.seq[i])
+        io, oo = int(lay.in_off[i]), int(lay.out_off[i])
+        ad = struct.pack(">QBBBH", seq, 23, 3, 3, n)
+        return (keys_h[32 * k:32 * k + 32], tls_nonce(ivs_h[12 * k:12 * k + 12], seq), ad,
+                pt[io:io + n].cpu().numpy().tobytes(), cts["rfc"][oo:oo + n + 16].cpu().numpy().tobytes())
+
+    return dict(count=count, payload=int(lay.payload), legs=legs, pt=pt, back=back, sts=sts, record=record,
+                desc=f"{count} Zipf(1.1) TLS records 64 B-16 KiB (mean {lay.payload / count:.0f} B), {num_keys} keys")
+
+
+def run(w: dict, reps: int, warmup: int) -> dict:
+    import torch
+
+    from suruga_amd import batch as B
+
+    order = [("draft_seal", lambda: B.seal(w["legs"]["draft"][0])), ("rfc_seal", lambda: B.seal(w["legs"]["rfc"][0])),
+             ("draft_open", lambda: B.open_(w["legs"]["draft"][1])), ("rfc_open", lambda: B.open_(w["legs"]["rfc"][1]))]
+    times = {k: [] for k, _ in order}
+    for rep in range(warmup + reps):
+        for name, fn in order:  # alternating: every leg once per round
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if rep >= warmup:
+                times[name].append(a.elapsed_time(b))
+    torch.cuda.synchronize()
+    for name in ("draft", "rfc"):
+        assert int(w["sts"][name].sum().item()) == 0, f"{name}: open status"
+    assert torch.equal(w["back"], w["pt"]), "round trip"
+    out = {"batch": w["desc"], "payload_bytes": w["payload"]}
+    for name, ms in times.items():
+        out[name] = summary(ms, w["payload"])
+    for d in ("seal", "open"):
+        out[f"rfc_vs_draft_{d}"] = round(out[f"rfc_{d}"]["ms"] / out[f"draft_{d}"]["ms"], 4)
+    # where the time goes: keying pre-pass and record kernel of each construction
+    out["timing"] = {}
+    for name in ("draft", "rfc"):
+        B.set_timing(True)
+        for _ in range(5):
+            B.seal(w["legs"][name][0])
+            B.open_(w["legs"][name][1])
+        torch.cuda.synchronize()
+        t = B.timing_read()
+        B.set_timing(False)
+        out["timing"][name] = {k: round(v, 5) for k, v in t.items() if k.endswith("_ms")}
+    return out
+
+
+def check(w: dict) -> dict:
+    """A sample of the RFC leg's sealed records against tests/rfc8439_ref.py."""
+    import rfc8439_ref as R
+
+    count = w["count"]
+    idx = sorted({0, 1, count // 2, count - 1} | {(i * 2654435761) % count for i in range(SAMPLE)})
+    t0 = time.perf_counter()
+    for i in idx:
+        key, nonce, ad, pt, sealed = w["record"](i)
+        assert sealed == R.seal(key, nonce, pt, ad), f"record {i} differs from the RFC 8439 reference"
+    ossl = R.openssl()
+    if ossl is not None:
+        key, nonce, ad, pt, sealed = w["record"](idx[-1])
+        assert sealed == ossl.seal(key, nonce, pt, ad), "record differs from OpenSSL"
+    return {"records_checked": len(idx), "openssl": ossl.version if ossl else None,
+            "check_s": round(time.perf_counter() - t0, 2)}
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--records", type=int, default=1 << 18, help="uniform 16 KiB batch")
+    ap.add_argument("--mixed-records", type=int, default=1 << 18, help="Zipf batch (0: skip)")
+    ap.add_argument("--reps", type=int, default=25)
+    ap.add_argument("--warmup", type=int, default=3)
+    args = ap.parse_args()
+
+    import torch
+
+    from suruga_amd import _build, _native, devmon
+
+    _build.build_library()
+    assert torch.cuda.is_available(), "rfc_batch_bench needs an MI355X"
+    props = torch.cuda.get_device_properties(0)
+    bus = f"{props.pci_domain_id:04x}:{props.pci_bus_id:02x}:{props.pci_device_id:02x}.0"
+    res = {"tool": "rfc_batch_bench", "device": torch.cuda.get_device_name(0), "lib": _native.loaded_info(),
+           "reps": args.reps, "warmup": args.warmup}
+    w = make_uniform(args.records)
+    sampler = devmon.Sampler(bus, period=0.002).start()  # the clock and power while the uniform legs run
+    t0 = time.perf_counter()
+    res["uniform"] = run(w, args.reps, args.warmup)
+    clk = sampler.stop(t0, time.perf_counter())
+    res["clock"] = {"sclk_mhz": clk["sclk_mhz"], "board_power_w": clk["board_power_w"],
+                    "power_cap_w": clk.get("power_cap_w")}
+    res["uniform"]["check"] = check(w)
+    del w
+    torch.cuda.empty_cache()
+    if args.mixed_records:
+        w = make_mixed(args.mixed_records)
+        res["mixed"] = run(w, args.reps, args.warmup)
+        res["mixed"]["check"] = check(w)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
