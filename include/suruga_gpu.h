@@ -220,9 +220,10 @@ int sg_open_batch(const sg_batch* b);
  *     the AD is the 13 bytes be64(seq) || type || major || minor || be16(n).
  * SG_E_ARG, before any GPU work: x NULL, x->flags non-zero, ivs not 4-byte
  * aligned, ivs NULL in TLS mode, unknown b->flags, and whatever the draft
- * calls reject.  Uniform 16 KiB batches run on the wave-per-record kernel and
- * every other batch on the size classes (the packed kernel and the 4-16 KiB
- * buckets of mixed draft batches are not built for this construction). */
+ * calls reject.  The batch takes the routes of the draft calls, every kernel
+ * in its RFC 8439 form: uniform 16 KiB batches the wave-per-record kernel,
+ * the eligible records of a mixed TLS batch the packed kernel (64 B-4 KiB) and
+ * the 4-16 KiB buckets, everything else the size classes. */
 typedef struct sg_batch_rfc8439 {
     const uint8_t* ivs;   /* device, [num_keys][12], 4-byte aligned: TLS mode only */
     uint32_t       flags; /* 0; anything else SG_E_ARG */
@@ -607,6 +608,23 @@ int sg_set_lockstep(int enable);
  * environment SG_PACK ("0"/"1"), else 1.  Returns the previous setting; a
  * negative argument only queries. */
 int sg_set_packed(int enable);
+
+/* Where the records of a mixed batch went (host-only bookkeeping of the
+ * dispatcher: no device work, no wait, no kernel argument).  The counts are
+ * the list populations the call read back anyway; they serve the draft calls
+ * and the RFC 8439 ones alike.  Thread-local: the calling thread's last
+ * sg_seal_batch / sg_open_batch / sg_*_batch_rfc8439 call. */
+typedef struct sg_batch_routes {
+    uint32_t known;      /* 1: this thread's last sg_*_batch* call classified its records and
+                            read the populations back (a mixed batch, not under capture);
+                            0: the other fields are not meaningful */
+    uint32_t classes;    /* records run by the size-class kernels */
+    uint32_t bucket[3];  /* wave-per-record buckets J = 2, 3, 4 */
+    uint32_t packed;     /* packed kernel */
+    uint32_t skipped;    /* longer than max_len */
+    uint32_t _pad;
+} sg_batch_routes;
+int sg_last_batch_routes(sg_batch_routes* out);   /* SG_OK, or SG_E_ARG for NULL */
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,7 @@ EXPORTS = [
     "sg_workspace_size", "sg_seal_batch", "sg_open_batch", "sg_seal_batch_rfc8439", "sg_open_batch_rfc8439",
     "sg_fill_records", "sg_compare_records",
     "sg_last_error", "sg_build_info", "sg_source_hash", "sg_set_timing", "sg_timing_read", "sg_set_lockstep", "sg_set_packed",
+    "sg_last_batch_routes",
     "sg_wire_bound", "sg_write_records", "sg_read_records", "sg_parse_records", "sg_record_timing",
     "sg_host_register", "sg_host_unregister",
     "sg_sha256", "sg_hmac_sha256", "sg_prf_new", "sg_prf_get_bytes", "sg_prf_free",
@@ -91,6 +92,13 @@ class SgBatchRfc8439(C.Structure):
     """Mirror of ``struct sg_batch_rfc8439``."""
 
     _fields_ = [("ivs", C.c_void_p), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class SgBatchRoutes(C.Structure):
+    """Mirror of ``struct sg_batch_routes``."""
+
+    _fields_ = [("known", C.c_uint32), ("classes", C.c_uint32), ("bucket", C.c_uint32 * 3), ("packed", C.c_uint32),
+                ("skipped", C.c_uint32), ("_pad", C.c_uint32)]
 
 
 class SgMsg(C.Structure):
@@ -261,6 +269,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.sg_set_lockstep.argtypes = [C.c_int]
     lib.sg_set_packed.restype = C.c_int
     lib.sg_set_packed.argtypes = [C.c_int]
+    lib.sg_last_batch_routes.restype = C.c_int
+    lib.sg_last_batch_routes.argtypes = [C.POINTER(SgBatchRoutes)]
     lib.sg_timing_read.restype = C.c_int
     d = C.POINTER(C.c_double)
     u = C.POINTER(C.c_uint32)

@@ -166,3 +166,13 @@ def timing_read() -> dict:
                                     C.byref(u[1]), C.byref(u[2])))
     return {"seal_ms": d[0].value, "open_ms": d[1].value, "keying_ms": d[2].value,
             "n_seal": u[0].value, "n_open": u[1].value, "n_keying": u[2].value}
+
+
+def last_routes() -> dict:
+    """Where the records of this thread's last ``seal`` / ``open_`` went
+    (``sg_last_batch_routes``): ``known`` is False unless that call was a mixed
+    batch whose list populations the dispatcher read back."""
+    r = N.SgBatchRoutes()
+    N.check(N.load().sg_last_batch_routes(C.byref(r)))
+    return {"known": bool(r.known), "classes": int(r.classes), "bucket": [int(x) for x in r.bucket],
+            "packed": int(r.packed), "skipped": int(r.skipped)}

@@ -236,9 +236,8 @@ int launch_batch(const sg_batch* b, const sg_batch_rfc8439* x, bool open, hipStr
     // on the populations read back), and the per-record arrays are read as
     // dwords by the bucket kernels
     // (the packed kernel, sg_pack.hip, likewise takes the 64 B-4 KiB ones)
-    // (RFC 8439: the packed kernel and the buckets are not built; a mixed batch
-    // runs on the size classes alone)
-    if (!wpr && !uniform && p.tls && !p.rfc && ((sg::wpr_enabled() && max_n > 4096u) || (sg::pack_enabled() && max_n >= 64u))) {
+    // (either construction: the routed kernels exist in the draft and the RFC 8439 form)
+    if (!wpr && !uniform && p.tls && ((sg::wpr_enabled() && max_n > 4096u) || (sg::pack_enabled() && max_n >= 64u))) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         SG_HIP(hipStreamIsCapturing(s, &cap));
         const bool ok = cap == hipStreamCaptureStatusNone &&
@@ -286,6 +285,7 @@ int launch_batch(const sg_batch* b, const sg_batch_rfc8439* x, bool open, hipStr
 }
 
 int run_batch(const sg_batch* b, bool open, const sg_batch_rfc8439* x = nullptr) {
+    sg::routes_reset();  // sg_last_batch_routes speaks of this call from here on
     int rc = validate(b, open, x);
     if (rc != SG_OK || b->count == 0) return rc;
 
@@ -528,6 +528,15 @@ int sg_compare_records(const uint8_t* a, uint64_t sa, const uint8_t* b, uint64_t
 
 int sg_set_lockstep(int enable) { return sg::set_wpr(enable); }
 int sg_set_packed(int enable) { return sg::set_pack(enable); }
+
+int sg_last_batch_routes(sg_batch_routes* out) {
+    if (!out) return fail(SG_E_ARG, "sg_batch_routes is NULL%s");
+    static_assert(sizeof(sg_batch_routes) == 4u * sg::kRouteWords, "sg_batch_routes layout");
+    uint32_t w[sg::kRouteWords];
+    sg::routes_get(w);
+    std::memcpy(out, w, sizeof w);
+    return SG_OK;
+}
 
 int sg_set_timing(int enable) {
     std::lock_guard<std::mutex> lk(g_timing_mu);

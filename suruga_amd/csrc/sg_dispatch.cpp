@@ -153,7 +153,16 @@ struct SideJoin {
     }
 };
 
+thread_local uint32_t t_routes[kRouteWords];  // sg_last_batch_routes: host bookkeeping only
+
 }  // namespace
+
+void routes_reset() {
+    for (uint32_t& w : t_routes) w = 0u;
+}
+void routes_get(uint32_t out[kRouteWords]) {
+    for (uint32_t i = 0; i < kRouteWords; ++i) out[i] = t_routes[i];
+}
 
 hipError_t launch_aead(const KParams& p, bool open, uint32_t max_n, bool uniform, hipStream_t s, uint32_t* over,
                        hipEvent_t ev_keyed, hipEvent_t ev_start) {
@@ -214,6 +223,16 @@ hipError_t launch_aead(const KParams& p, bool open, uint32_t max_n, bool uniform
         pin.done();
         for (uint32_t i = 0; i <= kNumLists; ++i) pop[i] = pin.p[i];
         *over = pop[kTailOver];
+        {  // the routes the records took (sg_last_batch_routes)
+            static_assert(kRouteWords == 2u + kWprBuckets + 3u, "sg_batch_routes");
+            t_routes[0] = 1u;
+            t_routes[1] = 0u;
+            for (uint32_t c = 0; c < kNumClasses; ++c) t_routes[1] += pop[c];
+            for (uint32_t b = 0; b < kWprBuckets; ++b) t_routes[2u + b] = pop[kNumClasses + b];
+            t_routes[2u + kWprBuckets] = pop[kPackList];
+            t_routes[3u + kWprBuckets] = pop[kTailOver];
+            t_routes[4u + kWprBuckets] = 0u;
+        }
         uint32_t nbuckets = 0;
         for (uint32_t b = 0; b < kWprBuckets; ++b) nbuckets += pop[kNumClasses + b];
         if (((p.pack_mix && pop[kPackList] != 0u) || (p.wpr_mix && nbuckets != 0u)) && side[0].acquire(s) == hipSuccess) {

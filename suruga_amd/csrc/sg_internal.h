@@ -45,7 +45,8 @@ constexpr uint32_t kWHi = 120;
 constexpr uint32_t kWprRecWords = 160;
 // Record descriptor of a listed wave-per-record record (mixed batches), u32
 // words, indexed like the keying records by the record's slot in its bucket:
-//   in_off[2] out_off[2] n rec key_index n14 n15 0 0 0
+//   in_off[2] out_off[2] n rec key_index n14 n15 n13 0 0
+// (n13: the nonce's first word, RecLayout::kRfc8439; 0 in the draft)
 constexpr uint32_t kWprDescWords = 12;
 
 // Kernel parameters (passed by value as kernarg).
@@ -84,9 +85,10 @@ struct KParams {
 // MsgLayout in sg_msg_device.h): the draft (8-byte nonce, state word 13 = 0,
 // MAC stream ad || le64(|ad|) || ct || le64(|ct|)) or RFC 8439 section 2.8
 // (12-byte nonce in words 13-15, MAC stream ad || 0.. || ct || 0.. ||
-// le64(|ad|) || le64(|ct|), every block full).  The size classes and the
-// uniform 16 KiB wave-per-record launch exist in both; the packed kernel and
-// the J = 2..4 buckets are draft only (KParams.wpr_mix / pack_mix stay 0 under rfc).
+// le64(|ad|) || le64(|ct|), every block full).  Every record kernel exists in
+// both: the size classes, the uniform 16 KiB wave-per-record launch, the J =
+// 2..4 buckets and the packed kernel, so a mixed TLS batch takes the same
+// routes (KParams.wpr_mix / pack_mix) in either construction.
 enum class RecLayout { kDraft, kRfc8439 };
 
 // Size classes of the AEAD kernel: class c (0..7) holds records of
@@ -225,6 +227,12 @@ int set_pack(int enable);
 hipError_t launch_pack(const KParams& p, bool open, const uint32_t* list, const uint32_t* cnt, uint32_t* ctr,
                        hipStream_t s);
 const char* pack_kernel_config();
+// Where the records of this thread's last mixed batch went (sg_last_batch_routes,
+// suruga_gpu.h), filled by launch_aead from the populations it reads back.
+// Words: known, classes, bucket[kWprBuckets], packed, skipped, 0.
+constexpr uint32_t kRouteWords = 8;
+void routes_reset();                          // known = 0: at the start of every batch call
+void routes_get(uint32_t out[kRouteWords]);
 // ---- sg_plumb.hip ----
 // zero the output of every record whose open status is 1 (wrong mac)
 hipError_t launch_scrub(const KParams& p, hipStream_t s);

@@ -51,6 +51,33 @@
 // 2^26 + 2^7, summed as 64 bits), so the at most 64 terms of a record never
 // overflow a word; every step is exact mod 2^130 - 5 and the tag is the
 // reference's bit for bit.
+//
+// RecLayout::kRfc8439 (sg_*_batch_rfc8439, RFC 7905 TLS records).  The MAC
+// stream is ad || 0^3 || ct || le64(13) || le64(n): the 13-byte AD padded to 16
+// is block 0, the ciphertext starts on a block boundary and every block is
+// full, B = 4 nb + 2 again.  Lane j's 64 ciphertext bytes are blocks 4 j + 1 ..
+// 4 j + 4 whole, so
+//   Q_j = sum_{k=1..4} (v_k + 2^128) r^(5 - k)
+// is the four-step Horner over the lane's own words with the pad bit: no byte
+// shift and no fifth value.  The weight W(i) = r^(1 + 4 i), i = nb - 1 - j, and
+// its tables are the draft's.  The constant term is
+//   (block0 + 2^128) r^B + (13 + n 2^64 + 2^128) r,
+// block0 the 13 AD bytes and three zero bytes.  The AD's first eight bytes are
+// be64(seq), taken from the sequence number: the nonce words are the key's
+// write IV XOR the sequence number (RFC 7905) and say nothing about the AD.
+// The nonce's first word (state word 13 of block 0 and of the data blocks, and
+// of the feed-forward) takes the slot word that the draft gives the record
+// index; the finish reads the index from the list again (open only).
+// Bounds of the unreduced accumulator for this stream: each Horner step leaves
+// h < 2^131 (h4 <= 4), so Q as radix-2^26 limbs has v0..v3 < 2^26 and
+// v4 < 2^24 + 4 2^24 < 2^27, inside fmul's operand bound (limbs < 2^27); the
+// product Q W comes out of mul_add's carry pass with limbs 0, 2, 3, 4 < 2^26
+// and limb 1 < 2^26 + 2^7.  A record has at most 64 lane terms: limbs 0, 2, 3,
+// 4 sum below 64 2^26 = 2^32, each in its own 32-bit half, and limb 1 below
+// 2^32 + 2^13 in its own 64-bit word, whose bit 32 the finish folds into limb
+// 2 (at most 1).  The draft's fifth value, which could push h4 to 5, is gone,
+// so the RFC stream holds these bounds with more room than the draft's.
+// tests/test_pack_mac_model_rfc8439.py pins the decomposition and the bounds.
 #include "sg_internal.h"
 #include "sg_device.h"
 #include "sg_chacha_grp.inc"  // grouped ChaCha20 double round (tools/gen_chacha_grp.py --product)
@@ -109,7 +136,12 @@ constexpr uint32_t kSOut = 16;    // out_off lo, hi
 constexpr uint32_t kSS = 18;      // s[4]
 constexpr uint32_t kSCtot = 22;   // constant term (5 limbs)
 constexpr uint32_t kSNb = 27, kSStart = 28, kSRec = 29;
+// RecLayout::kRfc8439: the nonce's first word where the draft keeps the record
+// index (the finish takes the index from the list instead), so both layouts
+// share the stride, the aligned 8-byte reads of kSIn / kSOut and the LDS budget
+constexpr uint32_t kSN13 = kSRec;
 static_assert(kSRec < kSlotWords, "slot layout");
+static_assert(kSlotWords % 2u == 0u && kSIn % 2u == 0u && kSOut % 2u == 0u, "8-byte slot reads");
 
 // Per-record MAC accumulator: the lane terms
 // fmul(Q, W) go in unreduced -- limbs 0, 2, 3, 4 < 2^26 (64 of them stay below
@@ -184,6 +216,14 @@ __device__ __forceinline__ void lane_mac(H32& h, const uint32_t d[16], uint32_t 
     h.h3 = addc(h.h3, 0u, c, &c);
     h.h4 += c;
 }
+// RFC 8439: the lane's block is MAC blocks 4 j + 1 .. 4 j + 4, whole and in place
+__device__ __forceinline__ void lane_mac_rfc(H32& h, const uint32_t d[16], uint32_t r0, uint32_t r1, uint32_t r2,
+                                             uint32_t r3, uint32_t s1, uint32_t s2, uint32_t s3) {
+    h = H32{0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 4; ++k)  // (h + v_k + 2^128) r
+        horner_step(h, d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3], 1u, r0, r1, r2, r3, s1, s2, s3);
+}
 
 // Phase timing (experiment builds only, -DSG_PACK_PROFILE=1; output
 // unchanged): s_memtime stamps of waves 0 and 7 of the first kProfWgs
@@ -203,11 +243,19 @@ __device__ unsigned long long g_pack_prof[kProfWgs][kProfStamps];
 #define SG_STAMP(w, k)
 #endif
 
+// The record's key and nonce in the layout's own shape (the draft's has no word 13)
+template <RecLayout LAY>
+__device__ __forceinline__ auto pack_record_key(const KParams& p, uint32_t rec) {
+    if constexpr (LAY == RecLayout::kRfc8439) return record_key_rfc(p, rec);
+    else return record_key(p, rec);
+}
+
 // One run: records first .. first + nrec - 1 of the packed list.
-template <bool OPEN>
+template <bool OPEN, RecLayout LAY>
 __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __restrict__ list, const uint32_t first,
                                          const uint32_t nrec, PackLds& L, const uint32_t tid, const uint32_t lane,
                                          const uint32_t wave) {
+    constexpr bool RFC = LAY == RecLayout::kRfc8439;
 
     SG_STAMP(0u, 0);
     for (uint32_t i = tid; i < kPackBlocks / 32u; i += kPackThreads) L.bits[i] = 0u;
@@ -229,7 +277,7 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
             const uint32_t len = record_len(p, rec);
             const uint64_t io = rec_in_off(p, rec);
             const uint64_t oo = rec_out_off(p, rec);
-            const RecKey rk = record_key(p, rec);
+            const auto rk = pack_record_key<LAY>(p, rec);
             const uint32_t n = OPEN ? len - 16u : len;  // listed records: 64 <= n <= 4096, n % 64 == 0
             nb = n >> 6;
 #if SG_PACK_PROFILE
@@ -237,7 +285,9 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
 #endif
             SG_STAMP(0u, 8);
             uint32_t ks[16];
-            chacha_block(ks, rk.k, 0u, rk.n14, rk.n15);  // block 0 -> poly key (chacha20_poly1305.rs:50,75)
+            // block 0 -> poly key (chacha20_poly1305.rs:50,75)
+            if constexpr (RFC) chacha_block(ks, rk.k, 0u, rk.n13, rk.n14, rk.n15);
+            else chacha_block(ks, rk.k, 0u, rk.n14, rk.n15);
             const PolyKey pk = poly_key(ks);
             SG_STAMP(0u, 9);
 #pragma unroll
@@ -249,7 +299,8 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
             sl[kSOut] = (uint32_t)oo; sl[kSOut + 1] = (uint32_t)(oo >> 32);
             sl[kSS + 0] = pk.s[0]; sl[kSS + 1] = pk.s[1]; sl[kSS + 2] = pk.s[2]; sl[kSS + 3] = pk.s[3];
             sl[kSNb] = nb;
-            sl[kSRec] = rec;
+            if constexpr (RFC) sl[kSN13] = rk.n13;
+            else sl[kSRec] = rec;
             // hi[a] = r^(1 + 32 a), lo[b] = R^b (R = r^4), two product chains
             const F26 r = words_to_f26(pk.r0, pk.r1, pk.r2, pk.r3, 0u);
             const F26 r2 = fmul(r, r), R = fmul(r2, r2);
@@ -275,10 +326,19 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
             const F26 rB = fmul(fmul(wl, R), r);
             // block 0: be64(seq) || type || major || minor || be16(n) || le64(13)[0..3] (tls.rs:103-112)
             const uint32_t w2 = (p.tls_hdr & 0x00ffffffu) | (((n >> 8) & 0xffu) << 24);
-            const uint32_t w3 = (n & 0xffu) | (13u << 8);
-            const F26 blk0 = words_to_f26(rk.n14, rk.n15, w2, w3, 1u);   // + the pad 2^128
-            const F26 sfx = words_to_f26(0u, n << 8, 0u, 256u, 0u);      // n 2^40 + 2^104
-            store_f26(sl + kSCtot, fmul_add(blk0, rB, fmul(sfx, r)));
+            if constexpr (RFC) {
+                // block 0: the AD and three zero bytes; its be64(seq) from the sequence number
+                // (the nonce words carry the write IV, RFC 7905); last block: le64(13) || le64(n)
+                const uint32_t a0 = bswap32((uint32_t)(rk.seq >> 32)), a1 = bswap32((uint32_t)rk.seq);
+                const F26 blk0 = words_to_f26(a0, a1, w2, n & 0xffu, 1u);  // + the pad 2^128
+                const F26 sfx = words_to_f26(13u, 0u, n, 0u, 1u);          // 13 + n 2^64 + 2^128
+                store_f26(sl + kSCtot, fmul_add(blk0, rB, fmul(sfx, r)));
+            } else {
+                const uint32_t w3 = (n & 0xffu) | (13u << 8);
+                const F26 blk0 = words_to_f26(rk.n14, rk.n15, w2, w3, 1u);   // + the pad 2^128
+                const F26 sfx = words_to_f26(0u, n << 8, 0u, 256u, 0u);      // n 2^40 + 2^104
+                store_f26(sl + kSCtot, fmul_add(blk0, rB, fmul(sfx, r)));
+            }
         }
         const uint32_t incl = wave_incl_scan(nb, lane);
         start = incl - nb;
@@ -362,8 +422,10 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
 #pragma unroll
         for (int i = 0; i < 8; ++i) kw[i] = sl[kSKey + i];
         const uint32_t ctr = j + 1u, n14 = sl[kSN14], n15 = sl[kSN15];  // data uses blocks 1.. (chacha20_poly1305.rs:52)
+        uint32_t n13 = 0u;  // RFC 8439 section 2.3: the nonce's first word
+        if constexpr (RFC) n13 = sl[kSN13];
         uint32_t x[16] = {kSigma0, kSigma1, kSigma2, kSigma3, kw[0], kw[1], kw[2], kw[3],
-                          kw[4],   kw[5],   kw[6],   kw[7],   ctr,     0u,    n14,   n15};
+                          kw[4],   kw[5],   kw[6],   kw[7],   ctr,     RFC ? n13 : 0u, n14, n15};
         // EXEC limited to the lanes with a block (none in a round without a
         // chunk for this wave; s_barrier ignores EXEC, so all waves still meet)
         const uint64_t live = __builtin_amdgcn_ballot_w64(valid);
@@ -382,7 +444,7 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
             const u32x4 o0 = d0 ^ u32x4{x[0] + kSigma0, x[1] + kSigma1, x[2] + kSigma2, x[3] + kSigma3};
             const u32x4 o1 = d1 ^ u32x4{x[4] + kw[0], x[5] + kw[1], x[6] + kw[2], x[7] + kw[3]};
             const u32x4 o2 = d2 ^ u32x4{x[8] + kw[4], x[9] + kw[5], x[10] + kw[6], x[11] + kw[7]};
-            const u32x4 o3 = d3 ^ u32x4{x[12] + ctr, x[13], x[14] + n14, x[15] + n15};
+            const u32x4 o3 = d3 ^ u32x4{x[12] + ctr, RFC ? x[13] + n13 : x[13], x[14] + n14, x[15] + n15};
             uint8_t* dst = p.out + oo + 64u * j;
             pst16(dst, o0);
             pst16(dst + 16, o1);
@@ -394,7 +456,8 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
                                      a2[0], a2[1], a2[2], a2[3], a3[0], a3[1], a3[2], a3[3]};
             const uint32_t r0 = sl[kSR + 0], r1 = sl[kSR + 1], r2 = sl[kSR + 2], r3 = sl[kSR + 3];
             H32 h;
-            lane_mac(h, cw, r0, r1, r2, r3, r1 + (r1 >> 2), r2 + (r2 >> 2), r3 + (r3 >> 2));
+            if constexpr (RFC) lane_mac_rfc(h, cw, r0, r1, r2, r3, r1 + (r1 >> 2), r2 + (r2 >> 2), r3 + (r3 >> 2));
+            else lane_mac(h, cw, r0, r1, r2, r3, r1 + (r1 >> 2), r2 + (r2 >> 2), r3 + (r3 >> 2));
             const F26 Q = words_to_f26(h.h0, h.h1, h.h2, h.h3, h.h4);
             const uint32_t i = sl[kSNb] - 1u - j;
             const uint32_t* tb = L.tab + m * kTabWords;
@@ -416,7 +479,10 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
     // ---- finish: one lane per record (waves 0-1) --------------------------------
     if (act) {
         const uint32_t* sl = L.slot + m0 * kSlotWords;
-        const uint32_t n = 64u * sl[kSNb], rec = sl[kSRec];
+        const uint32_t n = 64u * sl[kSNb];
+        uint32_t rec = 0u;  // (open: the status index)
+        if constexpr (!RFC) rec = sl[kSRec];
+        else if constexpr (OPEN) rec = list[first + m0];  // the slot word holds n13
         const uint32_t* ac = L.acc + kAccWords * m0;
         // (v1 = lo + hi 2^32 -> hi 2^58 = (hi << 6) 2^52 joins limb 2 after the
         // first carry pass: limb 2's raw sum can reach 2^32 - 64, and hi <= 1)
@@ -441,7 +507,7 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
 // population is read from the workspace tail (the host does not need it, so
 // the launch goes ahead of the population readback) and the 128-record runs
 // come from a device counter, so that the runs' different lengths even out.
-template <bool OPEN>
+template <bool OPEN, RecLayout LAY>
 __global__ __launch_bounds__(kPackThreads) __attribute__((amdgpu_waves_per_eu(6)))
 void sg_pack_kernel(const KParams p, const uint32_t* __restrict__ list, const uint32_t* __restrict__ cnt, uint32_t* ctr) {
     __shared__ PackLds L;
@@ -454,7 +520,7 @@ void sg_pack_kernel(const KParams p, const uint32_t* __restrict__ list, const ui
         const uint32_t run = __builtin_amdgcn_readfirstlane(L.run);
         if (run >= nruns) break;  // (workgroup-uniform)
         const uint32_t first = run * kPackRecs;
-        pack_run<OPEN>(p, list, first, count - first < kPackRecs ? count - first : kPackRecs, L, tid, lane, wave);
+        pack_run<OPEN, LAY>(p, list, first, count - first < kPackRecs ? count - first : kPackRecs, L, tid, lane, wave);
         __syncthreads();  // the finish read the slots that the next run's setup rewrites, and L.run
     }
 }
@@ -470,10 +536,10 @@ hipError_t launch_pack(const KParams& p, bool open, const uint32_t* list, const 
     if ((e = device_cus(&cus)) != hipSuccess) return e;
     const uint32_t most = (p.count + kPackRecs - 1u) / kPackRecs;
     const uint32_t grid = 3u * (uint32_t)cus < most ? 3u * (uint32_t)cus : most;  // three workgroups per CU
-    if (open)
-        hipLaunchKernelGGL((sg_pack_kernel<true>), dim3(grid), dim3(kPackThreads), 0, s, p, list, count, ctr);
-    else
-        hipLaunchKernelGGL((sg_pack_kernel<false>), dim3(grid), dim3(kPackThreads), 0, s, p, list, count, ctr);
+    constexpr RecLayout D = RecLayout::kDraft, R = RecLayout::kRfc8439;
+    const auto kernel = p.rfc ? (open ? sg_pack_kernel<true, R> : sg_pack_kernel<false, R>)
+                              : (open ? sg_pack_kernel<true, D> : sg_pack_kernel<false, D>);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPackThreads), 0, s, p, list, count, ctr);
     return hipGetLastError();
 }
 
@@ -491,7 +557,9 @@ bool pack_enabled() { return g_pack.on(); }
 int set_pack(int enable) { return g_pack.set(enable); }
 
 const char* pack_kernel_config() {
-    return "sg_pack_kernel v5: mixed-batch TLS records of 64 B-4 KiB (multiples of 64 B) packed 64-byte block per lane "
+    return "sg_pack_kernel v6 (draft and RFC 8439 / RFC 7905 forms; RFC: word-13 nonce, block-aligned 4-step lane "
+           "Horner without a fifth value, AD / length constant term of the RFC stream): mixed-batch TLS records of "
+           "64 B-4 KiB (multiples of 64 B) packed 64-byte block per lane "
            "across 128-record runs (512-thread workgroups on a persistent grid taking runs from a device counter, launched "
            "ahead of the population readback; chunk rounds, lock-step grouped ChaCha20 rounds with EXEC limited "
            "to the lanes holding a block; chunks to SIMD pairs first, waves without a chunk in the last round keep "

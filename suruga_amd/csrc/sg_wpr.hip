@@ -51,7 +51,7 @@
 // (tests/test_wpr_mac_model.py pins this decomposition against the CPU
 // restatement of poly1305.rs).
 //
-// RecLayout::kRfc8439 (the uniform launch only; sg_*_batch_rfc8439): in the RFC
+// RecLayout::kRfc8439 (the uniform launch and the J = 2..4 buckets; sg_*_batch_rfc8439): in the RFC
 // 8439 stream ad || 0.. || ct || 0.. || le64(|ad|) || le64(n) the ciphertext
 // starts on a block boundary, which is the sigma = 0 case above for every AD
 // length, so the MFMA body is the draft's.  The keying kernel's constant term
@@ -61,6 +61,10 @@
 // in state word 13 (u[13] on the SALU, x[13] + n13 in the feed-forward), and
 // the TLS nonce is the key's write IV XOR the byte-swapped sequence number (RFC
 // 7905), on the SALU.  tests/test_wpr_mac_model_rfc8439.py pins the constant term.
+// Bucket records (LIST) carry the nonce's first word in descriptor word 9; their
+// constant term is wpr_geom<kRfc8439>(13, n) of the right-aligned record, with
+// the S(c) pieces of the draft's bucket keying (they depend on n / 64 alone) and
+// the same single length block (tests/test_wpr_bucket_model_rfc8439.py).
 #include "sg_internal.h"
 #include "sg_device.h"
 #include "sg_chacha_grp.inc"  // grouped ChaCha20 double round (tools/gen_chacha_grp.py --product)
@@ -186,7 +190,6 @@ template <bool OPEN, bool LIST, RecLayout LAY>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg_wpr_keying_kernel(
     const KParams p, const WprKeyJobs jobs) {
     constexpr bool RFC = LAY == RecLayout::kRfc8439;
-    static_assert(!(RFC && LIST), "the buckets are draft only");
     const uint32_t lane = threadIdx.x;
     WprList wl = jobs.b[0];
     uint32_t b0 = 0;
@@ -229,7 +232,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
             uint32_t* d = wl.desc + (uint64_t)slot * kWprDescWords;
             st16(d, u32x4{(uint32_t)io, (uint32_t)(io >> 32), (uint32_t)oo, (uint32_t)(oo >> 32)});
             st16(d + 4, u32x4{n, rec, ki, rk.n14});
-            st16(d + 8, u32x4{rk.n15, 0u, 0u, 0u});
+            st16(d + 8, u32x4{rk.n15, RFC ? rk.n13 : 0u, 0u, 0u});
         }
     }
 
@@ -519,7 +522,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                                                                                                const WprList wl) {
     static_assert(J >= 1u && J <= 4u && (LIST || J == 4u), "uniform launches are full 16 KiB records");
     constexpr bool RFC = LAY == RecLayout::kRfc8439;
-    static_assert(!(RFC && LIST), "the buckets are draft only");
     constexpr uint32_t j0 = 4u - J;  // the first chunk of the right-aligned record in the 16 KiB frame
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const uint32_t wave = uniform(threadIdx.x >> 6), lane = threadIdx.x & 63u;
@@ -577,6 +579,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             d.ki = cload(dw, 6);
             d.n14 = cload(dw, 7);
             d.n15 = cload(dw, 8);
+            if constexpr (RFC) d.n13 = cload(dw, 9);
         } else {
             d.rec = slot;
             d.io = p.in_stride * slot;
@@ -619,6 +622,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         d.ki = uniform(dl[6]);
         d.n14 = uniform(dl[7]);
         d.n15 = uniform(dl[8]);
+        if constexpr (RFC) d.n13 = uniform(dl[9]);
         return d;
     };
 
@@ -1258,7 +1262,7 @@ hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_
 }
 
 hipError_t launch_wpr_keying_lists(const KParams& p, bool open, const WprList* wl, hipStream_t s) {
-    if (!p.tls || p.rfc) return hipErrorInvalidValue;  // buckets are TLS records of the draft
+    if (!p.tls) return hipErrorInvalidValue;  // buckets are TLS records (of either construction)
     WprKeyJobs jobs = {};
     uint32_t grid = 0;
     for (uint32_t b = 0; b < kWprBuckets; ++b) {
@@ -1269,21 +1273,29 @@ hipError_t launch_wpr_keying_lists(const KParams& p, bool open, const WprList* w
         ++jobs.njobs;
     }
     if (grid == 0) return hipSuccess;
-    if (open)
-        hipLaunchKernelGGL((sg_wpr_keying_kernel<true, true, RecLayout::kDraft>), dim3(grid), dim3(kWprKeyThreads), 0, s, p, jobs);
-    else
-        hipLaunchKernelGGL((sg_wpr_keying_kernel<false, true, RecLayout::kDraft>), dim3(grid), dim3(kWprKeyThreads), 0, s, p, jobs);
+    constexpr RecLayout D = RecLayout::kDraft, R = RecLayout::kRfc8439;
+    const auto keying = p.rfc ? (open ? sg_wpr_keying_kernel<true, true, R> : sg_wpr_keying_kernel<false, true, R>)
+                              : (open ? sg_wpr_keying_kernel<true, true, D> : sg_wpr_keying_kernel<false, true, D>);
+    hipLaunchKernelGGL(keying, dim3(grid), dim3(kWprKeyThreads), 0, s, p, jobs);
     return hipGetLastError();
 }
 
 hipError_t launch_wpr_list(const KParams& p, bool open, uint32_t J, const WprList& wl, hipStream_t s) {
     if (wl.count == 0) return hipSuccess;
-    if (!p.tls || p.rfc || J < kWprMinJ || J > 4u) return hipErrorInvalidValue;  // buckets are TLS records of 2..4 chunks
+    if (!p.tls || J < kWprMinJ || J > 4u) return hipErrorInvalidValue;  // buckets are TLS records of 2..4 chunks
     hipError_t e;
     int cus = 0;
     if ((e = device_cus(&cus)) != hipSuccess) return e;
     const uint32_t grid = wpr_grid(cus, wl.count);
-#define SG_WPR_LAUNCH(O, JJ) hipLaunchKernelGGL((sg_wpr_kernel<O, true, JJ, true, RecLayout::kDraft>), dim3(grid), dim3(512), kWprWgLds, s, p, wl)
+#define SG_WPR_LAUNCH(O, JJ)                                                                                         \
+    do {                                                                                                            \
+        if (p.rfc)                                                                                                  \
+            hipLaunchKernelGGL((sg_wpr_kernel<O, true, JJ, true, RecLayout::kRfc8439>), dim3(grid), dim3(512),       \
+                               kWprWgLds, s, p, wl);                                                                \
+        else                                                                                                        \
+            hipLaunchKernelGGL((sg_wpr_kernel<O, true, JJ, true, RecLayout::kDraft>), dim3(grid), dim3(512),         \
+                               kWprWgLds, s, p, wl);                                                                \
+    } while (0)
     switch (J) {
         case 2: if (open) SG_WPR_LAUNCH(true, 2); else SG_WPR_LAUNCH(false, 2); break;
         case 3: if (open) SG_WPR_LAUNCH(true, 3); else SG_WPR_LAUNCH(false, 3); break;
@@ -1306,7 +1318,8 @@ const char* wpr_kernel_config() {
            "v_mfma_i32_32x32x32_i8 per record fed from the ciphertext registers one chunk behind (Toeplitz digit "
            "lines of r^(128k+d) in LDS, read as aligned dwords + v_alignbyte), exact per-lane assembly, "
            "W = r^(4(31-q)) scaling, DPP sum; keying pre-pass with the constant term; bucket records: the idle lanes "
-           "of the first chunk sit out its rounds (EXEC)";
+           "of the first chunk sit out its rounds (EXEC); every form also as RecLayout::kRfc8439 (RFC 8439 / RFC 7905: "
+           "word-13 nonce, block-aligned MAC stream; uniform 16 KiB launch and the J = 2..4 buckets)";
 }
 
 }  // namespace sg

@@ -7,12 +7,17 @@ Two batches, both device-resident TLS records:
 * ``uniform``: ``--records`` (default 2^18) records of 16 KiB, one key, sequential
   seq -- the wave-per-record kernel in both constructions;
 * ``mixed``: ``--mixed-records`` records of the C2 Zipf layout (64 B-16 KiB, 256
-  connection keys, suruga_amd.workloads.c2_layout) -- the draft runs it on the
-  packed kernel, the buckets and the size classes, RFC 8439 on the size classes
-  alone, so ``rfc_vs_draft_*`` here prices that route.
+  connection keys, suruga_amd.workloads.c2_layout) -- both constructions run it on
+  the packed kernel, the buckets and the size classes.  A third leg,
+  ``rfc_classes``, runs the RFC batch with ``sg_set_packed(0)`` and
+  ``sg_set_lockstep(0)``: the size classes alone, the only route the RFC batch had
+  before the routed kernels existed in its form; ``routed_vs_classes_*`` is the
+  routed RFC time over that leg's.  ``routes`` holds every leg's route populations
+  (``sg_last_batch_routes``), and the two RFC legs' sealed images must be equal.
 
-The draft and RFC legs alternate launch by launch in one process (draft seal, RFC
-seal, draft open, RFC open per round), so they share the clock the board holds.
+The legs alternate launch by launch in one process (draft seal, RFC seal, class-only
+RFC seal, then the opens in the same order, per round), so they share the clock the
+board holds.
 Each leg reports the median of ``--reps`` launches after ``--warmup`` from HIP
 events, GiB/s of payload, and ``spread`` = (max - min) / median.
 ``rfc_vs_draft_*`` is RFC time over draft time.  ``timing`` splits each
@@ -21,6 +26,9 @@ construction's launches into keying pre-pass and record kernel
 batch is compared with tests/rfc8439_ref.py, every byte and the tag.
 
     python tools/rfc_batch_bench.py [--records 262144] [--mixed-records 262144] [--reps 25]
+
+``--records 0`` skips the uniform batch.  ``clock`` (uniform) and ``mixed.clock`` are
+the shader clock and board power sampled while each batch's legs ran.
 """
 from __future__ import annotations
 
@@ -109,7 +117,8 @@ def make_mixed(count: int):
     in_off, out_off, kidx, seqs = t64(lay.in_off), t64(lay.out_off), t32(lay.key_index), t64(lay.seq)
     maxl = int(lay.lens.max())
     legs, cts, sts = {}, {}, {}
-    for name, extra in (("draft", {}), ("rfc", dict(rfc8439=True, ivs=ivs))):
+    for name, extra in (("draft", {}), ("rfc", dict(rfc8439=True, ivs=ivs)),
+                        ("rfc_classes", dict(rfc8439=True, ivs=ivs))):
         ct = torch.empty(lay.ct_bytes, dtype=torch.uint8, device="cuda")
         st = torch.zeros(count, dtype=torch.uint8, device="cuda")
         legs[name] = (B.Batch(count=count, keys=keys, inp=pt, out=ct, lens=lens, max_len=maxl, in_off=in_off,
@@ -126,6 +135,7 @@ def make_mixed(count: int):
                 pt[io:io + n].cpu().numpy().tobytes(), cts["rfc"][oo:oo + n + 16].cpu().numpy().tobytes())
 
     return dict(count=count, payload=int(lay.payload), legs=legs, pt=pt, back=back, sts=sts, record=record,
+                forms={"rfc_classes": dict(lockstep=0, packed=0)}, same=[(cts["rfc"], cts["rfc_classes"])],
                 desc=f"{count} Zipf(1.1) TLS records 64 B-16 KiB (mean {lay.payload / count:.0f} B), {num_keys} keys")
 
 
@@ -134,8 +144,23 @@ def run(w: dict, reps: int, warmup: int) -> dict:
 
     from suruga_amd import batch as B
 
-    order = [("draft_seal", lambda: B.seal(w["legs"]["draft"][0])), ("rfc_seal", lambda: B.seal(w["legs"]["rfc"][0])),
-             ("draft_open", lambda: B.open_(w["legs"]["draft"][1])), ("rfc_open", lambda: B.open_(w["legs"]["rfc"][1]))]
+    from gpu_support import kernel_forms  # sets the switches and puts them back after the launch
+
+    from suruga_amd import _native
+
+    lib = _native.load()
+    names = list(w["legs"])
+    forms = w.get("forms", {})
+    routes = {}
+
+    def leg(name, d):
+        def fn():
+            with kernel_forms(lib, **forms.get(name, {})):
+                (B.open_ if d else B.seal)(w["legs"][name][d])
+            routes.setdefault(f"{name}_{'open' if d else 'seal'}", B.last_routes())
+        return f"{name}_{'open' if d else 'seal'}", fn
+
+    order = [leg(name, d) for d in (0, 1) for name in names]
     times = {k: [] for k, _ in order}
     for rep in range(warmup + reps):
         for name, fn in order:  # alternating: every leg once per round
@@ -147,14 +172,19 @@ def run(w: dict, reps: int, warmup: int) -> dict:
             if rep >= warmup:
                 times[name].append(a.elapsed_time(b))
     torch.cuda.synchronize()
-    for name in ("draft", "rfc"):
+    for name in names:
         assert int(w["sts"][name].sum().item()) == 0, f"{name}: open status"
     assert torch.equal(w["back"], w["pt"]), "round trip"
+    for a, b in w.get("same", []):
+        assert torch.equal(a, b), "the routed and the class-only RFC images differ"
     out = {"batch": w["desc"], "payload_bytes": w["payload"]}
     for name, ms in times.items():
         out[name] = summary(ms, w["payload"])
     for d in ("seal", "open"):
         out[f"rfc_vs_draft_{d}"] = round(out[f"rfc_{d}"]["ms"] / out[f"draft_{d}"]["ms"], 4)
+        if "rfc_classes" in names:
+            out[f"routed_vs_classes_{d}"] = round(out[f"rfc_{d}"]["ms"] / out[f"rfc_classes_{d}"]["ms"], 4)
+    out["routes"] = routes
     # where the time goes: keying pre-pass and record kernel of each construction
     out["timing"] = {}
     for name in ("draft", "rfc"):
@@ -189,7 +219,7 @@ def check(w: dict) -> dict:
 
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--records", type=int, default=1 << 18, help="uniform 16 KiB batch")
+    ap.add_argument("--records", type=int, default=1 << 18, help="uniform 16 KiB batch (0: skip)")
     ap.add_argument("--mixed-records", type=int, default=1 << 18, help="Zipf batch (0: skip)")
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=3)
@@ -205,19 +235,24 @@ def main() -> None:
     bus = f"{props.pci_domain_id:04x}:{props.pci_bus_id:02x}:{props.pci_device_id:02x}.0"
     res = {"tool": "rfc_batch_bench", "device": torch.cuda.get_device_name(0), "lib": _native.loaded_info(),
            "reps": args.reps, "warmup": args.warmup}
-    w = make_uniform(args.records)
-    sampler = devmon.Sampler(bus, period=0.002).start()  # the clock and power while the uniform legs run
-    t0 = time.perf_counter()
-    res["uniform"] = run(w, args.reps, args.warmup)
-    clk = sampler.stop(t0, time.perf_counter())
-    res["clock"] = {"sclk_mhz": clk["sclk_mhz"], "board_power_w": clk["board_power_w"],
-                    "power_cap_w": clk.get("power_cap_w")}
-    res["uniform"]["check"] = check(w)
-    del w
-    torch.cuda.empty_cache()
+    def sampled(w):  # run() with the clock and power while its legs run
+        sampler = devmon.Sampler(bus, period=0.002).start()
+        t0 = time.perf_counter()
+        out = run(w, args.reps, args.warmup)
+        clk = sampler.stop(t0, time.perf_counter())
+        return out, {"sclk_mhz": clk["sclk_mhz"], "board_power_w": clk["board_power_w"],
+                     "power_cap_w": clk.get("power_cap_w")}
+
+    if args.records:
+        w = make_uniform(args.records)
+        res["uniform"], res["clock"] = sampled(w)
+        res["uniform"]["check"] = check(w)
+        del w
+        torch.cuda.empty_cache()
     if args.mixed_records:
         w = make_mixed(args.mixed_records)
-        res["mixed"] = run(w, args.reps, args.warmup)
+        res["mixed"], clk = sampled(w)
+        res["mixed"]["clock"] = clk
         res["mixed"]["check"] = check(w)
     print(json.dumps(res))
 
