@@ -30,7 +30,7 @@ HIP_SOURCES = [CSRC / "sg_kernels.hip", CSRC / "sg_wpr.hip", CSRC / "sg_pack.hip
                CSRC / "sg_msg_batch.hip", CSRC / "sg_msg_batch_capi.cpp"]
 HIP_DEPS = HIP_SOURCES + [CSRC / "sg_internal.h", CSRC / "sg_device.h", CSRC / "sg_host.h", CSRC / "sg_err.h",
                           CSRC / "sg_wire.h", CSRC / "sg_copy_pool.h", CSRC / "sg_env.h", CSRC / "sg_chacha_grp.inc",
-                          CSRC / "sg_msg_plan.h", CSRC / "sg_msg_device.h",
+                          CSRC / "sg_msg_plan.h", CSRC / "sg_msg_device.h", CSRC / "sg_layout.h",
                           ROOT / "include" / "suruga_gpu.h"]
 ORACLE_SOURCES = [ORACLE_DIR / "suruga_oracle.c"]
 ORACLE_DEPS = ORACLE_SOURCES + [ORACLE_DIR / "suruga_oracle.h", ORACLE_DIR / "so_pool.h"]

@@ -113,7 +113,7 @@ constexpr uint32_t kSigma0 = 0x61707865u, kSigma1 = 0x3320646eu, kSigma2 = 0x796
 // words, ctr = state word 12, n13 = state word 13, n14/n15 = nonce words.
 // ks[i] = round20(state)[i] (little-endian words).  Word 13 is 0 in the draft
 // construction (chacha20.rs:114-121) and the first nonce word in RFC 8439
-// (section 2.3): the message kernels and the RecLayout::kRfc8439 record kernels.
+// (section 2.3): the Construction::kRfc8439 kernels.
 __device__ __forceinline__ void chacha_block(uint32_t ks[16], const uint32_t k[8], uint32_t ctr, uint32_t n13,
                                              uint32_t n14, uint32_t n15) {
     uint32_t x0 = kSigma0, x1 = kSigma1, x2 = kSigma2, x3 = kSigma3;
@@ -129,11 +129,6 @@ __device__ __forceinline__ void chacha_block(uint32_t ks[16], const uint32_t k[8
     ks[4] = x4 + k[0]; ks[5] = x5 + k[1]; ks[6] = x6 + k[2]; ks[7] = x7 + k[3];
     ks[8] = x8 + k[4]; ks[9] = x9 + k[5]; ks[10] = x10 + k[6]; ks[11] = x11 + k[7];
     ks[12] = x12 + ctr; ks[13] = x13 + n13; ks[14] = x14 + n14; ks[15] = x15 + n15;
-}
-// the draft's form: word 13 is always 0
-__device__ __forceinline__ void chacha_block(uint32_t ks[16], const uint32_t k[8], uint32_t ctr, uint32_t n14,
-                                             uint32_t n15) {
-    chacha_block(ks, k, ctr, 0u, n14, n15);
 }
 
 // ---- uniform-record variant: the counter-free part of round 1 on the SALU ----
@@ -156,9 +151,6 @@ __device__ __forceinline__ ChaChaPre chacha_pre(const uint32_t k[8], uint32_t n1
     uint32_t x13 = n13, x14 = n14, x15 = n15;
     SG_QR_S(x1, x5, x9, x13) SG_QR_S(x2, x6, x10, x14) SG_QR_S(x3, x7, x11, x15)
     return ChaChaPre{{0x61707865u + k[0], x1, x2, x3, k[0], x5, x6, x7, k[4], x9, x10, x11, 0u, x13, x14, x15}};
-}
-__device__ __forceinline__ ChaChaPre chacha_pre(const uint32_t k[8], uint32_t n14, uint32_t n15) {
-    return chacha_pre(k, 0u, n14, n15);
 }
 
 // Same result as chacha_block(ks, k, ctr, n13, n14, n15), starting from
@@ -184,10 +176,6 @@ __device__ __forceinline__ void chacha_block_pre(uint32_t ks[16], const ChaChaPr
     ks[4] = x4 + k[0]; ks[5] = x5 + k[1]; ks[6] = x6 + k[2]; ks[7] = x7 + k[3];
     ks[8] = x8 + k[4]; ks[9] = x9 + k[5]; ks[10] = x10 + k[6]; ks[11] = x11 + k[7];
     ks[12] = x12 + ctr; ks[13] = x13 + n13; ks[14] = x14 + n14; ks[15] = x15 + n15;
-}
-__device__ __forceinline__ void chacha_block_pre(uint32_t ks[16], const ChaChaPre& P, const uint32_t k[8],
-                                                 uint32_t ctr, uint32_t n14, uint32_t n15) {
-    chacha_block_pre(ks, P, k, ctr, 0u, n14, n15);
 }
 
 // ---- Poly1305 field arithmetic, radix 2^26 ---------------------------------
@@ -429,73 +417,55 @@ __device__ __forceinline__ uint8_t tag_mismatch(const A& rx, const B& tw) {
 }
 
 // ---- per-record parameters ---------------------------------------------------
+// Key and nonce of a record: the key words and state words 13-15 (n13 = 0 in
+// the draft, whose 8-byte nonce fills words 14-15; RFC 8439 section 2.3 puts a
+// 12-byte nonce in words 13-15), and the TLS sequence number (0 in explicit mode).
 struct RecKey {
-    uint32_t k[8];
-    uint32_t n14, n15;
-    uint64_t seq;
-};
-
-__device__ __forceinline__ RecKey record_key(const KParams& p, uint32_t rec) {
-    RecKey rk;
-    uint32_t ki = p.key_index ? p.key_index[rec] : 0u;
-    ki = ki < p.num_keys ? ki : p.num_keys - 1u;  // out-of-range indices stay inside the key table
-    const uint32_t* kw = reinterpret_cast<const uint32_t*>(p.keys + 32u * ki);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) rk.k[i] = kw[i];  // keys are little-endian words (chacha20.rs:37-39)
-    if (p.tls) {
-        // nonce = u64_be_array(seq) (tls.rs:103, util.rs:43-45) loaded as two
-        // little-endian words (chacha20.rs:45-46)
-        rk.seq = p.seq ? p.seq[rec] : p.seq0 + rec;
-        rk.n14 = bswap32((uint32_t)(rk.seq >> 32));
-        rk.n15 = bswap32((uint32_t)rk.seq);
-    } else {
-        const uint8_t* nb = p.nonces + 8ull * rec;
-        rk.seq = 0;
-        rk.n14 = le32(nb);
-        rk.n15 = le32(nb + 4);
-    }
-    return rk;
-}
-
-// The same for the RFC 8439 record batch: a 12-byte nonce in state words 13-15
-// (RFC 8439 section 2.3).  TLS mode is RFC 7905 section 2: the key's 12-byte
-// write IV XOR (00 00 00 00 || be64(seq)); explicit mode reads 12 bytes per record.
-struct RecKeyRfc {
     uint32_t k[8];
     uint32_t n13, n14, n15;
     uint64_t seq;
 };
-__device__ __forceinline__ RecKeyRfc record_key_rfc(const KParams& p, uint32_t rec) {
-    RecKeyRfc rk;
-    uint32_t ki = p.key_index ? p.key_index[rec] : 0u;
-    ki = ki < p.num_keys ? ki : p.num_keys - 1u;  // (record_key's clamp: the IV table has num_keys rows too)
+
+// Row of the key table (and of the RFC 7905 write-IV table, which has num_keys
+// rows too) for a key index: out-of-range indices stay inside the table.
+__device__ __forceinline__ uint32_t key_slot_of(const KParams& p, uint32_t ki) {
+    return ki < p.num_keys ? ki : p.num_keys - 1u;
+}
+__device__ __forceinline__ uint32_t key_slot(const KParams& p, uint32_t rec) {
+    return key_slot_of(p, p.key_index ? p.key_index[rec] : 0u);
+}
+
+template <Construction C>
+__device__ __forceinline__ RecKey record_key(const KParams& p, uint32_t rec) {
+    constexpr bool RFC = C == Construction::kRfc8439;
+    RecKey rk;
+    const uint32_t ki = key_slot(p, rec);
     const uint32_t* kw = reinterpret_cast<const uint32_t*>(p.keys + 32u * ki);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) rk.k[i] = kw[i];
+    for (int i = 0; i < 8; ++i) rk.k[i] = kw[i];  // keys are little-endian words (chacha20.rs:37-39)
     if (p.tls) {
-        const uint32_t* iv = reinterpret_cast<const uint32_t*>(p.ivs + 12u * ki);
+        // draft: nonce = u64_be_array(seq) (tls.rs:103, util.rs:43-45) loaded as
+        // two little-endian words (chacha20.rs:45-46); RFC 7905 section 2: the
+        // key's 12-byte write IV XOR (00 00 00 00 || be64(seq))
         rk.seq = p.seq ? p.seq[rec] : p.seq0 + rec;
-        rk.n13 = iv[0];
-        rk.n14 = iv[1] ^ bswap32((uint32_t)(rk.seq >> 32));
-        rk.n15 = iv[2] ^ bswap32((uint32_t)rk.seq);
-    } else {
-        const uint8_t* nb = p.nonces + 12ull * rec;
+        if constexpr (RFC) {
+            const uint32_t* iv = reinterpret_cast<const uint32_t*>(p.ivs + 12u * ki);
+            rk.n13 = iv[0];
+            rk.n14 = iv[1] ^ bswap32((uint32_t)(rk.seq >> 32));
+            rk.n15 = iv[2] ^ bswap32((uint32_t)rk.seq);
+        } else {
+            rk.n13 = 0u;
+            rk.n14 = bswap32((uint32_t)(rk.seq >> 32));
+            rk.n15 = bswap32((uint32_t)rk.seq);
+        }
+    } else {  // explicit mode: nonce_len<C>() bytes per record, little-endian words
+        const uint8_t* nb = p.nonces + (uint64_t)nonce_len<C>() * rec;
         rk.seq = 0;
-        rk.n13 = le32(nb);
-        rk.n14 = le32(nb + 4);
-        rk.n15 = le32(nb + 8);
+        rk.n13 = RFC ? le32(nb) : 0u;
+        rk.n14 = le32(nb + (RFC ? 4 : 0));
+        rk.n15 = le32(nb + (RFC ? 8 : 4));
     }
     return rk;
-}
-// record_key in the shape of the layout: the draft's word 13 is 0
-template <RecLayout LAY>
-__device__ __forceinline__ RecKeyRfc record_key_of(const KParams& p, uint32_t rec) {
-    if constexpr (LAY == RecLayout::kRfc8439) {
-        return record_key_rfc(p, rec);
-    } else {
-        const RecKey d = record_key(p, rec);
-        return RecKeyRfc{{d.k[0], d.k[1], d.k[2], d.k[3], d.k[4], d.k[5], d.k[6], d.k[7]}, 0u, d.n14, d.n15, d.seq};
-    }
 }
 
 __device__ __forceinline__ uint32_t record_len(const KParams& p, uint32_t rec) {
@@ -518,18 +488,15 @@ __device__ __forceinline__ uint8_t tls_ad_byte(uint64_t seq, uint32_t hdr, uint3
     return (uint8_t)n;
 }
 
-// Byte i (< adlen + 8) of the MAC stream prefix ad || le64(|ad|)
-// (chacha20_poly1305.rs:24-26).
+// Byte i (< ct_offset<C>(adlen)) of the MAC stream in front of the ciphertext:
+// ad || le64(|ad|) in the draft (chacha20_poly1305.rs:24-26), ad and its zero
+// padding in RFC 8439.
+template <Construction C>
 __device__ __forceinline__ uint8_t prefix_byte(const KParams& p, uint32_t rec, uint64_t seq, uint32_t n, uint32_t adlen,
                                                uint32_t i) {
     if (i < adlen) return p.tls ? tls_ad_byte(seq, p.tls_hdr, n, i) : p.ads[(uint64_t)p.ad_stride * rec + i];
-    return (uint8_t)((uint64_t)adlen >> (8u * (i - adlen)));
-}
-// Byte i (< 16 ceil(adlen / 16)) of the RFC 8439 prefix: ad, then its zero padding.
-__device__ __forceinline__ uint8_t prefix_byte_rfc(const KParams& p, uint32_t rec, uint64_t seq, uint32_t n,
-                                                   uint32_t adlen, uint32_t i) {
-    if (i < adlen) return p.tls ? tls_ad_byte(seq, p.tls_hdr, n, i) : p.ads[(uint64_t)p.ad_stride * rec + i];
-    return 0u;
+    if constexpr (C == Construction::kRfc8439) return 0u;
+    else return (uint8_t)((uint64_t)adlen >> (8u * (i - adlen)));
 }
 
 }  // namespace dev

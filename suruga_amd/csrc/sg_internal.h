@@ -8,6 +8,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+#include "sg_layout.h"
+
 namespace sg {
 
 constexpr uint32_t kThreads = 256;        // one record per 256-thread workgroup
@@ -46,7 +50,7 @@ constexpr uint32_t kWprRecWords = 160;
 // Record descriptor of a listed wave-per-record record (mixed batches), u32
 // words, indexed like the keying records by the record's slot in its bucket:
 //   in_off[2] out_off[2] n rec key_index n14 n15 n13 0 0
-// (n13: the nonce's first word, RecLayout::kRfc8439; 0 in the draft)
+// (n13: the nonce's first word, Construction::kRfc8439; 0 in the draft)
 constexpr uint32_t kWprDescWords = 12;
 
 // Kernel parameters (passed by value as kernarg).
@@ -78,18 +82,24 @@ struct KParams {
     uint32_t pack_mix;       // mixed batch: route eligible small records to the packed kernel (sg_pack.hip)
     // RFC 8439 record batch (sg_*_batch_rfc8439); at the end: the offsets above stay
     const uint8_t* ivs;      // TLS mode under rfc: write IVs [num_keys][12] (RFC 7905), 4-byte aligned
-    uint32_t rfc;            // 1 = RFC 8439 construction (RecLayout::kRfc8439 kernels), 0 = the draft
+    uint32_t rfc;            // 1 = RFC 8439 (Construction::kRfc8439 kernels), 0 = the draft
 };
 
-// The construction a record kernel computes, chosen at compile time (as
-// MsgLayout in sg_msg_device.h): the draft (8-byte nonce, state word 13 = 0,
-// MAC stream ad || le64(|ad|) || ct || le64(|ct|)) or RFC 8439 section 2.8
-// (12-byte nonce in words 13-15, MAC stream ad || 0.. || ct || 0.. ||
-// le64(|ad|) || le64(|ct|), every block full).  Every record kernel exists in
-// both: the size classes, the uniform 16 KiB wave-per-record launch, the J =
-// 2..4 buckets and the packed kernel, so a mixed TLS batch takes the same
-// routes (KParams.wpr_mix / pack_mix) in either construction.
-enum class RecLayout { kDraft, kRfc8439 };
+// Every record kernel exists in both constructions (Construction,
+// sg_layout.h): the size classes, the uniform 16 KiB wave-per-record launch,
+// the J = 2..4 buckets and the packed kernel, so a mixed TLS batch takes the
+// same routes (KParams.wpr_mix / pack_mix) in either.
+//
+// The launchers' one selector: calls f(OPEN, C) with the run-time pair (rfc,
+// open) as compile-time constants (OPEN.value a bool, C.value a Construction),
+// so a launcher names its kernel once, as K<OPEN.value, ..., C.value>.
+template <class F>
+inline void with_form(bool rfc, bool open, F&& f) {
+    constexpr std::integral_constant<Construction, Construction::kDraft> D{};
+    constexpr std::integral_constant<Construction, Construction::kRfc8439> R{};
+    if (rfc) open ? f(std::true_type{}, R) : f(std::false_type{}, R);
+    else open ? f(std::true_type{}, D) : f(std::false_type{}, D);
+}
 
 // Size classes of the AEAD kernel: class c (0..7) holds records of
 // n <= 128 << c bytes (class 7: the rest, up to SG_MAX_RECORD_LEN) and gives
@@ -118,12 +128,12 @@ __host__ __device__ constexpr uint32_t class_mac_lanes(uint32_t c) { return clas
 __host__ __device__ constexpr uint32_t class_max(uint32_t c) { return c < 7u ? 128u << c : 0xffffffffu; }
 // LDS bytes of one record slot: virtual-block space (16 bytes x max virtual blocks
 // 2*PL) | ad || le64 (16-rounded) | ct (64-rounded) | le64(n) + zeros
-// The RFC 8439 stream fits the same slot: its AD region 16 ceil(adlen / 16)
-// is <= 16 ceil((adlen + 8) / 16), and behind the ciphertext it writes at most
-// 15 zeros and the 16-byte length block, 31 <= 64 bytes.
+// The slot is the draft's (its ciphertext offset, 16-rounded).  The RFC 8439
+// stream fits it: its ciphertext offset is never larger, and behind the
+// ciphertext it writes at most 15 zeros and the 16-byte length block, 31 <= 64.
 __host__ __device__ inline uint32_t lds_rec_bytes(uint32_t cls, uint32_t adlen, uint32_t max_n) {
     const uint32_t PL = class_mac_lanes(cls);
-    return 32u * PL + ((adlen + 8u + 15u) & ~15u) + ((max_n + 63u) & ~63u) + 64u;
+    return 32u * PL + ((ct_offset<Construction::kDraft>(adlen) + 15u) & ~15u) + ((max_n + 63u) & ~63u) + 64u;
 }
 
 // Wave-per-record kernel (sg_wpr.hip): uniform batches of full 16 KiB TLS

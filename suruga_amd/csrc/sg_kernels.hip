@@ -32,12 +32,13 @@
 // reference's sequential Horner result bit for bit.
 //
 // The keying and AEAD kernels take the construction as a template parameter
-// (RecLayout, sg_internal.h).  RecLayout::kRfc8439 (sg_*_batch_rfc8439) differs
-// in three places: the 12-byte nonce fills state words 13-15 (record_key_rfc,
-// sg_device.h: explicit, or the RFC 7905 write IV XOR the sequence number), the
-// MAC stream is framed in LDS as ad || 0.. || ct || 0.. || le64(|ad|) ||
-// le64(|ct|), and mac_geom's stream length counts the padding (every block is
-// full).  The draft instantiations compile to what they were before the parameter.
+// (Construction, sg_layout.h).  Construction::kRfc8439 (sg_*_batch_rfc8439)
+// differs in three places: the 12-byte nonce fills state words 13-15
+// (record_key, sg_device.h: explicit, or the RFC 7905 write IV XOR the sequence
+// number), the MAC stream is framed in LDS as ad || 0.. || ct || 0.. ||
+// le64(|ad|) || le64(|ct|), and mac_geom's stream length counts the padding
+// (every block is full).  The draft instantiations compile to what they were
+// before the parameter.
 //
 // The launchers at the end are what the rest of the library sees of this file
 // (sg_internal.h); the dispatcher of a batch is sg_dispatch.cpp.
@@ -62,13 +63,17 @@ using namespace dev;
 struct MacGeom {
     uint32_t L, B, k, z;
 };
-// (RFC 8439: ad and ct are each zero-padded to 16 bytes and one block
-// le64(adlen) || le64(n) closes the stream, so every block is full)
-template <RecLayout LAY>
+// (the stream length is stream_bytes<C>, sg_layout.h; RFC 8439: every block is
+// full.  Its RFC form stays spelt with masks here: from the header's divisions
+// the compiler folds the block count below differently and the RFC kernels'
+// instructions change.)
+template <Construction C>
 __device__ __forceinline__ MacGeom mac_geom(uint32_t adlen, uint32_t n, uint32_t PL) {
     MacGeom g;
-    if constexpr (LAY == RecLayout::kRfc8439) g.L = ((adlen + 15u) & ~15u) + ((n + 15u) & ~15u) + 16u;
-    else g.L = adlen + 16u + n;
+    static_assert(stream_bytes<Construction::kRfc8439>(13u, 100u) == ((13u + 15u) & ~15u) + ((100u + 15u) & ~15u) + 16u,
+                  "the same length");
+    if constexpr (C == Construction::kRfc8439) g.L = ((adlen + 15u) & ~15u) + ((n + 15u) & ~15u) + 16u;
+    else g.L = stream_bytes<C>(adlen, n);
     g.B = (g.L + 15u) >> 4;
     g.k = (g.B + PL - 1u) / PL;
     g.k |= 1u;
@@ -112,7 +117,7 @@ __device__ __forceinline__ bool rec_pack(const KParams& p, uint32_t rec, uint32_
 // KeyJobs (sg_internal.h): njobs == 0 keys every record of the batch by
 // index; otherwise the records of up to kNumClasses lists (mixed batches key
 // only their size-class records here), job i on blocks [blk0[i], blk0[i+1]).
-template <bool OPEN, RecLayout LAY>
+template <bool OPEN, Construction C>
 __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const KeyJobs jobs) {
     constexpr uint32_t kKeyLdsStride = kKeyRecWords + 1;
     __shared__ uint32_t stage[kKeyingThreads * kKeyLdsStride];
@@ -137,7 +142,7 @@ __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const Ke
     const uint32_t n = OPEN ? (len >= 16u ? len - 16u : 0u) : len;
     out[kKeyRecWords] = 0u;  // nothing to write unless keyed below
     if (act) {
-        const RecKeyRfc rk = record_key_of<LAY>(p, rec);
+        const RecKey rk = record_key<C>(p, rec);
         uint32_t ks[16];
         chacha_block(ks, rk.k, 0u, rk.n13, rk.n14, rk.n15);  // block 0 -> poly key (chacha20_poly1305.rs:50)
         const PolyKey pk = poly_key(ks);
@@ -150,7 +155,7 @@ __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const Ke
         out[kSOff + 2] = pk.s[2];
         out[kSOff + 3] = pk.s[3];
         const uint32_t adlen = p.tls ? 13u : p.ad_len;
-        const MacGeom g = mac_geom<LAY>(adlen, n, mac_lanes(n));
+        const MacGeom g = mac_geom<C>(adlen, n, mac_lanes(n));
         const F26 r = words_to_f26(pk.r0, pk.r1, pk.r2, pk.r3, 0u);
         // R = r^k by square-and-multiply; then R^0..R^7 and R^0, R^8, .., R^56.
         // mul_add outputs are valid multipliers as they stand (limb 1 may exceed
@@ -199,7 +204,7 @@ __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const Ke
 // otherwise); PL = min(L, 64) of them run the MAC.  Per record, in LDS:
 //   [0, S) virtual-block space | S: ad | le64(adlen) | A: ct (n) | le64(n) | zeros
 // ---------------------------------------------------------------------------
-template <bool OPEN, uint32_t L, RecLayout LAY>
+template <bool OPEN, uint32_t L, Construction C>
 __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec, const bool active,
                                             uint8_t* lds, const uint32_t t) {
     constexpr uint32_t PL = L < 64u ? L : 64u;
@@ -219,17 +224,22 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
     }
     const uint8_t* in = nullptr;
     uint8_t* out = nullptr;
-    constexpr bool RFC = LAY == RecLayout::kRfc8439;
-    RecKeyRfc rk = {};
+    constexpr bool RFC = C == Construction::kRfc8439;
+    RecKey rk = {};
     const uint32_t adlen = p.tls ? 13u : p.ad_len;
     // RFC 8439: [Z, A) ad and its zero padding | A: ct (n) | zeros to 16 | le64(adlen) le64(n)
+    // A = Z + 16 ceil(ct_offset<C>(adlen) / 16) and S = A - ct_offset<C>(adlen) (sg_layout.h), spelt by
+    // hand: taken from the header, 76 of this file's 102 kernels came out with other instructions
+    static_assert(ct_offset<Construction::kRfc8439>(13u) == ((13u + 15u) & ~15u) &&
+                      ct_offset<Construction::kRfc8439>(32u) == 32u && ct_offset<Construction::kDraft>(13u) == 13u + 8u,
+                  "the offsets below are the header's");
     const uint32_t A = Z + (RFC ? (adlen + 15u) & ~15u : (adlen + 8u + 15u) & ~15u);
     const uint32_t S = RFC ? Z : A - adlen - 8u;  // stream start, >= Z
     uint8_t* ct_lds = lds + A;
     if (work) {
         in = p.in + rec_in_off(p, rec);
         out = p.out + rec_out_off(p, rec);
-        rk = record_key_of<LAY>(p, rec);
+        rk = record_key<C>(p, rec);
 
         // ---- phase 1: keystream XOR, 64 bytes per lane-block ----------------
         const bool vec_ok = (((uintptr_t)in | (uintptr_t)out) & 15u) == 0u;
@@ -319,7 +329,7 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
     if (!work || t >= PL) return;
 
     // ---- phase 2: Poly1305 on PL lanes -----------------------------------------
-    const MacGeom g = mac_geom<LAY>(adlen, n, PL);
+    const MacGeom g = mac_geom<C>(adlen, n, PL);
     const uint32_t* kr = p.ws + (uint64_t)rec * kKeyRecWords;
     uint32_t r0 = kr[kR32Off + 0], r1 = kr[kR32Off + 1], r2 = kr[kR32Off + 2], r3 = kr[kR32Off + 3];
     if constexpr (PL == 64u) {  // one record per wave: keep the key in SGPRs
@@ -479,13 +489,13 @@ __device__ __forceinline__ uint32_t group_of_thread() {
 }
 
 // Direct launch: workgroup w serves records w*RPW .. w*RPW + RPW - 1.
-template <bool OPEN, uint32_t L, RecLayout LAY>
+template <bool OPEN, uint32_t L, Construction C>
 __global__ __launch_bounds__(256) void sg_aead_kernel(const KParams p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     constexpr uint32_t RPW = 256u / L;
     const uint32_t g = group_of_thread<L>(), t = threadIdx.x % L;
     const uint32_t rec = blockIdx.x * RPW + g;
-    aead_record<OPEN, L, LAY>(p, rec, rec < p.count, lds + g * p.lds_rec_bytes, t);
+    aead_record<OPEN, L, C>(p, rec, rec < p.count, lds + g * p.lds_rec_bytes, t);
 }
 
 // Bucketed launch: records listed by sg_classify_kernel for this size class.
@@ -495,7 +505,7 @@ __global__ __launch_bounds__(256) void sg_aead_kernel(const KParams p) {
 // MAC).  PERSIST = true (stream capture, where the host cannot wait): a fixed
 // grid walks the list; the barrier closing each iteration makes waves 1-3
 // wait for wave 0's MAC, ~30 % slower per byte (tools/exp_list.py).
-template <bool OPEN, uint32_t L, bool PERSIST, RecLayout LAY>
+template <bool OPEN, uint32_t L, bool PERSIST, Construction C>
 __global__ __launch_bounds__(256) void sg_aead_list_kernel(const KParams p, const uint32_t* __restrict__ list,
                                                            const uint32_t* __restrict__ list_count) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -513,7 +523,7 @@ __global__ __launch_bounds__(256) void sg_aead_list_kernel(const KParams p, cons
         const bool active = slot < cnt;
         uint32_t rec = active ? list[slot] : 0u;
         if constexpr (L >= 64u) rec = __builtin_amdgcn_readfirstlane(rec);
-        aead_record<OPEN, L, LAY>(p, rec, active, lds + g * p.lds_rec_bytes, t);
+        aead_record<OPEN, L, C>(p, rec, active, lds + g * p.lds_rec_bytes, t);
         if constexpr (!PERSIST) break;
         __syncthreads();  // LDS is reused by the next iteration
     }
@@ -586,10 +596,9 @@ __global__ __launch_bounds__(1024) void sg_classify_kernel(const KParams p, uint
 
 hipError_t launch_keying(const KParams& p, bool open, const KeyJobs& jobs, uint32_t grid, hipStream_t s) {
     if (grid == 0) return hipSuccess;
-    constexpr RecLayout D = RecLayout::kDraft, R = RecLayout::kRfc8439;
-    const auto kernel = p.rfc ? (open ? sg_keying_kernel<true, R> : sg_keying_kernel<false, R>)
-                              : (open ? sg_keying_kernel<true, D> : sg_keying_kernel<false, D>);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kKeyingThreads), 0, s, p, jobs);
+    with_form(p.rfc, open, [&](auto OPEN, auto C) {
+        hipLaunchKernelGGL((sg_keying_kernel<OPEN.value, C.value>), dim3(grid), dim3(kKeyingThreads), 0, s, p, jobs);
+    });
     return hipGetLastError();
 }
 
@@ -614,10 +623,10 @@ template <uint32_t L>
 static hipError_t launch_direct(const KParams& p, bool open, hipStream_t s) {
     constexpr uint32_t RPW = 256u / L;
     const uint32_t grid = (p.count + RPW - 1u) / RPW;
-    constexpr RecLayout D = RecLayout::kDraft, R = RecLayout::kRfc8439;
-    const auto kernel = p.rfc ? (open ? sg_aead_kernel<true, L, R> : sg_aead_kernel<false, L, R>)
-                              : (open ? sg_aead_kernel<true, L, D> : sg_aead_kernel<false, L, D>);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), RPW * p.lds_rec_bytes, s, p);
+    with_form(p.rfc, open, [&](auto OPEN, auto C) {
+        const size_t lds = RPW * p.lds_rec_bytes;
+        hipLaunchKernelGGL((sg_aead_kernel<OPEN.value, L, C.value>), dim3(grid), dim3(kThreads), lds, s, p);
+    });
     return hipGetLastError();
 }
 
@@ -628,22 +637,17 @@ static hipError_t launch_list(const KParams& p, bool open, const uint32_t* list,
                               hipStream_t s) {
     constexpr uint32_t RPW = 256u / L;
     const size_t lds = RPW * p.lds_rec_bytes;
-    constexpr RecLayout D = RecLayout::kDraft, R = RecLayout::kRfc8439;
-    if (n_exact != 0xffffffffu) {
-        if (n_exact == 0) return hipSuccess;
-        const auto kernel =
-            p.rfc ? (open ? sg_aead_list_kernel<true, L, false, R> : sg_aead_list_kernel<false, L, false, R>)
-                  : (open ? sg_aead_list_kernel<true, L, false, D> : sg_aead_list_kernel<false, L, false, D>);
-        hipLaunchKernelGGL(kernel, dim3((n_exact + RPW - 1u) / RPW), dim3(kThreads), lds, s, p, list, cnt);
-        return hipGetLastError();
-    }
-    uint32_t grid = (p.count + RPW - 1u) / RPW;
+    if (n_exact == 0) return hipSuccess;
+    const bool persist = n_exact == 0xffffffffu;
+    uint32_t grid = ((persist ? p.count : n_exact) + RPW - 1u) / RPW;
     const uint32_t cap = kListGridPerCU * 256u;
-    if (grid > cap) grid = cap;
-    const auto kernel =
-        p.rfc ? (open ? sg_aead_list_kernel<true, L, true, R> : sg_aead_list_kernel<false, L, true, R>)
-              : (open ? sg_aead_list_kernel<true, L, true, D> : sg_aead_list_kernel<false, L, true, D>);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, s, p, list, cnt);
+    if (persist && grid > cap) grid = cap;
+    with_form(p.rfc, open, [&](auto OPEN, auto C) {
+        const dim3 g(grid), b(kThreads);
+        constexpr bool O = OPEN.value;
+        if (persist) hipLaunchKernelGGL((sg_aead_list_kernel<O, L, true, C.value>), g, b, lds, s, p, list, cnt);
+        else hipLaunchKernelGGL((sg_aead_list_kernel<O, L, false, C.value>), g, b, lds, s, p, list, cnt);
+    });
     return hipGetLastError();
 }
 

@@ -1,0 +1,57 @@
+// sg_layout.h -- the two AEAD constructions of the library and the geometry of
+// their MAC streams, in one place for the record kernels (sg_kernels.hip,
+// sg_wpr.hip, sg_pack.hip), the message kernels (sg_msg_device.h) and the
+// host-side plan (sg_msg_plan.h).  No HIP: plain constexpr functions, which
+// hipcc takes as host and device code, so the host-only programs include it too.
+// Not part of the public ABI.
+#pragma once
+
+#include <stdint.h>
+
+namespace sg {
+
+// The construction, a compile-time parameter of every kernel that differs:
+//   kDraft    draft-agl-tls-chacha20poly1305-04 as in klutzy/suruga
+//             (chacha20_poly1305.rs:19-42): 8-byte nonce in state words 14-15,
+//             word 13 = 0; MAC stream ad || le64(adlen) || ct || le64(n), no padding
+//   kRfc8439  RFC 8439 section 2.8: 12-byte nonce in state words 13-15; MAC
+//             stream ad || zeros to 16 || ct || zeros to 16 || le64(adlen) ||
+//             le64(n), every block full
+// KParams.rfc, SG_MSG_RFC8439 and the *_rfc8439 calls select it at run time;
+// with_form (sg_internal.h) turns that into the template argument.
+enum class Construction { kDraft, kRfc8439 };
+
+template <Construction C>
+constexpr uint32_t nonce_len() {
+    return C == Construction::kRfc8439 ? 12u : 8u;
+}
+
+// Stream offset of the ciphertext and length of the stream for adlen AD bytes
+// and n data bytes, in the caller's integer type (the record kernels count in
+// uint32_t, the message kernels in int64_t, the plan in uint64_t).
+template <Construction C, class T>
+constexpr T ct_offset(T adlen) {
+    return C == Construction::kRfc8439 ? (adlen + 15) / 16 * 16 : adlen + 8;
+}
+template <Construction C, class T>
+constexpr T stream_bytes(T adlen, T n) {
+    return C == Construction::kRfc8439 ? ct_offset<C>(adlen) + (n + 15) / 16 * 16 + 16 : ct_offset<C>(adlen) + n + 8;
+}
+
+// chacha20_poly1305.rs:19-42: the TLS record's 13 AD bytes and its le64, then
+// the data and its le64 -- nothing rounded
+static_assert(nonce_len<Construction::kDraft>() == 8u, "draft nonce");
+static_assert(ct_offset<Construction::kDraft>(13u) == 21u && ct_offset<Construction::kDraft>(0u) == 8u, "draft");
+static_assert(stream_bytes<Construction::kDraft>(13u, 16384u) == 16413u, "draft: 13 + 8 + n + 8");
+static_assert(stream_bytes<Construction::kDraft>(0u, 0u) == 16u, "draft: the two lengths alone");
+static_assert(stream_bytes<Construction::kDraft, int64_t>(12, 114) == 142, "draft, signed");
+// RFC 8439 section 2.8.2: 12 AD bytes (padded to 16), 114 data bytes (padded
+// to 128), one length block: the 160 bytes of its "Poly1305 message"
+static_assert(nonce_len<Construction::kRfc8439>() == 12u, "RFC 8439 nonce");
+static_assert(ct_offset<Construction::kRfc8439>(12u) == 16u && ct_offset<Construction::kRfc8439>(0u) == 0u, "RFC 8439");
+static_assert(ct_offset<Construction::kRfc8439>(13u) == 16u && ct_offset<Construction::kRfc8439>(17u) == 32u, "RFC 8439");
+static_assert(stream_bytes<Construction::kRfc8439>(12u, 114u) == 160u, "RFC 8439 section 2.8.2");
+static_assert(stream_bytes<Construction::kRfc8439>(0u, 0u) == 16u, "RFC 8439: the length block alone");
+static_assert(stream_bytes<Construction::kRfc8439, int64_t>(13, 16384) == 16416, "RFC 7905 record, signed");
+
+}  // namespace sg

@@ -1,7 +1,7 @@
 // sg_msg.hip -- gfx950 kernels of the long-message path: one message (one key,
 // one nonce, n data bytes, adlen AD bytes, any lengths up to SG_MSG_MAX_LEN)
 // sealed or opened by a persistent grid over the whole chip.  Two
-// constructions, chosen at compile time by the MsgLayout parameter:
+// constructions, chosen at compile time by the Construction parameter:
 //   * the draft, as every other path of the library
 //     (chacha20_poly1305.rs:19-94): 8-byte nonce, Poly1305 key = keystream
 //     block 0, data byte i XORed with keystream block 1 + i / 64, counter in
@@ -68,36 +68,36 @@ struct MsgParams {
 
 namespace {
 
-template <bool OPEN, MsgLayout LAY>
+template <bool OPEN, Construction C>
 __global__ __launch_bounds__(256) void sg_msg_kernel(const MsgParams p) {
     __shared__ __attribute__((aligned(64))) uint8_t lds[kLdsBytes];
     const uint32_t lane = threadIdx.x;
-    const uint32_t n13 = LAY == MsgLayout::kRfc8439 ? p.n13 : 0u;
+    const uint32_t n13 = C == Construction::kRfc8439 ? p.n13 : 0u;
     const MsgKey mk = msg_key(p.key, n13, p.n14, p.n15);
     const MsgR rr = msg_r(mk);
     const F26 r = words_to_f26(mk.r0, mk.r1, mk.r2, mk.r3, 0u);
     const F26 R = fpow(r, p.plan.tile_blocks);
     const F26 Pl = msg_lane_power(r, lane);
     const ChaChaPre pre = chacha_pre(mk.k, n13, p.n14, p.n15);
-    const MsgStream m = msg_stream<LAY>(p.ad, p.in, p.out, n13, p.n14, p.n15, p.n, p.adlen, p.plan.mac_blocks,
-                                        p.plan.zero_blocks, p.plan.tile_blocks, p.plan.tile_bytes);
+    const MsgStream m = msg_stream<C>(p.ad, p.in, p.out, n13, p.n14, p.n15, p.n, p.adlen, p.plan.mac_blocks,
+                                      p.plan.zero_blocks, p.plan.tile_blocks, p.plan.tile_bytes);
 
     const uint64_t t0 = (uint64_t)blockIdx.x * p.plan.tiles_per_group;
     uint64_t t1 = t0 + p.plan.tiles_per_group;
     if (t1 > p.plan.tiles) t1 = p.plan.tiles;
 
     F26 acc = f26_zero();
-    for (uint64_t t = t0; t < t1; ++t) msg_tile<OPEN, LAY>(lds, lane, m, mk, pre, rr, R, t, acc);
+    for (uint64_t t = t0; t < t1; ++t) msg_tile<OPEN, C>(lds, lane, m, mk, pre, rr, R, t, acc);
     // ---- the group's partial: sum of the lanes' chains, each at its place in a tile
     const F26 Hg = block_sum(fmul(acc, Pl), reinterpret_cast<uint32_t*>(lds), lane);
     if (lane == 0u) store_f26(p.ws + (uint64_t)blockIdx.x * kMsgPartialWords, Hg);
 }
 
-template <bool OPEN, MsgLayout LAY>
+template <bool OPEN, Construction C>
 __global__ __launch_bounds__(256) void sg_msg_finish_kernel(const MsgParams p) {
     __shared__ uint32_t red[5u * (256u + 16u)];
     const uint32_t lane = threadIdx.x;
-    const MsgKey mk = msg_key(p.key, LAY == MsgLayout::kRfc8439 ? p.n13 : 0u, p.n14, p.n15);
+    const MsgKey mk = msg_key(p.key, C == Construction::kRfc8439 ? p.n13 : 0u, p.n14, p.n15);
     const F26 R = fpow(words_to_f26(mk.r0, mk.r1, mk.r2, mk.r3, 0u), p.plan.tile_blocks);
     F26 sum = f26_zero();
     for (uint32_t g = lane; g < p.plan.groups; g += 256u) {  // <= 4 terms per lane
@@ -116,27 +116,6 @@ __global__ __launch_bounds__(256) void sg_msg_finish_kernel(const MsgParams p) {
 __global__ __launch_bounds__(256) void sg_msg_scrub_kernel(uint8_t* out, const uint64_t n, const uint8_t* status) {
     if (*status == 0u) return;
     msg_zero(out, n, (uint64_t)blockIdx.x * 256u + threadIdx.x, (uint64_t)gridDim.x * 256u);
-}
-
-}  // namespace
-
-namespace {
-
-template <MsgLayout LAY>
-void launch_msg_kernels(const MsgParams& p, bool open, bool scrub, hipStream_t s) {
-    const sg_msg_plan& plan = p.plan;
-    if (open) {
-        hipLaunchKernelGGL((sg_msg_kernel<true, LAY>), dim3(plan.groups), dim3(kMsgThreads), 0, s, p);
-        hipLaunchKernelGGL((sg_msg_finish_kernel<true, LAY>), dim3(1), dim3(256), 0, s, p);
-        if (scrub && p.n) {
-            const uint64_t blocks = (p.n / 16u + 1023u) / 1024u;
-            const uint32_t grid = blocks < 1u ? 1u : (blocks > 4096u ? 4096u : (uint32_t)blocks);
-            hipLaunchKernelGGL(sg_msg_scrub_kernel, dim3(grid), dim3(256), 0, s, p.out, p.n, (const uint8_t*)p.status);
-        }
-    } else {
-        hipLaunchKernelGGL((sg_msg_kernel<false, LAY>), dim3(plan.groups), dim3(kMsgThreads), 0, s, p);
-        hipLaunchKernelGGL((sg_msg_finish_kernel<false, LAY>), dim3(1), dim3(256), 0, s, p);
-    }
 }
 
 }  // namespace
@@ -162,10 +141,15 @@ hipError_t launch_msg(const uint8_t* key, const uint8_t nonce[8], const uint8_t*
     p.n14 = dev::le32(nonce);
     p.n15 = dev::le32(nonce + 4);
     p.plan = plan;
-    if (nonce_hi)
-        launch_msg_kernels<MsgLayout::kRfc8439>(p, open, scrub, s);
-    else
-        launch_msg_kernels<MsgLayout::kDraft>(p, open, scrub, s);
+    with_form(nonce_hi != nullptr, open, [&](auto OPEN, auto C) {
+        hipLaunchKernelGGL((sg_msg_kernel<OPEN.value, C.value>), dim3(plan.groups), dim3(kMsgThreads), 0, s, p);
+        hipLaunchKernelGGL((sg_msg_finish_kernel<OPEN.value, C.value>), dim3(1), dim3(256), 0, s, p);
+    });
+    if (open && scrub && n) {
+        const uint64_t blocks = (n / 16u + 1023u) / 1024u;
+        const uint32_t grid = blocks < 1u ? 1u : (blocks > 4096u ? 4096u : (uint32_t)blocks);
+        hipLaunchKernelGGL(sg_msg_scrub_kernel, dim3(grid), dim3(256), 0, s, out, n, (const uint8_t*)status);
+    }
     return hipGetLastError();
 }
 

@@ -55,17 +55,17 @@ __device__ __forceinline__ T* uload(T* const* p) {
 }
 
 // data bytes [d0, d1) of tiles [a, b) of a message: the tile body's own cut
-template <MsgLayout LAY>
+template <Construction C>
 __device__ __forceinline__ void seg_data_range(const uint64_t zero_blocks, const uint64_t n, const uint64_t adlen,
                                                const uint32_t a, const uint32_t b, int64_t* d0, int64_t* d1) {
-    const int64_t P = msg_ct_offset<LAY>((int64_t)adlen);
+    const int64_t P = ct_offset<C>((int64_t)adlen);
     const int64_t s0 = (int64_t)a * (int64_t)kMsgTileBytes - 16 * (int64_t)zero_blocks;
     const int64_t s1 = (int64_t)b * (int64_t)kMsgTileBytes - 16 * (int64_t)zero_blocks;
     *d0 = s0 - P > 0 ? s0 - P : 0;
     *d1 = s1 - P < (int64_t)n ? s1 - P : (int64_t)n;
 }
 
-template <bool OPEN, MsgLayout LAY>
+template <bool OPEN, Construction C>
 __global__ __launch_bounds__(256) void sg_msg_batch_kernel(const MsgBatchParams p) {
     __shared__ __attribute__((aligned(64))) uint8_t lds[kLdsBytes];
     const uint32_t lane = threadIdx.x;
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void sg_msg_batch_kernel(const MsgBatchParams 
         const MsgBatchItem* it = p.items + mi;
         if (uload(&it->skip) != 0u) continue;  // an open of fewer than 16 bytes: nothing is touched
         const uint32_t n14 = uload(&it->n14), n15 = uload(&it->n15);
-        const uint32_t n13 = LAY == MsgLayout::kRfc8439 ? uload(&it->n13) : 0u;
+        const uint32_t n13 = C == Construction::kRfc8439 ? uload(&it->n13) : 0u;
         // ---- the message's keying, as sg_msg_kernel's
         const MsgKey mk = msg_key(uload(&it->key), n13, n14, n15);
         const MsgR rr = msg_r(mk);
@@ -87,11 +87,11 @@ __global__ __launch_bounds__(256) void sg_msg_batch_kernel(const MsgBatchParams 
         const F26 Pl = msg_lane_power(r, lane);
         const ChaChaPre pre = chacha_pre(mk.k, n13, n14, n15);
         const sg_msg_plan* pl = p.plans + mi;
-        const MsgStream m = msg_stream<LAY>(uload(&it->ad), uload(&it->in), uload(&it->out), n13, n14, n15,
-                                            uload(&it->n), uload(&it->adlen), uload(&pl->mac_blocks),
-                                            uload(&pl->zero_blocks), kMsgTileBlocks, kMsgTileBytes);
+        const MsgStream m = msg_stream<C>(uload(&it->ad), uload(&it->in), uload(&it->out), n13, n14, n15,
+                                          uload(&it->n), uload(&it->adlen), uload(&pl->mac_blocks),
+                                          uload(&pl->zero_blocks), kMsgTileBlocks, kMsgTileBytes);
         F26 acc = f26_zero();
-        for (uint64_t t = ta; t < tb; ++t) msg_tile<OPEN, LAY>(lds, lane, m, mk, pre, rr, R, t, acc);
+        for (uint64_t t = ta; t < tb; ++t) msg_tile<OPEN, C>(lds, lane, m, mk, pre, rr, R, t, acc);
         // ---- the segment's partial: sum of the lanes' chains, each at its place in a tile
         const F26 Hs = block_sum(fmul(acc, Pl), reinterpret_cast<uint32_t*>(lds), lane);
         if (lane == 0u) store_f26(p.partials + (uint64_t)sgi * kMsgPartialWords, Hs);
@@ -120,7 +120,7 @@ __device__ __forceinline__ F26 wave_sum(const F26 x, uint32_t* red, const uint32
 
 constexpr uint32_t kFinishWaves = 4;  // messages per workgroup of the finish kernel
 
-template <bool OPEN, MsgLayout LAY>
+template <bool OPEN, Construction C>
 __global__ __launch_bounds__(256) void sg_msg_batch_finish_kernel(const MsgBatchParams p) {
     __shared__ uint32_t red[kFinishWaves][5u * (64u + 4u)];
     const uint32_t wave = threadIdx.x >> 6, wl = threadIdx.x & 63u;
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void sg_msg_batch_finish_kernel(const MsgBatch
             if (wl == 0u) p.status[mi] = (uint8_t)SG_E_SHORT;  // chacha20_poly1305.rs:68-70
         return;
     }
-    const MsgKey mk = msg_key(uload(&it->key), LAY == MsgLayout::kRfc8439 ? uload(&it->n13) : 0u, uload(&it->n14),
+    const MsgKey mk = msg_key(uload(&it->key), C == Construction::kRfc8439 ? uload(&it->n13) : 0u, uload(&it->n14),
                               uload(&it->n15));
     const F26 R = fpow(words_to_f26(mk.r0, mk.r1, mk.r2, mk.r3, 0u), kMsgTileBlocks);
     const uint32_t tiles = (uint32_t)uload(&p.plans[mi].tiles);  // < 2^30
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void sg_msg_batch_finish_kernel(const MsgBatch
 // A failed open hands out no plaintext (chacha20_poly1305.rs:89-93): the grid
 // of the batch kernel again, every segment zeroing its own data bytes of a
 // message whose status says SG_E_BAD_MAC.
-template <MsgLayout LAY>
+template <Construction C>
 __global__ __launch_bounds__(256) void sg_msg_batch_scrub_kernel(const MsgBatchParams p) {
     const uint32_t first = uload(&p.group_segs[blockIdx.x].first);
     const uint32_t end = first + uload(&p.group_segs[blockIdx.x].count);
@@ -163,22 +163,9 @@ __global__ __launch_bounds__(256) void sg_msg_batch_scrub_kernel(const MsgBatchP
         const MsgBatchItem* it = p.items + mi;
         const uint64_t n = uload(&it->n);
         int64_t d0, d1;
-        seg_data_range<LAY>(uload(&p.plans[mi].zero_blocks), n, uload(&it->adlen), uload(&sg->tile_begin),
-                            uload(&sg->tile_end), &d0, &d1);
+        seg_data_range<C>(uload(&p.plans[mi].zero_blocks), n, uload(&it->adlen), uload(&sg->tile_begin),
+                          uload(&sg->tile_end), &d0, &d1);
         if (d1 > d0) msg_zero(uload(&it->out) + d0, (uint64_t)(d1 - d0), threadIdx.x, 256u);
-    }
-}
-
-template <MsgLayout LAY>
-void launch_msg_batch_kernels(const MsgBatchParams& p, uint32_t groups, bool open, bool scrub, hipStream_t s) {
-    const dim3 fin((p.count + kFinishWaves - 1u) / kFinishWaves);
-    if (open) {
-        hipLaunchKernelGGL((sg_msg_batch_kernel<true, LAY>), dim3(groups), dim3(kMsgThreads), 0, s, p);
-        hipLaunchKernelGGL((sg_msg_batch_finish_kernel<true, LAY>), fin, dim3(256), 0, s, p);
-        if (scrub) hipLaunchKernelGGL(sg_msg_batch_scrub_kernel<LAY>, dim3(groups), dim3(256), 0, s, p);
-    } else {
-        hipLaunchKernelGGL((sg_msg_batch_kernel<false, LAY>), dim3(groups), dim3(kMsgThreads), 0, s, p);
-        hipLaunchKernelGGL((sg_msg_batch_finish_kernel<false, LAY>), fin, dim3(256), 0, s, p);
     }
 }
 
@@ -199,10 +186,13 @@ hipError_t launch_msg_batch(const MsgBatchLayout& l, void* ws, uint32_t count, u
     p.partials = (uint32_t*)(w + l.partials);
     p.status = status;
     p.count = count;
-    if (rfc8439)
-        launch_msg_batch_kernels<MsgLayout::kRfc8439>(p, groups, open, scrub, s);
-    else
-        launch_msg_batch_kernels<MsgLayout::kDraft>(p, groups, open, scrub, s);
+    const dim3 fin((count + kFinishWaves - 1u) / kFinishWaves);
+    with_form(rfc8439, open, [&](auto OPEN, auto C) {
+        hipLaunchKernelGGL((sg_msg_batch_kernel<OPEN.value, C.value>), dim3(groups), dim3(kMsgThreads), 0, s, p);
+        hipLaunchKernelGGL((sg_msg_batch_finish_kernel<OPEN.value, C.value>), fin, dim3(256), 0, s, p);
+        if (OPEN.value && scrub)
+            hipLaunchKernelGGL(sg_msg_batch_scrub_kernel<C.value>, dim3(groups), dim3(256), 0, s, p);
+    });
     return hipGetLastError();
 }
 

@@ -15,6 +15,7 @@
 #include "../../include/suruga_gpu.h"
 #include "sg_host.h"
 #include "sg_msg_plan.h"
+#include "sg_wire.h"
 
 // nonce_hi lies in what was padding: every size and offset is the one the
 // header compiled to before the field existed
@@ -115,20 +116,10 @@ int run_msg_batch(const sg_msg_batch* b, bool open) {
     for (uint32_t i = 0; i < count; ++i) {
         const sg_msg_item& m = b->items[i];
         if (m.key_index >= b->num_keys) return fail(SG_E_ARG, "key_index out of range%s");
-        const bool shrt = open && m.in_len < SG_MAC_LEN;  // chacha20_poly1305.rs:68-70, reported per message
-        n[i] = shrt ? 0u : (open ? m.in_len - SG_MAC_LEN : m.in_len);
+        bool shrt;  // reported per message (the finish kernel), not by the call
+        const sg::MsgArgs a = {b->keys, m.ad, m.ad_len, m.in, m.in_len, m.out, b->status};
+        if (const char* bad = sg::msg_check_args(a, open, &n[i], &shrt)) return fail(SG_E_ARG, bad);
         adlen[i] = shrt ? 0u : m.ad_len;
-        if (shrt) continue;
-        if (n[i] > SG_MSG_MAX_LEN) return fail(SG_E_ARG, "message longer than SG_MSG_MAX_LEN%s");
-        if (m.ad_len > SG_MSG_MAX_LEN) return fail(SG_E_ARG, "ad_len exceeds SG_MSG_MAX_LEN%s");
-        const uint64_t out_len = open ? n[i] : n[i] + SG_MAC_LEN;
-        if ((m.in_len && !m.in) || (out_len && !m.out) || (m.ad_len && !m.ad))
-            return fail(SG_E_ARG, "in/out/ad must be non-NULL%s");
-        if (m.in != m.out && m.in_len && out_len) {
-            const uintptr_t x = (uintptr_t)m.in, y = (uintptr_t)m.out;
-            if (x < y + out_len && y < x + m.in_len)
-                return fail(SG_E_ARG, "out overlaps in (only out == in is allowed)%s");
-        }
     }
 
     // ---- from here on the GPU is touched
@@ -162,12 +153,10 @@ int run_msg_batch(const sg_msg_batch* b, bool open) {
         d.adlen = adlen[i];
         // the nonce as little-endian words (chacha20.rs:45-46); RFC 8439
         // (section 2.3): nonce_hi in front of them, in state word 13
-        d.n14 = (uint32_t)m.nonce[0] | (uint32_t)m.nonce[1] << 8 | (uint32_t)m.nonce[2] << 16 | (uint32_t)m.nonce[3] << 24;
-        d.n15 = (uint32_t)m.nonce[4] | (uint32_t)m.nonce[5] << 8 | (uint32_t)m.nonce[6] << 16 | (uint32_t)m.nonce[7] << 24;
+        d.n14 = sg::get_le32(m.nonce);
+        d.n15 = sg::get_le32(m.nonce + 4);
         d.skip = open && m.in_len < SG_MAC_LEN ? 1u : 0u;
-        d.n13 = rfc ? (uint32_t)m.nonce_hi[0] | (uint32_t)m.nonce_hi[1] << 8 | (uint32_t)m.nonce_hi[2] << 16 |
-                          (uint32_t)m.nonce_hi[3] << 24
-                    : 0u;
+        d.n13 = rfc ? sg::get_le32(m.nonce_hi) : 0u;
     }
     sg_msg_batch_plan plan;
     rc = sg_msg_batch_plan_for_flags(n, adlen, count, b->flags & SG_MSG_RFC8439, (uint32_t)sg::msg_groups(), &plan,

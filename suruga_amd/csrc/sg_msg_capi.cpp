@@ -36,20 +36,11 @@ int run_msg(const sg_msg* m, bool open) {
     if (!m) return fail(SG_E_ARG, "message is NULL%s");
     if (m->flags & ~sg::kMsgKnownFlags) return fail(SG_E_ARG, "unknown flags%s");
     const bool rfc = (m->flags & SG_MSG_RFC8439) != 0u;  // else nonce_hi is never read
-    if (open && m->in_len < SG_MAC_LEN) return SG_E_SHORT;  // chacha20_poly1305.rs:68-70
-    const uint64_t n = open ? m->in_len - SG_MAC_LEN : m->in_len;
-    if (n > SG_MSG_MAX_LEN) return fail(SG_E_ARG, "message longer than SG_MSG_MAX_LEN%s");
-    if (m->ad_len > SG_MSG_MAX_LEN) return fail(SG_E_ARG, "ad_len exceeds SG_MSG_MAX_LEN%s");
-    const uint64_t out_len = open ? n : n + SG_MAC_LEN;
-    if (!m->key) return fail(SG_E_ARG, "key must be non-NULL%s");
-    if ((m->in_len && !m->in) || (out_len && !m->out) || (m->ad_len && !m->ad))
-        return fail(SG_E_ARG, "in/out/ad must be non-NULL%s");
-    if (open && !m->status) return fail(SG_E_ARG, "open requires a status byte%s");
-    if (m->in != m->out && m->in_len && out_len) {
-        const uintptr_t a = (uintptr_t)m->in, b = (uintptr_t)m->out;
-        if (a < b + out_len && b < a + m->in_len)
-            return fail(SG_E_ARG, "out overlaps in (only out == in is allowed)%s");
-    }
+    uint64_t n;
+    bool shrt;
+    const sg::MsgArgs a = {m->key, m->ad, m->ad_len, m->in, m->in_len, m->out, m->status};
+    if (const char* bad = sg::msg_check_args(a, open, &n, &shrt)) return fail(SG_E_ARG, bad);
+    if (shrt) return SG_E_SHORT;
     sg_msg_plan plan;
     if (sg_msg_plan_for_flags(n, m->ad_len, m->flags & SG_MSG_RFC8439, (uint32_t)sg::msg_groups(), &plan) != SG_OK)
         return fail(SG_E_ARG, "no plan for the message%s");

@@ -15,24 +15,10 @@ namespace {
 
 using namespace dev;
 
-// The MAC stream's layout, a compile-time parameter of the tile body and of
-// the kernels built on it:
-//   kDraft    ad || le64(adlen) || ct || le64(n), no padding
-//             (chacha20_poly1305.rs:19-42); state word 13 is 0
-//   kRfc8439  ad || zeros to 16 || ct || zeros to 16 || le64(adlen) || le64(n)
-//             (RFC 8439 section 2.8); state word 13 is the first nonce word
-// The ciphertext starts at stream offset P and the stream is L bytes long.
-enum class MsgLayout { kDraft, kRfc8439 };
-
-template <MsgLayout LAY>
-__host__ __device__ constexpr int64_t msg_ct_offset(int64_t adlen) {
-    return LAY == MsgLayout::kRfc8439 ? (adlen + 15) / 16 * 16 : adlen + 8;
-}
-template <MsgLayout LAY>
-__host__ __device__ constexpr int64_t msg_stream_bytes(int64_t adlen, int64_t n) {
-    return LAY == MsgLayout::kRfc8439 ? msg_ct_offset<LAY>(adlen) + (n + 15) / 16 * 16 + 16
-                                      : msg_ct_offset<LAY>(adlen) + n + 8;
-}
+// The construction (Construction, sg_layout.h) is a compile-time parameter of
+// the tile body and of the kernels built on it: the ciphertext starts at stream
+// offset P = ct_offset<C>(adlen) and the stream is L = stream_bytes<C>(adlen, n)
+// bytes long, counted in int64_t here.
 
 // tile bytes at [kLdsFront + A, + kMsgTileBytes), A = (s0 - P) & 63 < 64; the
 // 16-byte chunks the tile's edges cut are stored whole: up to 15 bytes before
@@ -103,7 +89,7 @@ struct MsgStream {
     uint32_t rem;    // its bytes, 1..16
 };
 
-template <MsgLayout LAY>
+template <Construction C>
 __device__ __forceinline__ MsgStream msg_stream(const uint8_t* ad, const uint8_t* in, uint8_t* out, uint32_t n13,
                                                 uint32_t n14, uint32_t n15, uint64_t n, uint64_t adlen,
                                                 uint64_t mac_blocks, uint64_t zero_blocks, uint32_t tile_blocks,
@@ -117,8 +103,8 @@ __device__ __forceinline__ MsgStream msg_stream(const uint8_t* ad, const uint8_t
     m.n15 = n15;
     m.n = (int64_t)n;
     m.adlen = (int64_t)adlen;
-    m.P = msg_ct_offset<LAY>(m.adlen);
-    m.L = msg_stream_bytes<LAY>(m.adlen, m.n);
+    m.P = ct_offset<C>(m.adlen);
+    m.L = stream_bytes<C>(m.adlen, m.n);
     m.TB = (int64_t)tile_bytes;
     m.tile_blocks = tile_blocks;
     m.z = zero_blocks;
@@ -140,7 +126,7 @@ __device__ __forceinline__ MsgR msg_r(const MsgKey& mk) {
 // MAC stream out in LDS and step the lane's four blocks from h = 0 into the
 // lane's chain acc = acc R + f.  Ends behind a barrier: the next tile's stores
 // follow this tile's loads.
-template <bool OPEN, MsgLayout LAY>
+template <bool OPEN, Construction C>
 __device__ __forceinline__ void msg_tile(uint8_t* lds, const uint32_t lane, const MsgStream& p, const MsgKey& mk,
                                          const ChaChaPre& pre, const MsgR& rr, const F26& R, const uint64_t t,
                                          F26& acc) {
@@ -245,7 +231,7 @@ __device__ __forceinline__ void msg_tile(uint8_t* lds, const uint32_t lane, cons
     if (s0 < P || s1e > P + n) {  // uniform
         int64_t a = s0 > 0 ? s0 : 0, b = s1e < P ? s1e : P;
         for (int64_t s = a + lane; s < b; s += kMsgThreads) {
-            if constexpr (LAY == MsgLayout::kRfc8439)
+            if constexpr (C == Construction::kRfc8439)
                 tl[s - s0] = s < adlen ? p.ad[s] : (uint8_t)0;
             else
                 tl[s - s0] = s < adlen ? p.ad[s] : (uint8_t)((uint64_t)adlen >> (8 * (s - adlen)));
@@ -253,7 +239,7 @@ __device__ __forceinline__ void msg_tile(uint8_t* lds, const uint32_t lane, cons
         a = s0 > P + n ? s0 : P + n;
         for (int64_t s = a + lane; s < s1e; s += kMsgThreads) {
             const int64_t i = s - (P + n);
-            if constexpr (LAY == MsgLayout::kRfc8439) {
+            if constexpr (C == Construction::kRfc8439) {
                 const int64_t q = i - ((16 - (n & 15)) & 15);  // place in the length block
                 tl[s - s0] = q < 0 || q >= 16 ? (uint8_t)0
                              : q < 8 ? (uint8_t)((uint64_t)adlen >> (8 * q))
@@ -278,7 +264,7 @@ __device__ __forceinline__ void msg_tile(uint8_t* lds, const uint32_t lane, cons
             if (vb < z) {  // virtual: value 0, no pad bit
                 m = u32x4{0u, 0u, 0u, 0u};
                 pad = 0u;
-            } else if (LAY == MsgLayout::kDraft && vb == p.last && p.rem < 16u) {
+            } else if (C == Construction::kDraft && vb == p.last && p.rem < 16u) {
                 // a short final block carries its pad bit at its own length
                 // (poly1305.rs:216-225; the bytes behind the stream are zero)
                 const uint32_t fb = 1u << (8u * (p.rem & 3u));

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/suruga_gpu.h"
+#include "sg_layout.h"
 
 namespace sg {
 
@@ -27,16 +28,51 @@ constexpr uint32_t kMsgPartialWords = 8;  // 5 radix-2^26 limbs, padded to 32 by
 
 int msg_groups();  // sg_set_msg_groups / SG_MSG_GROUPS
 
-// Bytes of a message's MAC stream: ad || le64(adlen) || ct || le64(n) in the
-// draft; with SG_MSG_RFC8439 ad and ct are each padded with zeros to a
-// multiple of 16 and one block le64(adlen) || le64(n) follows (RFC 8439
-// section 2.8).  Both lengths <= SG_MSG_MAX_LEN: far below 2^64.
+// Bytes of a message's MAC stream (sg_layout.h), the construction chosen by
+// SG_MSG_RFC8439.  Both lengths <= SG_MSG_MAX_LEN: far below 2^64.
 inline uint64_t msg_stream_len(uint64_t n, uint64_t adlen, uint32_t flags) {
-    if (flags & SG_MSG_RFC8439) return (adlen + 15u) / 16u * 16u + (n + 15u) / 16u * 16u + 16u;
-    return adlen + 16u + n;
+    return flags & SG_MSG_RFC8439 ? stream_bytes<Construction::kRfc8439>(adlen, n)
+                                  : stream_bytes<Construction::kDraft>(adlen, n);
 }
 // the flags the plan functions and the message calls know
 constexpr uint32_t kMsgKnownFlags = SG_MSG_KEEP_FAILED | SG_MSG_RFC8439;
+
+// The argument checks of one message, shared by sg_seal_msg_dev /
+// sg_open_msg_dev and every item of sg_seal_msg_batch / sg_open_msg_batch, in
+// the order the single call reports them.  No pointer is dereferenced.  (The
+// batch checks its key table and status array once, ahead of its items.)
+struct MsgArgs {
+    const void* key;
+    const void* ad;
+    uint64_t ad_len;
+    const void* in;
+    uint64_t in_len;
+    const void* out;
+    const void* status;  // open only
+};
+// NULL: the message may run, *n its data bytes -- or, with *shrt set, it is an
+// open of fewer than SG_MAC_LEN bytes (chacha20_poly1305.rs:68-70): the caller's
+// SG_E_SHORT, not an argument error, and nothing else was looked at.
+// Otherwise the message of the SG_E_ARG to report (a format for sg::fail).
+// (Inline: the batch runs it once per item inside its timed call, and as a
+// call into another file it cost 3 ns per item, 50 us per 16384 messages.)
+inline const char* msg_check_args(const MsgArgs& a, bool open, uint64_t* n, bool* shrt) {
+    *n = 0;
+    *shrt = open && a.in_len < SG_MAC_LEN;
+    if (*shrt) return nullptr;
+    *n = open ? a.in_len - SG_MAC_LEN : a.in_len;
+    if (*n > SG_MSG_MAX_LEN) return "message longer than SG_MSG_MAX_LEN%s";
+    if (a.ad_len > SG_MSG_MAX_LEN) return "ad_len exceeds SG_MSG_MAX_LEN%s";
+    const uint64_t out_len = open ? *n : *n + SG_MAC_LEN;
+    if (!a.key) return "key must be non-NULL%s";
+    if ((a.in_len && !a.in) || (out_len && !a.out) || (a.ad_len && !a.ad)) return "in/out/ad must be non-NULL%s";
+    if (open && !a.status) return "open requires a status byte%s";
+    if (a.in != a.out && a.in_len && out_len) {
+        const uintptr_t x = (uintptr_t)a.in, y = (uintptr_t)a.out;
+        if (x < y + out_len && y < x + a.in_len) return "out overlaps in (only out == in is allowed)%s";
+    }
+    return nullptr;
+}
 
 // ---- the message batch (sg_msg_batch.hip, sg_msg_batch_capi.cpp)
 // One message as the batch kernels read it (wave-uniform loads): the host

@@ -52,7 +52,7 @@
 // overflow a word; every step is exact mod 2^130 - 5 and the tag is the
 // reference's bit for bit.
 //
-// RecLayout::kRfc8439 (sg_*_batch_rfc8439, RFC 7905 TLS records).  The MAC
+// Construction::kRfc8439 (sg_*_batch_rfc8439, RFC 7905 TLS records).  The MAC
 // stream is ad || 0^3 || ct || le64(13) || le64(n): the 13-byte AD padded to 16
 // is block 0, the ciphertext starts on a block boundary and every block is
 // full, B = 4 nb + 2 again.  Lane j's 64 ciphertext bytes are blocks 4 j + 1 ..
@@ -136,7 +136,7 @@ constexpr uint32_t kSOut = 16;    // out_off lo, hi
 constexpr uint32_t kSS = 18;      // s[4]
 constexpr uint32_t kSCtot = 22;   // constant term (5 limbs)
 constexpr uint32_t kSNb = 27, kSStart = 28, kSRec = 29;
-// RecLayout::kRfc8439: the nonce's first word where the draft keeps the record
+// Construction::kRfc8439: the nonce's first word where the draft keeps the record
 // index (the finish takes the index from the list instead), so both layouts
 // share the stride, the aligned 8-byte reads of kSIn / kSOut and the LDS budget
 constexpr uint32_t kSN13 = kSRec;
@@ -197,15 +197,23 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane) {
 // The record's 64-byte block d[16] (ciphertext words) as the Poly1305 values
 // v1..v5 of the header comment, the MAC stream shifted by 5 bytes:
 // stream word w of the lane is alignbyte(d[w - 1], d[w - 2], 3).
+// RFC 8439: the lane's block is MAC blocks 4 j + 1 .. 4 j + 4, whole and in place.
+template <Construction C>
 __device__ __forceinline__ void lane_mac(H32& h, const uint32_t d[16], uint32_t r0, uint32_t r1, uint32_t r2,
                                          uint32_t r3, uint32_t s1, uint32_t s2, uint32_t s3) {
+    h = H32{0u, 0u, 0u, 0u, 0u};
+    if constexpr (C == Construction::kRfc8439) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)  // (h + v_k + 2^128) r
+            horner_step(h, d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3], 1u, r0, r1, r2, r3, s1, s2, s3);
+        return;
+    }
     uint32_t e[18];
     e[0] = 0u;
     e[1] = d[0] << 8;
 #pragma unroll
     for (int w = 2; w < 17; ++w) e[w] = __builtin_amdgcn_alignbyte(d[w - 1], d[w - 2], 3);
     e[17] = d[15] >> 24;
-    h = H32{0u, 0u, 0u, 0u, 0u};
 #pragma unroll
     for (int k = 0; k < 4; ++k)  // (h + v_k + 2^128) r
         horner_step(h, e[4 * k], e[4 * k + 1], e[4 * k + 2], e[4 * k + 3], 1u, r0, r1, r2, r3, s1, s2, s3);
@@ -215,14 +223,6 @@ __device__ __forceinline__ void lane_mac(H32& h, const uint32_t d[16], uint32_t 
     h.h2 = addc(h.h2, 0u, c, &c);
     h.h3 = addc(h.h3, 0u, c, &c);
     h.h4 += c;
-}
-// RFC 8439: the lane's block is MAC blocks 4 j + 1 .. 4 j + 4, whole and in place
-__device__ __forceinline__ void lane_mac_rfc(H32& h, const uint32_t d[16], uint32_t r0, uint32_t r1, uint32_t r2,
-                                             uint32_t r3, uint32_t s1, uint32_t s2, uint32_t s3) {
-    h = H32{0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int k = 0; k < 4; ++k)  // (h + v_k + 2^128) r
-        horner_step(h, d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3], 1u, r0, r1, r2, r3, s1, s2, s3);
 }
 
 // Phase timing (experiment builds only, -DSG_PACK_PROFILE=1; output
@@ -243,19 +243,12 @@ __device__ unsigned long long g_pack_prof[kProfWgs][kProfStamps];
 #define SG_STAMP(w, k)
 #endif
 
-// The record's key and nonce in the layout's own shape (the draft's has no word 13)
-template <RecLayout LAY>
-__device__ __forceinline__ auto pack_record_key(const KParams& p, uint32_t rec) {
-    if constexpr (LAY == RecLayout::kRfc8439) return record_key_rfc(p, rec);
-    else return record_key(p, rec);
-}
-
 // One run: records first .. first + nrec - 1 of the packed list.
-template <bool OPEN, RecLayout LAY>
+template <bool OPEN, Construction C>
 __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __restrict__ list, const uint32_t first,
                                          const uint32_t nrec, PackLds& L, const uint32_t tid, const uint32_t lane,
                                          const uint32_t wave) {
-    constexpr bool RFC = LAY == RecLayout::kRfc8439;
+    constexpr bool RFC = C == Construction::kRfc8439;
 
     SG_STAMP(0u, 0);
     for (uint32_t i = tid; i < kPackBlocks / 32u; i += kPackThreads) L.bits[i] = 0u;
@@ -277,7 +270,7 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
             const uint32_t len = record_len(p, rec);
             const uint64_t io = rec_in_off(p, rec);
             const uint64_t oo = rec_out_off(p, rec);
-            const auto rk = pack_record_key<LAY>(p, rec);
+            const RecKey rk = record_key<C>(p, rec);
             const uint32_t n = OPEN ? len - 16u : len;  // listed records: 64 <= n <= 4096, n % 64 == 0
             nb = n >> 6;
 #if SG_PACK_PROFILE
@@ -285,9 +278,7 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
 #endif
             SG_STAMP(0u, 8);
             uint32_t ks[16];
-            // block 0 -> poly key (chacha20_poly1305.rs:50,75)
-            if constexpr (RFC) chacha_block(ks, rk.k, 0u, rk.n13, rk.n14, rk.n15);
-            else chacha_block(ks, rk.k, 0u, rk.n14, rk.n15);
+            chacha_block(ks, rk.k, 0u, rk.n13, rk.n14, rk.n15);  // block 0 -> poly key (chacha20_poly1305.rs:50,75)
             const PolyKey pk = poly_key(ks);
             SG_STAMP(0u, 9);
 #pragma unroll
@@ -456,8 +447,7 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
                                      a2[0], a2[1], a2[2], a2[3], a3[0], a3[1], a3[2], a3[3]};
             const uint32_t r0 = sl[kSR + 0], r1 = sl[kSR + 1], r2 = sl[kSR + 2], r3 = sl[kSR + 3];
             H32 h;
-            if constexpr (RFC) lane_mac_rfc(h, cw, r0, r1, r2, r3, r1 + (r1 >> 2), r2 + (r2 >> 2), r3 + (r3 >> 2));
-            else lane_mac(h, cw, r0, r1, r2, r3, r1 + (r1 >> 2), r2 + (r2 >> 2), r3 + (r3 >> 2));
+            lane_mac<C>(h, cw, r0, r1, r2, r3, r1 + (r1 >> 2), r2 + (r2 >> 2), r3 + (r3 >> 2));
             const F26 Q = words_to_f26(h.h0, h.h1, h.h2, h.h3, h.h4);
             const uint32_t i = sl[kSNb] - 1u - j;
             const uint32_t* tb = L.tab + m * kTabWords;
@@ -507,7 +497,7 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
 // population is read from the workspace tail (the host does not need it, so
 // the launch goes ahead of the population readback) and the 128-record runs
 // come from a device counter, so that the runs' different lengths even out.
-template <bool OPEN, RecLayout LAY>
+template <bool OPEN, Construction C>
 __global__ __launch_bounds__(kPackThreads) __attribute__((amdgpu_waves_per_eu(6)))
 void sg_pack_kernel(const KParams p, const uint32_t* __restrict__ list, const uint32_t* __restrict__ cnt, uint32_t* ctr) {
     __shared__ PackLds L;
@@ -520,7 +510,7 @@ void sg_pack_kernel(const KParams p, const uint32_t* __restrict__ list, const ui
         const uint32_t run = __builtin_amdgcn_readfirstlane(L.run);
         if (run >= nruns) break;  // (workgroup-uniform)
         const uint32_t first = run * kPackRecs;
-        pack_run<OPEN, LAY>(p, list, first, count - first < kPackRecs ? count - first : kPackRecs, L, tid, lane, wave);
+        pack_run<OPEN, C>(p, list, first, count - first < kPackRecs ? count - first : kPackRecs, L, tid, lane, wave);
         __syncthreads();  // the finish read the slots that the next run's setup rewrites, and L.run
     }
 }
@@ -536,10 +526,10 @@ hipError_t launch_pack(const KParams& p, bool open, const uint32_t* list, const 
     if ((e = device_cus(&cus)) != hipSuccess) return e;
     const uint32_t most = (p.count + kPackRecs - 1u) / kPackRecs;
     const uint32_t grid = 3u * (uint32_t)cus < most ? 3u * (uint32_t)cus : most;  // three workgroups per CU
-    constexpr RecLayout D = RecLayout::kDraft, R = RecLayout::kRfc8439;
-    const auto kernel = p.rfc ? (open ? sg_pack_kernel<true, R> : sg_pack_kernel<false, R>)
-                              : (open ? sg_pack_kernel<true, D> : sg_pack_kernel<false, D>);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPackThreads), 0, s, p, list, count, ctr);
+    with_form(p.rfc, open, [&](auto OPEN, auto C) {
+        hipLaunchKernelGGL((sg_pack_kernel<OPEN.value, C.value>), dim3(grid), dim3(kPackThreads), 0, s, p, list, count,
+                           ctr);
+    });
     return hipGetLastError();
 }
 

@@ -33,6 +33,10 @@ inline void put_be16(uint8_t* p, uint32_t v) {
     p[0] = (uint8_t)(v >> 8);
     p[1] = (uint8_t)v;
 }
+// four bytes at any alignment -> little-endian word
+inline uint32_t get_le32(const uint8_t* p) {
+    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+}
 inline void put_be64(uint8_t* p, uint64_t v) {
     for (int i = 0; i < 8; ++i) p[i] = (uint8_t)(v >> (56 - 8 * i));
 }

@@ -51,7 +51,7 @@
 // (tests/test_wpr_mac_model.py pins this decomposition against the CPU
 // restatement of poly1305.rs).
 //
-// RecLayout::kRfc8439 (the uniform launch and the J = 2..4 buckets; sg_*_batch_rfc8439): in the RFC
+// Construction::kRfc8439 (the uniform launch and the J = 2..4 buckets; sg_*_batch_rfc8439): in the RFC
 // 8439 stream ad || 0.. || ct || 0.. || le64(|ad|) || le64(n) the ciphertext
 // starts on a block boundary, which is the sigma = 0 case above for every AD
 // length, so the MFMA body is the draft's.  The keying kernel's constant term
@@ -109,11 +109,12 @@ struct WprGeom {
 // RFC 8439 (ad || 0.. || ct || 0.. || le64(|ad|) || le64(n)): the ciphertext
 // starts on a block boundary, o = 16 ceil(adlen / 16), sigma = 0, and one full
 // block closes the stream: B = beta + m + 1, rem = 16, delta = 0.
-template <RecLayout LAY>
+// (o and the stream length: sg_layout.h)
+template <Construction C>
 __device__ __forceinline__ WprGeom wpr_geom(uint32_t adlen, uint32_t n) {
     WprGeom g;
-    if constexpr (LAY == RecLayout::kRfc8439) {
-        g.o = (adlen + 15u) & ~15u;
+    g.o = ct_offset<C>(adlen);
+    if constexpr (C == Construction::kRfc8439) {
         g.sigma = 0u;
         g.beta = g.o >> 4;
         g.m = n >> 4;
@@ -122,10 +123,9 @@ __device__ __forceinline__ WprGeom wpr_geom(uint32_t adlen, uint32_t n) {
         g.delta = 0u;
         return g;
     }
-    g.o = adlen + 8u;
     g.sigma = g.o & 15u;
     g.beta = g.o >> 4;
-    const uint32_t L = adlen + 16u + n;
+    const uint32_t L = stream_bytes<C>(adlen, n);
     g.B = (L + 15u) >> 4;
     g.rem = L - 16u * (g.B - 1u);
     g.m = n >> 4;                        // 16-byte ciphertext chunks
@@ -186,10 +186,10 @@ struct WprKeyJobs {
 };
 
 // (compiled for two waves per SIMD: four and more spill to scratch)
-template <bool OPEN, bool LIST, RecLayout LAY>
+template <bool OPEN, bool LIST, Construction C>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg_wpr_keying_kernel(
     const KParams p, const WprKeyJobs jobs) {
-    constexpr bool RFC = LAY == RecLayout::kRfc8439;
+    constexpr bool RFC = C == Construction::kRfc8439;
     const uint32_t lane = threadIdx.x;
     WprList wl = jobs.b[0];
     uint32_t b0 = 0;
@@ -212,13 +212,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
     const uint32_t rec = LIST ? (act ? wl.list[slot] : 0u) : slot;
     uint32_t n = kWprN;
     if constexpr (LIST) n = act ? p.len[rec] - (OPEN ? 16u : 0u) : kWprN;
-    const WprGeom G = wpr_geom<LAY>(adlen, n);
+    const WprGeom G = wpr_geom<C>(adlen, n);
 
     F26 r = f26_zero();
     uint32_t s[4] = {0u, 0u, 0u, 0u};
-    RecKeyRfc rk = {};
+    RecKey rk = {};
     if (act) {
-        rk = record_key_of<LAY>(p, rec);
+        rk = record_key<C>(p, rec);
         uint32_t ks[16];
         chacha_block(ks, rk.k, 0u, rk.n13, rk.n14, rk.n15);  // block 0 -> poly key (chacha20_poly1305.rs:50,75)
         const PolyKey pk = poly_key(ks);
@@ -227,8 +227,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
         if constexpr (LIST) {  // the slot's descriptor: where the record lives, its length and nonce
             const uint64_t io = rec_in_off(p, rec);
             const uint64_t oo = rec_out_off(p, rec);
-            uint32_t ki = p.key_index ? p.key_index[rec] : 0u;
-            ki = ki < p.num_keys ? ki : p.num_keys - 1u;  // (record_key's clamp)
+            const uint32_t ki = key_slot(p, rec);
             uint32_t* d = wl.desc + (uint64_t)slot * kWprDescWords;
             st16(d, u32x4{(uint32_t)io, (uint32_t)(io >> 32), (uint32_t)oo, (uint32_t)(oo >> 32)});
             st16(d + 4, u32x4{n, rec, ki, rk.n14});
@@ -347,11 +346,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
             uint32_t w[4] = {0u, 0u, 0u, 0u};
             for (uint32_t i = 0; i < 16u; ++i) {
                 const uint32_t pos = 16u * b + i;
-                if constexpr (RFC) {  // ad and its zero padding (block beta is empty: sigma = 0)
-                    if (pos < G.o) w[i >> 2] |= (uint32_t)prefix_byte_rfc(p, rec, rk.seq, n, adlen, pos) << (8u * (i & 3u));
-                } else {
-                    if (pos < G.o) w[i >> 2] |= (uint32_t)prefix_byte(p, rec, rk.seq, n, adlen, pos) << (8u * (i & 3u));
-                }
+                // (RFC 8439: ad and its zero padding; block beta is empty, sigma = 0)
+                if (pos < G.o) w[i >> 2] |= (uint32_t)prefix_byte<C>(p, rec, rk.seq, n, adlen, pos) << (8u * (i & 3u));
             }
             hp = fmul_add(hp, r, words_to_f26(w[0], w[1], w[2], w[3], 0u));
         }
@@ -517,11 +513,11 @@ struct RecDesc {
     uint32_t n13;       // RFC 8439 only (the draft's word 13 is 0)
 };
 
-template <bool OPEN, bool TLS, uint32_t J, bool LIST, RecLayout LAY>
+template <bool OPEN, bool TLS, uint32_t J, bool LIST, Construction C>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void sg_wpr_kernel(const KParams p,
                                                                                                const WprList wl) {
     static_assert(J >= 1u && J <= 4u && (LIST || J == 4u), "uniform launches are full 16 KiB records");
-    constexpr bool RFC = LAY == RecLayout::kRfc8439;
+    constexpr bool RFC = C == Construction::kRfc8439;
     constexpr uint32_t j0 = 4u - J;  // the first chunk of the right-aligned record in the 16 KiB frame
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const uint32_t wave = uniform(threadIdx.x >> 6), lane = threadIdx.x & 63u;
@@ -585,8 +581,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             d.io = p.in_stride * slot;
             d.oo = p.out_stride * slot;
             d.n = kWprN;
-            d.ki = p.key_index ? cload(p.key_index, slot) : 0u;
-            d.ki = d.ki < p.num_keys ? d.ki : p.num_keys - 1u;  // (record_key's clamp)
+            d.ki = key_slot_of(p, p.key_index ? cload(p.key_index, slot) : 0u);  // (key_slot, by a scalar load)
             // nonce (chacha20.rs:25-51; TLS: be64(seq), tls.rs:103)
             if constexpr (RFC && TLS) {  // RFC 7905: the key's write IV XOR (0^32 || be64(seq)), on the SALU
                 uint64_t seq = p.seq0 + slot;
@@ -1237,27 +1232,21 @@ hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_
     jobs.b[0] = wl;
     jobs.njobs = 1;
     const uint32_t kgrid = (p.count + kWprKeyThreads - 1u) / kWprKeyThreads;
-    constexpr RecLayout D = RecLayout::kDraft, R = RecLayout::kRfc8439;
-    const auto keying = p.rfc ? (open ? sg_wpr_keying_kernel<true, false, R> : sg_wpr_keying_kernel<false, false, R>)
-                              : (open ? sg_wpr_keying_kernel<true, false, D> : sg_wpr_keying_kernel<false, false, D>);
-    hipLaunchKernelGGL(keying, dim3(kgrid), dim3(kWprKeyThreads), 0, s, p, jobs);
+    with_form(p.rfc, open, [&](auto OPEN, auto C) {
+        const dim3 g(kgrid), b(kWprKeyThreads);
+        hipLaunchKernelGGL((sg_wpr_keying_kernel<OPEN.value, false, C.value>), g, b, 0, s, p, jobs);
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if ((e = mark(ev_keyed, s)) != hipSuccess || (e = mark(ev_start, s)) != hipSuccess) return e;
     int cus = 0;
     if ((e = device_cus(&cus)) != hipSuccess) return e;
     const uint32_t grid = wpr_grid(cus, p.count);
-#define SG_WPR_LAUNCH(O, T)                                                                                          \
-    do {                                                                                                            \
-        if (p.rfc) hipLaunchKernelGGL((sg_wpr_kernel<O, T, 4, false, R>), dim3(grid), dim3(512), kWprWgLds, s, p, wl); \
-        else hipLaunchKernelGGL((sg_wpr_kernel<O, T, 4, false, D>), dim3(grid), dim3(512), kWprWgLds, s, p, wl);    \
-    } while (0)
-    if (open) {
-        if (p.tls) SG_WPR_LAUNCH(true, true); else SG_WPR_LAUNCH(true, false);
-    } else {
-        if (p.tls) SG_WPR_LAUNCH(false, true); else SG_WPR_LAUNCH(false, false);
-    }
-#undef SG_WPR_LAUNCH
+    with_form(p.rfc, open, [&](auto OPEN, auto C) {
+        const dim3 g(grid), b(512);
+        if (p.tls) hipLaunchKernelGGL((sg_wpr_kernel<OPEN.value, true, 4, false, C.value>), g, b, kWprWgLds, s, p, wl);
+        else hipLaunchKernelGGL((sg_wpr_kernel<OPEN.value, false, 4, false, C.value>), g, b, kWprWgLds, s, p, wl);
+    });
     return hipGetLastError();
 }
 
@@ -1273,10 +1262,10 @@ hipError_t launch_wpr_keying_lists(const KParams& p, bool open, const WprList* w
         ++jobs.njobs;
     }
     if (grid == 0) return hipSuccess;
-    constexpr RecLayout D = RecLayout::kDraft, R = RecLayout::kRfc8439;
-    const auto keying = p.rfc ? (open ? sg_wpr_keying_kernel<true, true, R> : sg_wpr_keying_kernel<false, true, R>)
-                              : (open ? sg_wpr_keying_kernel<true, true, D> : sg_wpr_keying_kernel<false, true, D>);
-    hipLaunchKernelGGL(keying, dim3(grid), dim3(kWprKeyThreads), 0, s, p, jobs);
+    with_form(p.rfc, open, [&](auto OPEN, auto C) {
+        const dim3 g(grid), b(kWprKeyThreads);
+        hipLaunchKernelGGL((sg_wpr_keying_kernel<OPEN.value, true, C.value>), g, b, 0, s, p, jobs);
+    });
     return hipGetLastError();
 }
 
@@ -1287,21 +1276,15 @@ hipError_t launch_wpr_list(const KParams& p, bool open, uint32_t J, const WprLis
     int cus = 0;
     if ((e = device_cus(&cus)) != hipSuccess) return e;
     const uint32_t grid = wpr_grid(cus, wl.count);
-#define SG_WPR_LAUNCH(O, JJ)                                                                                         \
-    do {                                                                                                            \
-        if (p.rfc)                                                                                                  \
-            hipLaunchKernelGGL((sg_wpr_kernel<O, true, JJ, true, RecLayout::kRfc8439>), dim3(grid), dim3(512),       \
-                               kWprWgLds, s, p, wl);                                                                \
-        else                                                                                                        \
-            hipLaunchKernelGGL((sg_wpr_kernel<O, true, JJ, true, RecLayout::kDraft>), dim3(grid), dim3(512),         \
-                               kWprWgLds, s, p, wl);                                                                \
-    } while (0)
-    switch (J) {
-        case 2: if (open) SG_WPR_LAUNCH(true, 2); else SG_WPR_LAUNCH(false, 2); break;
-        case 3: if (open) SG_WPR_LAUNCH(true, 3); else SG_WPR_LAUNCH(false, 3); break;
-        default: if (open) SG_WPR_LAUNCH(true, 4); else SG_WPR_LAUNCH(false, 4); break;
-    }
-#undef SG_WPR_LAUNCH
+    with_form(p.rfc, open, [&](auto OPEN, auto C) {
+        const dim3 g(grid), b(512);
+        constexpr bool O = OPEN.value;
+        switch (J) {
+            case 2: hipLaunchKernelGGL((sg_wpr_kernel<O, true, 2, true, C.value>), g, b, kWprWgLds, s, p, wl); break;
+            case 3: hipLaunchKernelGGL((sg_wpr_kernel<O, true, 3, true, C.value>), g, b, kWprWgLds, s, p, wl); break;
+            default: hipLaunchKernelGGL((sg_wpr_kernel<O, true, 4, true, C.value>), g, b, kWprWgLds, s, p, wl); break;
+        }
+    });
     return hipGetLastError();
 }
 
@@ -1318,8 +1301,8 @@ const char* wpr_kernel_config() {
            "v_mfma_i32_32x32x32_i8 per record fed from the ciphertext registers one chunk behind (Toeplitz digit "
            "lines of r^(128k+d) in LDS, read as aligned dwords + v_alignbyte), exact per-lane assembly, "
            "W = r^(4(31-q)) scaling, DPP sum; keying pre-pass with the constant term; bucket records: the idle lanes "
-           "of the first chunk sit out its rounds (EXEC); every form also as RecLayout::kRfc8439 (RFC 8439 / RFC 7905: "
-           "word-13 nonce, block-aligned MAC stream; uniform 16 KiB launch and the J = 2..4 buckets)";
+           "of the first chunk sit out its rounds (EXEC); every form also as Construction::kRfc8439 (RFC 8439 / RFC "
+           "7905: word-13 nonce, block-aligned MAC stream; uniform 16 KiB launch and the J = 2..4 buckets)";
 }
 
 }  // namespace sg

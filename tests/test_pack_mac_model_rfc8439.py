@@ -1,5 +1,5 @@
 """CPU check of the packed kernel's Poly1305 in RFC 8439 form
-(sg_pack_kernel<OPEN, RecLayout::kRfc8439>, suruga_amd/csrc/sg_pack.hip).
+(sg_pack_kernel<OPEN, Construction::kRfc8439>, suruga_amd/csrc/sg_pack.hip).
 
 A TLS record of n = 64 nb bytes has the MAC stream ad || 0^3 || ct || le64(13) ||
 le64(n), B = 4 nb + 2 full blocks.  The kernel computes its accumulator as

@@ -1,5 +1,5 @@
 """CPU check of the bucket keying in RFC 8439 form
-(sg_wpr_keying_kernel<OPEN, true, RecLayout::kRfc8439>, suruga_amd/csrc/sg_wpr.hip).
+(sg_wpr_keying_kernel<OPEN, true, Construction::kRfc8439>, suruga_amd/csrc/sg_wpr.hip).
 
 A bucket record of n = 64 k' bytes (4 KiB < n <= 16 KiB) runs right-aligned in the
 record kernel's 16 KiB frame: the frame bytes before it enter the MFMA as i8 zeros,

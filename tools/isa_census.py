@@ -40,7 +40,7 @@ import isa_count as ic  # noqa: E402
 from suruga_amd import _build  # noqa: E402
 
 FULL = ic.FULL
-DRAFT_ARG = ", (sg::RecLayout)0"  # RecLayout::kDraft as c++filt prints it
+DRAFT_ARG = ", (sg::Construction)0"  # Construction::kDraft as c++filt prints it
 
 
 def demangle(names):
@@ -123,11 +123,13 @@ def main():
                                         "(profiles/r01_valu_issue_probes.md)",
            "kernels": kernels}
     # The draft instantiations of the record kernels that take the construction as a
-    # template parameter (RecLayout, sg_internal.h) are also listed under the name they
+    # template parameter (Construction, sg_layout.h) are also listed under the name they
     # had before the parameter: bench.py's C1 roofline and earlier profiles look the
     # draft kernel up by that name, and it is the same kernel.
+    # (The message kernels share the parameter and were never looked up by a
+    # shorter name: they keep their one entry.)
     for k in list(kernels):
-        if DRAFT_ARG in k:
+        if DRAFT_ARG in k and "sg_msg" not in k:
             kernels.setdefault(k.replace(DRAFT_ARG, ""), kernels[k])
     dst = ROOT / "profiles" / f"isa_{src}.json"
     dst.write_text(json.dumps(res, indent=1) + "\n")

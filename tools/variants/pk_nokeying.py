@@ -8,7 +8,7 @@
 # its instructions still take)
 EDITS = [
     ("sg_pack.hip", """            uint32_t ks[16];
-            chacha_block(ks, rk.k, 0u, rk.n14, rk.n15);  // block 0 -> poly key (chacha20_poly1305.rs:50,75)""",
+            chacha_block(ks, rk.k, 0u, rk.n13, rk.n14, rk.n15);  // block 0 -> poly key (chacha20_poly1305.rs:50,75)""",
      """            uint32_t ks[16] = {0x0a1b2c3du, 0x04050607u, 0x08090a0bu, 0x0c0d0e0fu, rk.k[0], rk.k[1], rk.k[2], rk.k[3]};"""),
     ("sg_pack.hip", """            const F26 r = words_to_f26(pk.r0, pk.r1, pk.r2, pk.r3, 0u);
             const F26 r2 = fmul(r, r), R = fmul(r2, r2);
@@ -36,5 +36,5 @@ EDITS = [
             const F26 rB = fmul(fmul(wl, R), r);""", """            const F26 rB = f26_zero();
             (void)il;"""),
     ("sg_pack.hip", """            store_f26(sl + kSCtot, fmul_add(blk0, rB, fmul(sfx, r)));""",
-     """            store_f26(sl + kSCtot, f26_add(blk0, f26_add(rB, sfx)));"""),
+     """            store_f26(sl + kSCtot, f26_add(blk0, f26_add(rB, sfx)));""", "all"),  # both constructions' branches
 ]
