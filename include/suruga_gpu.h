@@ -232,6 +232,55 @@ typedef struct sg_batch_rfc8439 {
 int sg_seal_batch_rfc8439(const sg_batch* b, const sg_batch_rfc8439* x);
 int sg_open_batch_rfc8439(const sg_batch* b, const sg_batch_rfc8439* x);
 
+/* The record batch as TLS 1.3 protects records (RFC 8446 section 5.2 - 5.4) with
+ * TLS_CHACHA20_POLY1305_SHA256: RFC 8439 over TLSInnerPlaintext = content ||
+ * type || zeros.  Nonce, additional data and the inner type byte are built on
+ * the device, and open strips type and padding; through the RFC calls above a
+ * TLS 1.3 caller has to do all of that itself, in explicit mode.
+ * `b` is the unchanged sg_batch with these rules:
+ *   flags        SG_BATCH_TLS must be set; SG_BATCH_KEEP_FAILED is allowed.
+ *   nonces, ads, ver_major, ver_minor   ignored.
+ *   nonce_i      ivs[key_i] XOR (00 00 00 00 || be64(seq_i))      (section 5.3)
+ *   AD_i         17 03 03 be16(L_i), L_i the fragment length: the inner length
+ *                + 16 on seal, len_i on open                       (section 5.2)
+ * Seal: len_i is the content length, 0..2^14.  b->content_type is the inner
+ *   type of every record of the call and must be non-zero (a zero would read
+ *   as padding).  Record i reads len_i bytes and writes len_i + 17:
+ *   ct(content || type) || tag.  Seal adds no padding.
+ * Open: len_i is the fragment length, at most 2^14 + 256; below 16 the status
+ *   is SG_E_SHORT.  The len_i - 16 inner bytes go to `out` as in the RFC call.
+ *   Then, for every record whose status is SG_OK, the last non-zero inner byte
+ *   goes to inner_type[i] and the number of bytes before it to content_len[i];
+ *   a record with no non-zero byte (or no byte) gets SG_STATUS_NO_TYPE.  Every
+ *   record with another status gets type 0 and length 0.  The scrub,
+ *   SG_STATUS_SKIPPED, the workspace, stream and capture rules are those of
+ *   sg_open_batch_rfc8439.  content_len > 2^14 is the caller's to map to
+ *   record_overflow.
+ * SG_E_ARG before any GPU work: x NULL, x->flags non-zero, SG_BATCH_TLS not
+ * set, other flags, ivs NULL or not 4-byte aligned, a zero content_type on
+ * seal, max_len / uniform_len above 2^14 (seal) or 2^14 + 256 (open), open
+ * without inner_type or content_len or with content_len not 4-byte aligned,
+ * and whatever the RFC calls reject.
+ * Routes: a uniform batch of full records (uniform_len 2^14 on seal, 2^14 + 17
+ * on open; bases and strides 16-byte aligned, no len / offset arrays) runs on
+ * the wave-per-record kernel, whose keying pre-pass takes the type byte and
+ * its MAC block; every other batch on the size classes (inner lengths are
+ * never multiples of 64, so mixed batches take no packed or bucket route). */
+typedef struct sg_batch_tls13 {
+    const uint8_t* ivs;          /* device [num_keys][12], 4-byte aligned, required        */
+    uint8_t*       inner_type;   /* open: device, count bytes, required; seal: not read    */
+    uint32_t*      content_len;  /* open: device, count words, 4-byte aligned, required    */
+    uint32_t       flags;        /* 0; anything else SG_E_ARG                              */
+    uint32_t       _pad;
+} sg_batch_tls13;                /* 32 bytes */
+int sg_seal_batch_tls13(const sg_batch* b, const sg_batch_tls13* x);
+int sg_open_batch_tls13(const sg_batch* b, const sg_batch_tls13* x);
+#define SG_STATUS_NO_TYPE 5      /* open: tag good, inner plaintext all zero (or empty)    */
+/* Which route a TLS 1.3 batch would take (host only, no GPU call): 0 = size
+ * classes, 1 = wave-per-record kernel, SG_E_ARG for a batch the calls above
+ * reject on its own fields; honours sg_set_lockstep. */
+int sg_batch_tls13_route(const sg_batch* b, int open);
+
 /* ---- long messages: any data and AD length, one message over the whole chip
  * Encryptor::encrypt / Decryptor::decrypt take data and additional data of any
  * length (cipher/mod.rs:22-32, chacha20_poly1305.rs:19-94).  sg_seal, sg_open

@@ -18,6 +18,8 @@ SG_E_SHORT = 2
 SG_E_ARG = -1
 SG_E_HIP = -2
 SG_E_NODEV = -3
+SG_STATUS_SKIPPED = 3
+SG_STATUS_NO_TYPE = 5
 
 SG_BATCH_TLS = 0x1
 SG_BATCH_KEEP_FAILED = 0x2
@@ -36,6 +38,7 @@ EXPORTS = [
     "sg_key_size", "sg_fixed_iv_len", "sg_mac_len", "sg_abi_version",
     "sg_ctx_new", "sg_ctx_free", "sg_seal", "sg_open",
     "sg_workspace_size", "sg_seal_batch", "sg_open_batch", "sg_seal_batch_rfc8439", "sg_open_batch_rfc8439",
+    "sg_seal_batch_tls13", "sg_open_batch_tls13", "sg_batch_tls13_route",
     "sg_fill_records", "sg_compare_records",
     "sg_last_error", "sg_build_info", "sg_source_hash", "sg_set_timing", "sg_timing_read", "sg_set_lockstep", "sg_set_packed",
     "sg_last_batch_routes",
@@ -92,6 +95,13 @@ class SgBatchRfc8439(C.Structure):
     """Mirror of ``struct sg_batch_rfc8439``."""
 
     _fields_ = [("ivs", C.c_void_p), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class SgBatchTls13(C.Structure):
+    """Mirror of ``struct sg_batch_tls13``."""
+
+    _fields_ = [("ivs", C.c_void_p), ("inner_type", C.c_void_p), ("content_len", C.c_void_p), ("flags", C.c_uint32),
+                ("_pad", C.c_uint32)]
 
 
 class SgBatchRoutes(C.Structure):
@@ -254,6 +264,11 @@ def _declare(lib: C.CDLL) -> None:
     for f in (lib.sg_seal_batch_rfc8439, lib.sg_open_batch_rfc8439):
         f.restype = C.c_int
         f.argtypes = [C.POINTER(SgBatch), C.POINTER(SgBatchRfc8439)]
+    for f in (lib.sg_seal_batch_tls13, lib.sg_open_batch_tls13):
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(SgBatch), C.POINTER(SgBatchTls13)]
+    lib.sg_batch_tls13_route.restype = C.c_int
+    lib.sg_batch_tls13_route.argtypes = [C.POINTER(SgBatch), C.c_int]
     lib.sg_fill_records.restype = C.c_int
     lib.sg_fill_records.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64,
                                     C.c_uint64, C.c_void_p]

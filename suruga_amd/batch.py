@@ -11,6 +11,10 @@ With ``rfc8439=True`` the same batch runs through ``sg_seal_batch_rfc8439`` /
 ``sg_open_batch_rfc8439``: RFC 8439 with 12-byte nonces, and in TLS mode the
 RFC 7905 nonce (the key's write IV in ``ivs`` XOR the sequence number).
 
+``seal_tls13`` / ``open_tls13`` run it as TLS 1.3 records (RFC 8446 section 5.2,
+``sg_seal_batch_tls13`` / ``sg_open_batch_tls13``): the device appends the
+inner type byte on seal and returns ``inner_type`` / ``content_len`` on open.
+
 Tensors are torch tensors on the GPU (PyTorch is used here only for device
 memory and streams); all arithmetic runs in the gfx950 kernels.
 """
@@ -72,7 +76,17 @@ class Batch:
     stream: object = None             # torch.cuda.Stream / raw handle (0: the NULL stream) / None = current stream
     keep_failed: bool = False         # open: keep the unauthenticated plaintext of BAD_MAC records
     rfc8439: bool = False             # RFC 8439 / RFC 7905 (explicit mode: nonces are uint8 [count, 12])
-    ivs: object = None                # rfc8439 TLS mode: uint8 [num_keys, 12] device, the write IVs
+    ivs: object = None                # rfc8439 TLS mode / TLS 1.3: uint8 [num_keys, 12] device, the write IVs
+    inner_type: object = None         # open_tls13: uint8 [count] device, the records' inner content types
+    content_len: object = None        # open_tls13: uint32 [count] device, the records' content lengths
+
+    def to_c_tls13(self) -> N.SgBatchTls13:
+        x = N.SgBatchTls13()
+        x.ivs = _ptr(self.ivs)
+        x.inner_type = _ptr(self.inner_type)
+        x.content_len = _ptr(self.content_len)
+        x.flags = 0
+        return x
 
     def to_c_rfc8439(self) -> N.SgBatchRfc8439:
         x = N.SgBatchRfc8439()
@@ -141,6 +155,30 @@ def open_(batch: Batch) -> None:
     if batch.ivs is not None:
         raise ValueError("ivs belong to rfc8439=True")
     N.check(N.load().sg_open_batch(C.byref(cb)))
+
+
+def seal_tls13(batch: Batch) -> None:
+    """Seal every record as a TLS 1.3 record: out_i = ct(content_i || type) || tag_i,
+    len_i + 17 bytes; the type is ``batch.content_type`` (RFC 8446 section 5.2)."""
+    cb, xb = batch.to_c(), batch.to_c_tls13()
+    N.check(N.load().sg_seal_batch_tls13(C.byref(cb), C.byref(xb)))
+
+
+def open_tls13(batch: Batch) -> None:
+    """Open every TLS 1.3 record: the inner plaintext lands in ``out``, the status in
+    ``batch.status`` (0 ok, 1 wrong mac, 2 too short, 5 no inner type), and for status 0
+    the inner type and the content length in ``batch.inner_type`` / ``batch.content_len``."""
+    if batch.status is None or batch.inner_type is None or batch.content_len is None:
+        raise ValueError("open_tls13 needs status, inner_type and content_len tensors")
+    cb, xb = batch.to_c(), batch.to_c_tls13()
+    N.check(N.load().sg_open_batch_tls13(C.byref(cb), C.byref(xb)))
+
+
+def tls13_route(batch: Batch, open: bool) -> int:  # noqa: A002  (the C argument's name)
+    """The route ``seal_tls13`` / ``open_tls13`` would take, without any GPU call:
+    0 the size classes, 1 the wave-per-record kernel (``sg_batch_tls13_route``)."""
+    cb = batch.to_c()
+    return N.check(N.load().sg_batch_tls13_route(C.byref(cb), 1 if open else 0))
 
 
 def fill_records(buf, stride: int, length: int, count: int, seed: int, j0: int = 0, stream=None) -> None:

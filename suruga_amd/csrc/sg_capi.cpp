@@ -5,7 +5,7 @@
 // staging for the single-record Encryptor/Decryptor calls, and the launches
 // of the gfx950 kernels through sg_internal.h's launch_* functions (uniform
 // 16 KiB batches: sg_wpr.hip; every other batch: sg_dispatch.cpp; fill,
-// compare and scrub: sg_plumb.hip).  There is no CPU fallback: every
+// compare, scrub and the TLS 1.3 strip: sg_plumb.hip).  There is no CPU fallback: every
 // seal/open goes through the HIP kernels or fails with an error code.
 #include <hip/hip_runtime.h>
 
@@ -199,8 +199,54 @@ bool wpr_eligible(const sg_batch* b, bool open) {
     return ((uintptr_t)b->in | (uintptr_t)b->out | b->in_stride | b->out_stride) % 16u == 0u;
 }
 
+// TLS 1.3 record batch (sg_*_batch_tls13): RFC 8446 section 5.1 / 5.2 bounds of a
+// record's content (seal) and of its fragment (open)
+constexpr uint32_t kTls13MaxContent = 1u << 14;
+constexpr uint32_t kTls13MaxFragment = (1u << 14) + 256u;
+
+// What the TLS 1.3 calls check of the batch itself (x aside), before validate().
+int validate_tls13(const sg_batch* b, bool open) {
+    if (!b) return fail(SG_E_ARG, "batch is NULL%s");
+    if (!(b->flags & SG_BATCH_TLS))
+        return fail(SG_E_ARG, "the TLS 1.3 batch builds nonce and AD on the device: SG_BATCH_TLS must be set%s");
+    if (b->flags & ~(SG_BATCH_TLS | SG_BATCH_KEEP_FAILED)) return fail(SG_E_ARG, "unknown flags%s");
+    const uint32_t maxl = b->len ? b->max_len : b->uniform_len;
+    if (!open && maxl > kTls13MaxContent) return fail(SG_E_ARG, "TLS 1.3 content longer than 2^14 bytes%s");
+    if (open && maxl > kTls13MaxFragment) return fail(SG_E_ARG, "TLS 1.3 fragment longer than 2^14 + 256 bytes%s");
+    if (!open && b->content_type == 0)
+        return fail(SG_E_ARG, "the inner content type must be non-zero (a zero byte reads as padding)%s");
+    return SG_OK;
+}
+
+int validate_tls13(const sg_batch* b, const sg_batch_tls13* x, bool open) {
+    if (!x) return fail(SG_E_ARG, "sg_batch_tls13 is NULL%s");
+    if (x->flags) return fail(SG_E_ARG, "sg_batch_tls13.flags must be 0%s");
+    int rc = validate_tls13(b, open);
+    if (rc != SG_OK) return rc;
+    if (!x->ivs) return fail(SG_E_ARG, "the TLS 1.3 batch needs the write IVs (sg_batch_tls13.ivs)%s");
+    if (((uintptr_t)x->ivs & 3u) != 0) return fail(SG_E_ARG, "IV table must be 4-byte aligned%s");
+    if (open) {
+        if (!x->inner_type || !x->content_len)
+            return fail(SG_E_ARG, "open needs the inner_type and content_len arrays%s");
+        if (((uintptr_t)x->content_len & 3u) != 0) return fail(SG_E_ARG, "content_len must be 4-byte aligned%s");
+    }
+    const sg_batch_rfc8439 r = {x->ivs, 0u, 0u};  // ... and whatever the RFC calls reject
+    return validate(b, open, &r);
+}
+
+// The wave-per-record kernel takes uniform TLS 1.3 batches of full records, 2^14
+// content bytes (a fragment of 2^14 + 17), in the layout wpr_eligible asks for.
+bool wpr_eligible_tls13(const sg_batch* b, bool open) {
+    if (!sg::wpr_enabled() || b->len || b->in_off || b->out_off) return false;
+    if (b->uniform_len != (open ? sg::kWprN + 1u + SG_MAC_LEN : sg::kWprN)) return false;
+    if (((uintptr_t)b->key_index | (uintptr_t)b->seq) % 4u) return false;
+    return ((uintptr_t)b->in | (uintptr_t)b->out | b->in_stride | b->out_stride) % 16u == 0u;
+}
+
 // Keying + AEAD launches of one batch on stream s with workspace ws.
-int launch_batch(const sg_batch* b, const sg_batch_rfc8439* x, bool open, hipStream_t s, void* ws) {
+// t: the extension of the TLS 1.3 calls (then x holds its IVs), else NULL
+int launch_batch(const sg_batch* b, const sg_batch_rfc8439* x, const sg_batch_tls13* t, bool open, hipStream_t s,
+                 void* ws) {
     sg::KParams p;
     std::memset(&p, 0, sizeof p);
     p.keys = b->keys;
@@ -222,22 +268,25 @@ int launch_batch(const sg_batch* b, const sg_batch_rfc8439* x, bool open, hipStr
     p.uniform_len = b->uniform_len;
     p.count = b->count;
     p.tls = (b->flags & SG_BATCH_TLS) ? 1u : 0u;
-    p.ad_len = p.tls ? 13u : b->ad_len;
+    p.ad_len = t ? 5u : p.tls ? 13u : b->ad_len;
     p.ad_stride = b->ad_stride;
     p.tls_hdr = (uint32_t)b->content_type | ((uint32_t)b->ver_major << 8) | ((uint32_t)b->ver_minor << 16);
     p.rfc = x ? 1u : 0u;
     p.ivs = x ? x->ivs : nullptr;
+    p.tls13 = t ? 1u : 0u;
     const uint32_t maxl = b->len ? b->max_len : b->uniform_len;
-    const uint32_t max_n = open ? (maxl >= 16u ? maxl - 16u : 0u) : maxl;
+    // (TLS 1.3 seal: the AEAD runs over the inner plaintext, content || type)
+    const uint32_t max_n = open ? (maxl >= 16u ? maxl - 16u : 0u) : maxl + (t ? 1u : 0u);
     const bool uniform = !b->len || sg::size_class(max_n) == 0u;
-    const bool wpr = wpr_eligible(b, open);
+    const bool wpr = t ? wpr_eligible_tls13(b, open) : wpr_eligible(b, open);
     // mixed TLS batches: full-chunk records (4-16 KiB, multiples of 64 bytes)
     // go to the wave-per-record buckets; not under capture (they are launched
     // on the populations read back), and the per-record arrays are read as
     // dwords by the bucket kernels
     // (the packed kernel, sg_pack.hip, likewise takes the 64 B-4 KiB ones)
     // (either construction: the routed kernels exist in the draft and the RFC 8439 form)
-    if (!wpr && !uniform && p.tls && ((sg::wpr_enabled() && max_n > 4096u) || (sg::pack_enabled() && max_n >= 64u))) {
+    // (TLS 1.3: inner lengths of full chunks + 1 are no multiple of 64; mixed batches stay on the classes)
+    if (!wpr && !uniform && p.tls && !t && ((sg::wpr_enabled() && max_n > 4096u) || (sg::pack_enabled() && max_n >= 64u))) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         SG_HIP(hipStreamIsCapturing(s, &cap));
         const bool ok = cap == hipStreamCaptureStatusNone &&
@@ -268,6 +317,8 @@ int launch_batch(const sg_batch* b, const sg_batch_rfc8439* x, bool open, hipStr
     }
     // failed opens hand out no plaintext (chacha20_poly1305.rs:89-93)
     if (he == hipSuccess && open && !(b->flags & SG_BATCH_KEEP_FAILED)) he = sg::launch_scrub(p, s);
+    // TLS 1.3: inner type and content length of the records that opened (RFC 8446 section 5.4)
+    if (he == hipSuccess && open && t) he = sg::launch_strip(p, t->inner_type, t->content_len, s);
     if (timing) {
         if (he == hipSuccess) he = hipEventRecord(e[3], s);
         std::lock_guard<std::mutex> lk(g_timing_mu);
@@ -284,10 +335,12 @@ int launch_batch(const sg_batch* b, const sg_batch_rfc8439* x, bool open, hipStr
     return SG_OK;
 }
 
-int run_batch(const sg_batch* b, bool open, const sg_batch_rfc8439* x = nullptr) {
+int run_batch(const sg_batch* b, bool open, const sg_batch_rfc8439* x = nullptr, const sg_batch_tls13* t = nullptr) {
     sg::routes_reset();  // sg_last_batch_routes speaks of this call from here on
-    int rc = validate(b, open, x);
+    int rc = t ? validate_tls13(b, t, open) : validate(b, open, x);
     if (rc != SG_OK || b->count == 0) return rc;
+    const sg_batch_rfc8439 t_ivs = {t ? t->ivs : nullptr, 0u, 0u};
+    if (t) x = &t_ivs;
 
     int dev = 0;
     SG_HIP(hipGetDevice(&dev));
@@ -315,7 +368,7 @@ int run_batch(const sg_batch* b, bool open, const sg_batch_rfc8439* x = nullptr)
         if ((rc = ws_acquire(d, need, s, &cws)) != SG_OK) return rc;
         ws = cws->ptr;
     }
-    rc = launch_batch(b, x, open, s, ws);
+    rc = launch_batch(b, x, t, open, s, ws);
     if (cws) ws_release(cws, s, true);
     // NULL stream: the call returns when the batch is done, whatever it returns
     if (!b->stream) {
@@ -509,6 +562,18 @@ static int run_batch_rfc8439(const sg_batch* b, const sg_batch_rfc8439* x, bool 
 }
 int sg_seal_batch_rfc8439(const sg_batch* b, const sg_batch_rfc8439* x) { return run_batch_rfc8439(b, x, false); }
 int sg_open_batch_rfc8439(const sg_batch* b, const sg_batch_rfc8439* x) { return run_batch_rfc8439(b, x, true); }
+
+static int run_batch_tls13(const sg_batch* b, const sg_batch_tls13* x, bool open) {
+    if (!x) return fail(SG_E_ARG, "sg_batch_tls13 is NULL%s");
+    return run_batch(b, open, nullptr, x);
+}
+int sg_seal_batch_tls13(const sg_batch* b, const sg_batch_tls13* x) { return run_batch_tls13(b, x, false); }
+int sg_open_batch_tls13(const sg_batch* b, const sg_batch_tls13* x) { return run_batch_tls13(b, x, true); }
+int sg_batch_tls13_route(const sg_batch* b, int open) {
+    const int rc = validate_tls13(b, open != 0);
+    if (rc != SG_OK) return rc;
+    return wpr_eligible_tls13(b, open != 0) ? 1 : 0;
+}
 
 int sg_fill_records(uint8_t* buf, uint64_t stride, uint32_t len, uint32_t count, uint64_t seed, uint64_t j0,
                     void* stream) {

@@ -488,6 +488,15 @@ __device__ __forceinline__ uint8_t tls_ad_byte(uint64_t seq, uint32_t hdr, uint3
     return (uint8_t)n;
 }
 
+// AD byte i (< 5) of a TLS 1.3 record (RFC 8446 section 5.2): the record header
+// opaque_type 23 || legacy_record_version 03 03 || be16(L), L the fragment length
+__device__ __forceinline__ uint8_t tls13_ad_byte(uint32_t L, uint32_t i) {
+    if (i == 0) return 0x17u;
+    if (i < 3) return 0x03u;
+    if (i == 3) return (uint8_t)(L >> 8);
+    return (uint8_t)L;
+}
+
 // Byte i (< ct_offset<C>(adlen)) of the MAC stream in front of the ciphertext:
 // ad || le64(|ad|) in the draft (chacha20_poly1305.rs:24-26), ad and its zero
 // padding in RFC 8439.

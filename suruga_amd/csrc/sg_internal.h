@@ -83,6 +83,9 @@ struct KParams {
     // RFC 8439 record batch (sg_*_batch_rfc8439); at the end: the offsets above stay
     const uint8_t* ivs;      // TLS mode under rfc: write IVs [num_keys][12] (RFC 7905), 4-byte aligned
     uint32_t rfc;            // 1 = RFC 8439 (Construction::kRfc8439 kernels), 0 = the draft
+    // TLS 1.3 record batch (sg_*_batch_tls13, RFC 8446 section 5.2); at the end again
+    uint32_t tls13;          // 1: rfc and tls are 1 too; AD = 17 03 03 be16(fragment length), seal appends
+                             // the inner type byte (tls_hdr's low byte) to every record
 };
 
 // Every record kernel exists in both constructions (Construction,
@@ -99,6 +102,15 @@ inline void with_form(bool rfc, bool open, F&& f) {
     constexpr std::integral_constant<Construction, Construction::kRfc8439> R{};
     if (rfc) open ? f(std::true_type{}, R) : f(std::false_type{}, R);
     else open ? f(std::true_type{}, D) : f(std::false_type{}, D);
+}
+
+// ... and with the TLS 1.3 record form (KParams.tls13; T13.value a bool, true only
+// with Construction::kRfc8439) as a third constant: f(OPEN, C, T13).
+template <class F>
+inline void with_form13(const KParams& p, bool open, F&& f) {
+    constexpr std::integral_constant<Construction, Construction::kRfc8439> R{};
+    if (p.tls13) open ? f(std::true_type{}, R, std::true_type{}) : f(std::false_type{}, R, std::true_type{});
+    else with_form(p.rfc != 0u, open, [&](auto OPEN, auto C) { f(OPEN, C, std::false_type{}); });
 }
 
 // Size classes of the AEAD kernel: class c (0..7) holds records of
@@ -141,6 +153,10 @@ __host__ __device__ inline uint32_t lds_rec_bytes(uint32_t cls, uint32_t adlen, 
 // gives every record but a stream's tail), 16-byte aligned strided layout, any
 // AD length.  One wave per record, eight records per 512-thread workgroup.
 constexpr uint32_t kWprN = 16384;
+// TLS 1.3 (KParams.tls13): full records of 2^14 content bytes and the inner type
+// byte, n = 16385.  The record kernel runs the 2^14 bytes as above; the keying
+// kernel takes byte 2^14 (keystream block 257) and its MAC block.
+constexpr uint32_t kWprTailBlock = kWprN / 64u + 1u;
 // Workspace (u32 words) for a batch of `count` records:
 //   [0, 88 count)                   size-class keying records (by record index)
 //   [88 count, 248 count)           wave-per-record keying records (by slot)
@@ -246,6 +262,9 @@ void routes_get(uint32_t out[kRouteWords]);
 // ---- sg_plumb.hip ----
 // zero the output of every record whose open status is 1 (wrong mac)
 hipError_t launch_scrub(const KParams& p, hipStream_t s);
+// TLS 1.3 open: the inner type and content length of every record whose status
+// is 0 (status 5 where the inner plaintext holds no non-zero byte)
+hipError_t launch_strip(const KParams& p, uint8_t* inner_type, uint32_t* content_len, hipStream_t s);
 // record-layer framing in HBM (sg_record.cpp zero-copy path): build the wire
 // image of `count` records (pitch = 5 + frag; the last record's fragment
 // last_frag) from aligned fragment slots, or take the fragments of a wire

@@ -40,6 +40,14 @@
 // (every block is full).  The draft instantiations compile to what they were
 // before the parameter.
 //
+// T13 (KParams.tls13, sg_*_batch_tls13; with Construction::kRfc8439 only) is the
+// TLS 1.3 record form of RFC 8446 section 5.2: the AD is the 5-byte record header
+// 17 03 03 be16(fragment length) (tls13_ad_byte, sg_device.h), and on seal the
+// AEAD input is the record's content and the inner type byte behind it, one byte
+// more than the record's length: the keying and classify kernels count it, and
+// the block that holds it takes the byte path.  The instantiations without it
+// compile to what they were before the parameter.
+//
 // The launchers at the end are what the rest of the library sees of this file
 // (sg_internal.h); the dispatcher of a batch is sg_dispatch.cpp.
 #include "sg_internal.h"
@@ -117,8 +125,11 @@ __device__ __forceinline__ bool rec_pack(const KParams& p, uint32_t rec, uint32_
 // KeyJobs (sg_internal.h): njobs == 0 keys every record of the batch by
 // index; otherwise the records of up to kNumClasses lists (mixed batches key
 // only their size-class records here), job i on blocks [blk0[i], blk0[i+1]).
-template <bool OPEN, Construction C>
+// T13 (KParams.tls13, RFC 8446 section 5.2): the MAC runs over the inner
+// plaintext, one byte longer than the content on seal, behind a 5-byte AD.
+template <bool OPEN, Construction C, bool T13>
 __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const KeyJobs jobs) {
+    static_assert(!T13 || C == Construction::kRfc8439, "TLS 1.3 records are RFC 8439");
     constexpr uint32_t kKeyLdsStride = kKeyRecWords + 1;
     __shared__ uint32_t stage[kKeyingThreads * kKeyLdsStride];
     __shared__ uint32_t recs[kKeyingThreads];
@@ -139,7 +150,7 @@ __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const Ke
     recs[lane] = rec;
     uint32_t* out = stage + lane * kKeyLdsStride;
     const uint32_t len = act ? record_len(p, rec) : 0u;
-    const uint32_t n = OPEN ? (len >= 16u ? len - 16u : 0u) : len;
+    const uint32_t n = OPEN ? (len >= 16u ? len - 16u : 0u) : len + (T13 ? 1u : 0u);
     out[kKeyRecWords] = 0u;  // nothing to write unless keyed below
     if (act) {
         const RecKey rk = record_key<C>(p, rec);
@@ -154,7 +165,7 @@ __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const Ke
         out[kSOff + 1] = pk.s[1];
         out[kSOff + 2] = pk.s[2];
         out[kSOff + 3] = pk.s[3];
-        const uint32_t adlen = p.tls ? 13u : p.ad_len;
+        const uint32_t adlen = T13 ? 5u : p.tls ? 13u : p.ad_len;
         const MacGeom g = mac_geom<C>(adlen, n, mac_lanes(n));
         const F26 r = words_to_f26(pk.r0, pk.r1, pk.r2, pk.r3, 0u);
         // R = r^k by square-and-multiply; then R^0..R^7 and R^0, R^8, .., R^56.
@@ -204,7 +215,10 @@ __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const Ke
 // otherwise); PL = min(L, 64) of them run the MAC.  Per record, in LDS:
 //   [0, S) virtual-block space | S: ad | le64(adlen) | A: ct (n) | le64(n) | zeros
 // ---------------------------------------------------------------------------
-template <bool OPEN, uint32_t L, Construction C>
+// T13 (TLS 1.3, RFC 8446 section 5.2): n is the inner plaintext length; seal
+// reads len = n - 1 content bytes and appends the inner type byte, so the block
+// that holds it takes the byte path; the AD is the 5-byte record header.
+template <bool OPEN, uint32_t L, Construction C, bool T13>
 __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec, const bool active,
                                             uint8_t* lds, const uint32_t t) {
     constexpr uint32_t PL = L < 64u ? L : 64u;
@@ -213,7 +227,7 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
     bool work = active;
     const uint32_t len = active ? record_len(p, rec) : 0u;
     if (active) {
-        n = len;
+        n = len + (T13 && !OPEN ? 1u : 0u);
         if constexpr (OPEN) {
             if (len < 16u) {  // chacha20_poly1305.rs:68-70 "message too short"
                 if (t == 0) p.status[rec] = 2u;
@@ -226,7 +240,7 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
     uint8_t* out = nullptr;
     constexpr bool RFC = C == Construction::kRfc8439;
     RecKey rk = {};
-    const uint32_t adlen = p.tls ? 13u : p.ad_len;
+    const uint32_t adlen = T13 ? 5u : p.tls ? 13u : p.ad_len;
     // RFC 8439: [Z, A) ad and its zero padding | A: ct (n) | zeros to 16 | le64(adlen) le64(n)
     // A = Z + 16 ceil(ct_offset<C>(adlen) / 16) and S = A - ct_offset<C>(adlen) (sg_layout.h), spelt by
     // hand: taken from the header, 76 of this file's 102 kernels came out with other instructions
@@ -248,7 +262,7 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
         if constexpr (L >= 64u) pre = chacha_pre(rk.k, rk.n13, rk.n14, rk.n15);
         for (uint32_t b = t; b < nblocks; b += L) {
             const uint32_t off = b << 6;
-            if (vec_ok && off + 64u <= n) {
+            if (vec_ok && off + 64u <= (T13 && !OPEN ? len : n)) {
                 const u32x4 d0 = ld16(in + off), d1 = ld16(in + off + 16);
                 const u32x4 d2 = ld16(in + off + 32), d3 = ld16(in + off + 48);
                 uint32_t ks[16];
@@ -285,7 +299,9 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
                     for (uint32_t k = 0; k < 4; ++k) {
                         const uint32_t idx = off + 4u * w + k;
                         if (idx < n) {
-                            const uint8_t x = in[idx];
+                            uint8_t x;
+                            if constexpr (T13 && !OPEN) x = idx < len ? in[idx] : (uint8_t)p.tls_hdr;  // content || type
+                            else x = in[idx];
                             const uint8_t y = x ^ (uint8_t)(ks[w] >> (8u * k));
                             out[idx] = y;
                             ct_lds[idx] = OPEN ? x : y;
@@ -300,7 +316,9 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
             // ad || 0.. (to 16) || ct || 0.. (to 16) || le64(|ad|) || le64(|ct|)  (RFC 8439 section 2.8)
             for (uint32_t i = t; i < A - Z; i += PL) {
                 uint8_t v = 0u;
-                if (i < adlen)
+                if constexpr (T13) {
+                    if (i < adlen) v = tls13_ad_byte(n + 16u, i);
+                } else if (i < adlen)
                     v = p.tls ? tls_ad_byte(rk.seq, p.tls_hdr, n, i) : p.ads[(uint64_t)p.ad_stride * rec + i];
                 lds[S + i] = v;
             }
@@ -489,13 +507,13 @@ __device__ __forceinline__ uint32_t group_of_thread() {
 }
 
 // Direct launch: workgroup w serves records w*RPW .. w*RPW + RPW - 1.
-template <bool OPEN, uint32_t L, Construction C>
+template <bool OPEN, uint32_t L, Construction C, bool T13>
 __global__ __launch_bounds__(256) void sg_aead_kernel(const KParams p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     constexpr uint32_t RPW = 256u / L;
     const uint32_t g = group_of_thread<L>(), t = threadIdx.x % L;
     const uint32_t rec = blockIdx.x * RPW + g;
-    aead_record<OPEN, L, C>(p, rec, rec < p.count, lds + g * p.lds_rec_bytes, t);
+    aead_record<OPEN, L, C, T13>(p, rec, rec < p.count, lds + g * p.lds_rec_bytes, t);
 }
 
 // Bucketed launch: records listed by sg_classify_kernel for this size class.
@@ -505,7 +523,7 @@ __global__ __launch_bounds__(256) void sg_aead_kernel(const KParams p) {
 // MAC).  PERSIST = true (stream capture, where the host cannot wait): a fixed
 // grid walks the list; the barrier closing each iteration makes waves 1-3
 // wait for wave 0's MAC, ~30 % slower per byte (tools/exp_list.py).
-template <bool OPEN, uint32_t L, bool PERSIST, Construction C>
+template <bool OPEN, uint32_t L, bool PERSIST, Construction C, bool T13>
 __global__ __launch_bounds__(256) void sg_aead_list_kernel(const KParams p, const uint32_t* __restrict__ list,
                                                            const uint32_t* __restrict__ list_count) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -523,7 +541,7 @@ __global__ __launch_bounds__(256) void sg_aead_list_kernel(const KParams p, cons
         const bool active = slot < cnt;
         uint32_t rec = active ? list[slot] : 0u;
         if constexpr (L >= 64u) rec = __builtin_amdgcn_readfirstlane(rec);
-        aead_record<OPEN, L, C>(p, rec, active, lds + g * p.lds_rec_bytes, t);
+        aead_record<OPEN, L, C, T13>(p, rec, active, lds + g * p.lds_rec_bytes, t);
         if constexpr (!PERSIST) break;
         __syncthreads();  // LDS is reused by the next iteration
     }
@@ -536,7 +554,8 @@ __global__ __launch_bounds__(256) void sg_aead_list_kernel(const KParams p, cons
 constexpr uint32_t kClassifyThreads = 1024;
 constexpr uint32_t kClassifyPerThread = 4;
 
-template <bool OPEN>
+// (T13: a TLS 1.3 seal's class is that of its inner length, one byte more)
+template <bool OPEN, bool T13>
 __global__ __launch_bounds__(1024) void sg_classify_kernel(const KParams p, uint32_t* __restrict__ lists,
                                                            uint32_t* __restrict__ counts, const uint32_t max_n) {
     // counts: the kNumLists populations, then the over-long count
@@ -552,7 +571,7 @@ __global__ __launch_bounds__(1024) void sg_classify_kernel(const KParams p, uint
         cls[i] = kNumLists;
         if (rec < p.count) {
             const uint32_t len = record_len(p, rec);
-            const uint32_t n = OPEN ? (len >= 16u ? len - 16u : 0u) : len;
+            const uint32_t n = OPEN ? (len >= 16u ? len - 16u : 0u) : len + (T13 ? 1u : 0u);
             if (n <= max_n) {
                 const uint32_t J = rec_wpr_bucket(p, rec, n);
                 cls[i] = J ? kNumClasses + J - kWprMinJ : rec_pack(p, rec, n) ? kPackList : size_class(n);
@@ -596,8 +615,9 @@ __global__ __launch_bounds__(1024) void sg_classify_kernel(const KParams p, uint
 
 hipError_t launch_keying(const KParams& p, bool open, const KeyJobs& jobs, uint32_t grid, hipStream_t s) {
     if (grid == 0) return hipSuccess;
-    with_form(p.rfc, open, [&](auto OPEN, auto C) {
-        hipLaunchKernelGGL((sg_keying_kernel<OPEN.value, C.value>), dim3(grid), dim3(kKeyingThreads), 0, s, p, jobs);
+    with_form13(p, open, [&](auto OPEN, auto C, auto T13) {
+        hipLaunchKernelGGL((sg_keying_kernel<OPEN.value, C.value, T13.value>), dim3(grid), dim3(kKeyingThreads), 0, s, p,
+                           jobs);
     });
     return hipGetLastError();
 }
@@ -612,10 +632,12 @@ hipError_t launch_classify(const KParams& p, bool open, uint32_t* lists, uint32_
                            hipStream_t s) {
     const uint32_t per_wg = kClassifyThreads * kClassifyPerThread;
     const dim3 grid((p.count + per_wg - 1u) / per_wg);
-    if (open)
-        hipLaunchKernelGGL(sg_classify_kernel<true>, grid, dim3(kClassifyThreads), 0, s, p, lists, counts, max_n);
+    if (open)  // (an open's length is the fragment's in either record form)
+        hipLaunchKernelGGL((sg_classify_kernel<true, false>), grid, dim3(kClassifyThreads), 0, s, p, lists, counts, max_n);
+    else if (p.tls13)
+        hipLaunchKernelGGL((sg_classify_kernel<false, true>), grid, dim3(kClassifyThreads), 0, s, p, lists, counts, max_n);
     else
-        hipLaunchKernelGGL(sg_classify_kernel<false>, grid, dim3(kClassifyThreads), 0, s, p, lists, counts, max_n);
+        hipLaunchKernelGGL((sg_classify_kernel<false, false>), grid, dim3(kClassifyThreads), 0, s, p, lists, counts, max_n);
     return hipGetLastError();
 }
 
@@ -623,9 +645,9 @@ template <uint32_t L>
 static hipError_t launch_direct(const KParams& p, bool open, hipStream_t s) {
     constexpr uint32_t RPW = 256u / L;
     const uint32_t grid = (p.count + RPW - 1u) / RPW;
-    with_form(p.rfc, open, [&](auto OPEN, auto C) {
+    with_form13(p, open, [&](auto OPEN, auto C, auto T13) {
         const size_t lds = RPW * p.lds_rec_bytes;
-        hipLaunchKernelGGL((sg_aead_kernel<OPEN.value, L, C.value>), dim3(grid), dim3(kThreads), lds, s, p);
+        hipLaunchKernelGGL((sg_aead_kernel<OPEN.value, L, C.value, T13.value>), dim3(grid), dim3(kThreads), lds, s, p);
     });
     return hipGetLastError();
 }
@@ -642,11 +664,11 @@ static hipError_t launch_list(const KParams& p, bool open, const uint32_t* list,
     uint32_t grid = ((persist ? p.count : n_exact) + RPW - 1u) / RPW;
     const uint32_t cap = kListGridPerCU * 256u;
     if (persist && grid > cap) grid = cap;
-    with_form(p.rfc, open, [&](auto OPEN, auto C) {
+    with_form13(p, open, [&](auto OPEN, auto C, auto T13) {
         const dim3 g(grid), b(kThreads);
-        constexpr bool O = OPEN.value;
-        if (persist) hipLaunchKernelGGL((sg_aead_list_kernel<O, L, true, C.value>), g, b, lds, s, p, list, cnt);
-        else hipLaunchKernelGGL((sg_aead_list_kernel<O, L, false, C.value>), g, b, lds, s, p, list, cnt);
+        constexpr bool O = OPEN.value, T = T13.value;
+        if (persist) hipLaunchKernelGGL((sg_aead_list_kernel<O, L, true, C.value, T>), g, b, lds, s, p, list, cnt);
+        else hipLaunchKernelGGL((sg_aead_list_kernel<O, L, false, C.value, T>), g, b, lds, s, p, list, cnt);
     });
     return hipGetLastError();
 }

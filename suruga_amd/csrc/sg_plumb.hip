@@ -6,6 +6,7 @@
 //   sg_frame_kernel / sg_unframe_kernel  the record layer's wire image in HBM
 //   sg_copy_out_kernel                   (sg_record.cpp, zero-copy path)
 //   sg_scrub_kernel                      zeroes the output of failed opens
+//   sg_strip_kernel                      TLS 1.3 open: inner type and content length
 #include "sg_internal.h"
 #include "../../include/suruga_gpu.h"  // SG_HEADER_LEN (record-layer framing kernels)
 
@@ -221,11 +222,54 @@ __global__ __launch_bounds__(256) void sg_scrub_kernel(const KParams p) {
     }
 }
 
+// TLS 1.3 open (RFC 8446 section 5.2, 5.4): the inner plaintext is content ||
+// type || zeros.  One thread per record, after the open kernels and the scrub:
+// a record whose status is 0 is walked back from its end to its last non-zero
+// byte, the inner type; the bytes before it are the content.  Records carry no
+// padding as a rule, so the walk ends at its first byte; behind it, whole
+// aligned dwords of zeros are taken at a time.  The walk never leaves the
+// record's n = len - 16 output bytes.  A record of zeros alone (or an empty
+// one) has no type: status 5.  Every other record gets type 0 and length 0.
+__global__ __launch_bounds__(256) void sg_strip_kernel(const KParams p, uint8_t* __restrict__ inner_type,
+                                                       uint32_t* __restrict__ content_len) {
+    const uint32_t rec = blockIdx.x * 256u + threadIdx.x;
+    if (rec >= p.count) return;
+    uint8_t ty = 0u;
+    uint32_t cl = 0u;
+    if (p.status[rec] == 0u) {
+        const uint32_t len = record_len(p, rec);
+        uint32_t k = len >= 16u ? len - 16u : 0u;  // the bytes [0, k) are still to be looked at
+        const uint8_t* o = p.out + rec_out_off(p, rec);
+        while (k) {
+            if (k >= 4u && ((uintptr_t)(o + k) & 3u) == 0u && *reinterpret_cast<const uint32_t*>(o + k - 4u) == 0u) {
+                k -= 4u;
+                continue;
+            }
+            if (o[k - 1u]) break;
+            --k;
+        }
+        if (k) {
+            ty = o[k - 1u];
+            cl = k - 1u;
+        } else {
+            p.status[rec] = 5u;  // SG_STATUS_NO_TYPE
+        }
+    }
+    inner_type[rec] = ty;
+    content_len[rec] = cl;
+}
+
 }  // namespace
 
 hipError_t launch_scrub(const KParams& p, hipStream_t s) {
     if (p.count == 0) return hipSuccess;
     hipLaunchKernelGGL(sg_scrub_kernel, dim3((p.count + 255u) / 256u), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_strip(const KParams& p, uint8_t* inner_type, uint32_t* content_len, hipStream_t s) {
+    if (p.count == 0) return hipSuccess;
+    hipLaunchKernelGGL(sg_strip_kernel, dim3((p.count + 255u) / 256u), dim3(256), 0, s, p, inner_type, content_len);
     return hipGetLastError();
 }
 

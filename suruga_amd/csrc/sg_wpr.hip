@@ -65,6 +65,12 @@
 // constant term is wpr_geom<kRfc8439>(13, n) of the right-aligned record, with
 // the S(c) pieces of the draft's bucket keying (they depend on n / 64 alone) and
 // the same single length block (tests/test_wpr_bucket_model_rfc8439.py).
+//
+// TLS 1.3 (T13 / TLS13, sg_*_batch_tls13, uniform launches): a full record is 2^14
+// content bytes and the inner type byte.  The record kernel runs the 2^14 bytes as
+// above (delta = 1: one block more follows them) and moves only the tag, to the
+// odd address n + 1; the keying kernel takes the tail byte, keystream block 257
+// and the tail block's term of ctot (tests/test_wpr_mac_model_tls13.py).
 #include "sg_internal.h"
 #include "sg_device.h"
 #include "sg_chacha_grp.inc"  // grouped ChaCha20 double round (tools/gen_chacha_grp.py --product)
@@ -185,11 +191,21 @@ struct WprKeyJobs {
     uint32_t njobs;
 };
 
+// T13 (KParams.tls13; uniform launches of Construction::kRfc8439 only): a TLS 1.3
+// record of 2^14 content bytes and the inner type byte, n = 2^14 + 1 (RFC 8446
+// section 5.2).  The MAC stream is AD(5) || 11 zeros || 1024 ciphertext blocks ||
+// [ct byte 2^14 || 15 zeros] || le64(5) || le64(n): the record kernel's 1024 blocks
+// with one block more behind them, i.e. wpr_geom's B + 1 and delta = 1.  The
+// record kernel runs the 2^14 bytes; this kernel takes the tail over: keystream
+// block 257 beside block 0, the tail byte (seal: type ^ ks into out[2^14]; open:
+// in[2^14] ^ ks into out[2^14]) and its block (byte + 2^128) r^2 in ctot
+// (tests/test_wpr_mac_model_tls13.py).
 // (compiled for two waves per SIMD: four and more spill to scratch)
-template <bool OPEN, bool LIST, Construction C>
+template <bool OPEN, bool LIST, Construction C, bool T13>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg_wpr_keying_kernel(
     const KParams p, const WprKeyJobs jobs) {
     constexpr bool RFC = C == Construction::kRfc8439;
+    static_assert(!T13 || (RFC && !LIST), "TLS 1.3: uniform RFC 8439 launches");
     const uint32_t lane = threadIdx.x;
     WprList wl = jobs.b[0];
     uint32_t b0 = 0;
@@ -205,18 +221,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
 #pragma unroll
     for (uint32_t i = 0; i < kWprRecWords; ++i) rbuf[i] = 0u;
     uint32_t* st = rbuf + 80;  // the second half first (offsets below are half-relative)
-    const uint32_t adlen = p.tls ? 13u : p.ad_len;
+    const uint32_t adlen = T13 ? 5u : p.tls ? 13u : p.ad_len;
     if (blockIdx.x == b0 && lane == 0u) *wl.ctr = 0u;  // the record kernel's group counter
 
     const bool act = slot < wl.count;
     const uint32_t rec = LIST ? (act ? wl.list[slot] : 0u) : slot;
     uint32_t n = kWprN;
     if constexpr (LIST) n = act ? p.len[rec] - (OPEN ? 16u : 0u) : kWprN;
-    const WprGeom G = wpr_geom<C>(adlen, n);
+    WprGeom G = wpr_geom<C>(adlen, n);
+    if constexpr (T13) {  // the tail block behind the 1024 of the record kernel
+        G.B += 1u;
+        G.delta = 1u;
+    }
 
     F26 r = f26_zero();
     uint32_t s[4] = {0u, 0u, 0u, 0u};
     RecKey rk = {};
+    uint32_t tail = 0u;  // T13: ciphertext byte 2^14
     if (act) {
         rk = record_key<C>(p, rec);
         uint32_t ks[16];
@@ -224,6 +245,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
         const PolyKey pk = poly_key(ks);
         r = words_to_f26(pk.r0, pk.r1, pk.r2, pk.r3, 0u);
         s[0] = pk.s[0]; s[1] = pk.s[1]; s[2] = pk.s[2]; s[3] = pk.s[3];
+        if constexpr (T13) {
+            chacha_block(ks, rk.k, kWprTailBlock, rk.n13, rk.n14, rk.n15);  // byte 2^14 is its first
+            uint8_t* ob = p.out + p.out_stride * rec + kWprN;
+            if constexpr (OPEN) {
+                tail = p.in[p.in_stride * rec + kWprN];
+                *ob = (uint8_t)(tail ^ ks[0]);
+            } else {
+                tail = (p.tls_hdr ^ ks[0]) & 0xffu;  // the inner type (content_type)
+                *ob = (uint8_t)tail;
+            }
+        }
         if constexpr (LIST) {  // the slot's descriptor: where the record lives, its length and nonce
             const uint64_t io = rec_in_off(p, rec);
             const uint64_t oo = rec_out_off(p, rec);
@@ -347,7 +379,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
             for (uint32_t i = 0; i < 16u; ++i) {
                 const uint32_t pos = 16u * b + i;
                 // (RFC 8439: ad and its zero padding; block beta is empty, sigma = 0)
-                if (pos < G.o) w[i >> 2] |= (uint32_t)prefix_byte<C>(p, rec, rk.seq, n, adlen, pos) << (8u * (i & 3u));
+                if constexpr (T13) {  // the record header; L = n + 1 + 16
+                    if (pos < adlen) w[i >> 2] |= (uint32_t)tls13_ad_byte(kWprN + 17u, pos) << (8u * (i & 3u));
+                } else if (pos < G.o)
+                    w[i >> 2] |= (uint32_t)prefix_byte<C>(p, rec, rk.seq, n, adlen, pos) << (8u * (i & 3u));
             }
             hp = fmul_add(hp, r, words_to_f26(w[0], w[1], w[2], w[3], 0u));
         }
@@ -356,7 +391,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
     // suffix le64(n) at stream offset o + n = 16 (beta + m) + sigma: n 2^(8 sigma) split at 2^128
     // (RFC 8439: the single full block le64(adlen) || le64(n), the stream's last, at weight r)
     F26 suffix;
-    if constexpr (RFC) {
+    if constexpr (T13) {  // the tail block at r^2 (its 2^128 is in pads), then the length block
+        suffix = fmul_add(F26{tail, 0u, 0u, 0u, 0u}, r2, fmul(words_to_f26(adlen, 0u, n + 1u, 0u, 0u), r));
+    } else if constexpr (RFC) {
         suffix = fmul(words_to_f26(adlen, 0u, n, 0u, 0u), r);
     } else {
         const uint32_t wi = G.sigma >> 2, bs = 8u * (G.sigma & 3u);
@@ -513,11 +550,14 @@ struct RecDesc {
     uint32_t n13;       // RFC 8439 only (the draft's word 13 is 0)
 };
 
-template <bool OPEN, bool TLS, uint32_t J, bool LIST, Construction C>
+// TLS13 (TLS 1.3 uniform launch, see the keying kernel): the record's 2^14 bytes as
+// ever; only the tag moves behind the tail byte, to the odd address n + 1.
+template <bool OPEN, bool TLS, uint32_t J, bool LIST, Construction C, bool TLS13>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void sg_wpr_kernel(const KParams p,
                                                                                                const WprList wl) {
     static_assert(J >= 1u && J <= 4u && (LIST || J == 4u), "uniform launches are full 16 KiB records");
     constexpr bool RFC = C == Construction::kRfc8439;
+    static_assert(!TLS13 || (RFC && TLS && !LIST), "TLS 1.3: uniform RFC 8439 launches");
     constexpr uint32_t j0 = 4u - J;  // the first chunk of the right-aligned record in the 16 KiB frame
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const uint32_t wave = uniform(threadIdx.x >> 6), lane = threadIdx.x & 63u;
@@ -736,7 +776,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         // open: the received tag (chacha20_poly1305.rs:72-73) into the wave's tag
         // slot by LDS-DMA; it is read in the epilogue (a scalar load here would
         // hold up the table reads below until it returned)
-        if (OPEN && lane == 0u) dma_one(lds_rxs, inb + n);
+        // (TLS13: the tag lies at in + n + 1; the two aligned 16-byte units that hold it
+        // land in the idle descriptor slot's end and the tag slot, still one DMA)
+        if constexpr (TLS13) {
+            if (OPEN && lane < 2u) dma_one(lds_rxs - 16u, inb + n + 16u * lane);
+        } else if (OPEN && lane == 0u) dma_one(lds_rxs, inb + n);
         SG_TICK(t_tw);
         SG_ACC(0, t_rs, t_tw);  // wait for the keying table
         const uint32_t* tab = reinterpret_cast<const uint32_t*>(lines);
@@ -1144,7 +1188,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                         lane63(f.v3) + ctot.v3, lane63(f.v4) + ctot.v4};
         uint32_t tw[4];
         tag_words(fs, sk, tw);
-        if (active && lane == 0u) {
+        if constexpr (TLS13) {
+            if constexpr (!OPEN) {  // one byte per lane: exactly [n + 1, n + 17) is written
+                const uint32_t wi = lane >> 2;
+                const uint32_t w = wi == 0u ? tw[0] : wi == 1u ? tw[1] : wi == 2u ? tw[2] : tw[3];
+                if (active && lane < 16u) outb[n + 1u + lane] = (uint8_t)(w >> (8u * (lane & 3u)));
+            } else if (active && lane == 0u) {  // the tag from the aligned units, shifted by its one byte
+                const uint32_t* rxl = reinterpret_cast<const uint32_t*>(lines + kWprRxOff - 16u);
+                const uint32_t rx[4] = {__builtin_amdgcn_alignbyte(rxl[1], rxl[0], 1), __builtin_amdgcn_alignbyte(rxl[2], rxl[1], 1),
+                                        __builtin_amdgcn_alignbyte(rxl[3], rxl[2], 1), __builtin_amdgcn_alignbyte(rxl[4], rxl[3], 1)};
+                p.status[cd.rec] = tag_mismatch(rx, tw);
+            }
+        } else if (active && lane == 0u) {
             if constexpr (!OPEN) {
                 st16(outb + n, u32x4{tw[0], tw[1], tw[2], tw[3]});  // ct || tag (chacha20_poly1305.rs:55)
             } else {
@@ -1232,9 +1287,9 @@ hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_
     jobs.b[0] = wl;
     jobs.njobs = 1;
     const uint32_t kgrid = (p.count + kWprKeyThreads - 1u) / kWprKeyThreads;
-    with_form(p.rfc, open, [&](auto OPEN, auto C) {
+    with_form13(p, open, [&](auto OPEN, auto C, auto T13) {
         const dim3 g(kgrid), b(kWprKeyThreads);
-        hipLaunchKernelGGL((sg_wpr_keying_kernel<OPEN.value, false, C.value>), g, b, 0, s, p, jobs);
+        hipLaunchKernelGGL((sg_wpr_keying_kernel<OPEN.value, false, C.value, T13.value>), g, b, 0, s, p, jobs);
     });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -1242,10 +1297,14 @@ hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_
     int cus = 0;
     if ((e = device_cus(&cus)) != hipSuccess) return e;
     const uint32_t grid = wpr_grid(cus, p.count);
-    with_form(p.rfc, open, [&](auto OPEN, auto C) {
+    with_form13(p, open, [&](auto OPEN, auto C, auto T13) {
         const dim3 g(grid), b(512);
-        if (p.tls) hipLaunchKernelGGL((sg_wpr_kernel<OPEN.value, true, 4, false, C.value>), g, b, kWprWgLds, s, p, wl);
-        else hipLaunchKernelGGL((sg_wpr_kernel<OPEN.value, false, 4, false, C.value>), g, b, kWprWgLds, s, p, wl);
+        if constexpr (T13.value) {
+            hipLaunchKernelGGL((sg_wpr_kernel<OPEN.value, true, 4, false, C.value, true>), g, b, kWprWgLds, s, p, wl);
+        } else {
+            if (p.tls) hipLaunchKernelGGL((sg_wpr_kernel<OPEN.value, true, 4, false, C.value, false>), g, b, kWprWgLds, s, p, wl);
+            else hipLaunchKernelGGL((sg_wpr_kernel<OPEN.value, false, 4, false, C.value, false>), g, b, kWprWgLds, s, p, wl);
+        }
     });
     return hipGetLastError();
 }
@@ -1264,7 +1323,7 @@ hipError_t launch_wpr_keying_lists(const KParams& p, bool open, const WprList* w
     if (grid == 0) return hipSuccess;
     with_form(p.rfc, open, [&](auto OPEN, auto C) {
         const dim3 g(grid), b(kWprKeyThreads);
-        hipLaunchKernelGGL((sg_wpr_keying_kernel<OPEN.value, true, C.value>), g, b, 0, s, p, jobs);
+        hipLaunchKernelGGL((sg_wpr_keying_kernel<OPEN.value, true, C.value, false>), g, b, 0, s, p, jobs);
     });
     return hipGetLastError();
 }
@@ -1280,9 +1339,9 @@ hipError_t launch_wpr_list(const KParams& p, bool open, uint32_t J, const WprLis
         const dim3 g(grid), b(512);
         constexpr bool O = OPEN.value;
         switch (J) {
-            case 2: hipLaunchKernelGGL((sg_wpr_kernel<O, true, 2, true, C.value>), g, b, kWprWgLds, s, p, wl); break;
-            case 3: hipLaunchKernelGGL((sg_wpr_kernel<O, true, 3, true, C.value>), g, b, kWprWgLds, s, p, wl); break;
-            default: hipLaunchKernelGGL((sg_wpr_kernel<O, true, 4, true, C.value>), g, b, kWprWgLds, s, p, wl); break;
+            case 2: hipLaunchKernelGGL((sg_wpr_kernel<O, true, 2, true, C.value, false>), g, b, kWprWgLds, s, p, wl); break;
+            case 3: hipLaunchKernelGGL((sg_wpr_kernel<O, true, 3, true, C.value, false>), g, b, kWprWgLds, s, p, wl); break;
+            default: hipLaunchKernelGGL((sg_wpr_kernel<O, true, 4, true, C.value, false>), g, b, kWprWgLds, s, p, wl); break;
         }
     });
     return hipGetLastError();

@@ -21,7 +21,13 @@ kernel (rocprofv3's demangled name):
 
 bench.py prices the PMC-counted dynamic VALU of a launch with clk_per_valu
 (valu_roofline), and DESIGN.md §4.2's ISA table is this file's C1 entry.
-Usage: python tools/isa_census.py [--keep DIR]
+Usage: python tools/isa_census.py [--keep DIR] [--against profiles/isa_<parent hash>.json]
+
+--against compares this tree's census with an earlier one and writes only the
+comparison, profiles/isa_<hash>_vs_<parent hash>.json: how many of the parent's
+entries are identical in every field, the names of those that changed or are
+gone, and every new kernel with its registers, VALU, LDS and scratch (the whole
+census of a tree with every record form is some 16,000 lines).
 """
 from __future__ import annotations
 
@@ -41,6 +47,11 @@ from suruga_amd import _build  # noqa: E402
 
 FULL = ic.FULL
 DRAFT_ARG = ", (sg::Construction)0"  # Construction::kDraft as c++filt prints it
+# The record kernels that take the TLS 1.3 record form as their last template argument
+# (T13 / TLS13, a bool): "..., false>(" is the form they had before it.
+T13_KERNELS = ("sg_wpr_kernel<", "sg_wpr_keying_kernel<", "sg_aead_kernel<", "sg_aead_list_kernel<", "sg_keying_kernel<",
+               "sg_classify_kernel<")
+T13_OFF = ", false>("
 
 
 def demangle(names):
@@ -102,7 +113,31 @@ def census_file(path: Path):
     return out
 
 
+def compare(parent: dict, kernels: dict) -> dict:
+    """This tree's census entries against an earlier census's, entry by entry."""
+    def row(v):
+        r = v["resources"]
+        return {"vgpr": r.get("vgpr_count"), "sgpr": r.get("sgpr_count"), "valu": v["whole"]["valu"], "mfma": v["mfma"],
+                "lds_bytes": r.get("group_segment_fixed_size"), "scratch_bytes": r.get("private_segment_fixed_size")}
+
+    return {"parent_entries": len(parent), "identical": sum(1 for k in parent if kernels.get(k) == parent[k]),
+            "changed": sorted(k for k in parent if k in kernels and kernels[k] != parent[k]),
+            "missing": sorted(k for k in parent if k not in kernels),
+            # a kernel that only gained a template argument is its parent's entry under a longer name
+            "renamed": sum(1 for k in kernels if k not in parent and T13_OFF in k and k.replace(T13_OFF, ">(") in parent),
+            "new": {k: row(kernels[k]) for k in kernels
+                    if k not in parent and not (T13_OFF in k and k.replace(T13_OFF, ">(") in parent)}}
+
+
+def dump_compact(cmp: dict) -> str:
+    """JSON with one new kernel per line."""
+    head = {k: v for k, v in cmp.items() if k != "new"}
+    rows = ",\n".join(f"  {json.dumps(k)}: {json.dumps(v)}" for k, v in cmp["new"].items())
+    return json.dumps(head, indent=1)[:-2] + ',\n "new": {\n' + rows + "\n }\n}\n"
+
+
 def main():
+    against = Path(sys.argv[sys.argv.index("--against") + 1]) if "--against" in sys.argv else None
     keep = None
     if "--keep" in sys.argv:
         keep = Path(sys.argv[sys.argv.index("--keep") + 1])
@@ -128,9 +163,22 @@ def main():
     # draft kernel up by that name, and it is the same kernel.
     # (The message kernels share the parameter and were never looked up by a
     # shorter name: they keep their one entry.)
+    # Likewise the instantiations without the TLS 1.3 record form, which are the kernels
+    # of before that argument: listed under the name without it as well (first, so
+    # that a draft kernel also gets its shortest name).
+    for k in list(kernels):
+        if T13_OFF in k and any(f in k for f in T13_KERNELS):
+            kernels.setdefault(k.replace(T13_OFF, ">("), kernels[k])
     for k in list(kernels):
         if DRAFT_ARG in k and "sg_msg" not in k:
             kernels.setdefault(k.replace(DRAFT_ARG, ""), kernels[k])
+    if against is not None:
+        old = json.loads(against.read_text())
+        cmp = {"source_hash": src, "parent_source_hash": old["source_hash"], **compare(old["kernels"], kernels)}
+        dst = ROOT / "profiles" / f"isa_{src}_vs_{old['source_hash']}.json"
+        dst.write_text(dump_compact(cmp))
+        print(dst, cmp["identical"], "of", cmp["parent_entries"], "identical,", len(cmp["new"]), "new")
+        return
     dst = ROOT / "profiles" / f"isa_{src}.json"
     dst.write_text(json.dumps(res, indent=1) + "\n")
     print(dst)
