@@ -68,14 +68,14 @@ struct DeviceState {
 std::mutex g_mu;  // device table, workspace pool bookkeeping (never held across a launch or a wait)
 std::vector<DeviceState> g_dev;
 
-// timing
-struct TimedLaunch {
-    hipEvent_t a, b;
-    int kind;  // 0 keying, 1 seal, 2 open
+// timing: a batch's events (keying window e0 -> mid, record window mid -> e2), each in one TimedBatch or in the pool
+struct TimedBatch {
+    hipEvent_t e0, mid, e2;
+    bool open;
 };
 std::mutex g_timing_mu;
 bool g_timing = false;
-std::vector<TimedLaunch> g_timed;
+std::vector<TimedBatch> g_timed;
 std::vector<hipEvent_t> g_event_pool;
 
 hipEvent_t get_event() {  // caller holds g_timing_mu
@@ -110,6 +110,13 @@ int device_state(int dev, DeviceState** out) {
     if (!d.ok) return fail(SG_E_NODEV, "device not usable%s");
     *out = &d;
     return SG_OK;
+}
+
+int current_device_state(DeviceState** out) {
+    int dev = 0;
+    SG_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_mu);
+    return device_state(dev, out);
 }
 
 // Take a cached workspace of >= need bytes for a call on stream s (the current
@@ -156,14 +163,56 @@ void ws_release(CachedWs* w, hipStream_t s, bool launched) {
     w->held = false;
 }
 
-// x: the extension of the RFC 8439 calls (NULL: the draft calls)
-int validate(const sg_batch* b, bool open, const sg_batch_rfc8439* x) {
+using sg::RecordForm;
+// A call's record form and its extension struct's fields: built by each entry point, read from validate on.
+struct BatchForm {
+    RecordForm form;
+    uint32_t xflags = 0u;             // the extension struct's flags (must be 0)
+    const uint8_t* ivs = nullptr;     // write IVs: RFC 8439 TLS mode and TLS 1.3
+    uint8_t* inner_type = nullptr;    // TLS 1.3 open
+    uint32_t* content_len = nullptr;  // TLS 1.3 open
+};
+int known_flags(const sg_batch* b) {
+    return (b->flags & ~(SG_BATCH_TLS | SG_BATCH_KEEP_FAILED)) ? fail(SG_E_ARG, "unknown flags%s") : SG_OK;
+}
+
+// TLS 1.3 (sg_*_batch_tls13): RFC 8446 section 5.1 / 5.2 bounds of a record's content (seal) and fragment (open)
+constexpr uint32_t kTls13MaxContent = 1u << 14;
+constexpr uint32_t kTls13MaxFragment = (1u << 14) + 256u;
+// What the TLS 1.3 calls check of the batch itself: all sg_batch_tls13_route checks.
+int validate_tls13(const sg_batch* b, bool open) {
     if (!b) return fail(SG_E_ARG, "batch is NULL%s");
-    if (x) {
-        if (x->flags) return fail(SG_E_ARG, "sg_batch_rfc8439.flags must be 0%s");
-        if (((uintptr_t)x->ivs & 3u) != 0) return fail(SG_E_ARG, "IV table must be 4-byte aligned%s");
-        if (b->flags & ~(SG_BATCH_TLS | SG_BATCH_KEEP_FAILED)) return fail(SG_E_ARG, "unknown flags%s");
-        if ((b->flags & SG_BATCH_TLS) && !x->ivs)
+    if (!(b->flags & SG_BATCH_TLS))
+        return fail(SG_E_ARG, "the TLS 1.3 batch builds nonce and AD on the device: SG_BATCH_TLS must be set%s");
+    if (known_flags(b) != SG_OK) return SG_E_ARG;
+    const uint32_t maxl = b->len ? b->max_len : b->uniform_len;
+    if (!open && maxl > kTls13MaxContent) return fail(SG_E_ARG, "TLS 1.3 content longer than 2^14 bytes%s");
+    if (open && maxl > kTls13MaxFragment) return fail(SG_E_ARG, "TLS 1.3 fragment longer than 2^14 + 256 bytes%s");
+    if (!open && b->content_type == 0)
+        return fail(SG_E_ARG, "the inner content type must be non-zero (a zero byte reads as padding)%s");
+    return SG_OK;
+}
+
+// Every argument check of a batch call, in the calls' order: the RFC 8439 and TLS 1.3
+// extensions (and the batch's flags) even for an empty batch, the rest with records in it.
+int validate(const sg_batch* b, const BatchForm& f, bool open) {
+    const bool t13 = f.form == RecordForm::kTls13;
+    if (t13) {
+        if (f.xflags) return fail(SG_E_ARG, "sg_batch_tls13.flags must be 0%s");
+        if (const int rc = validate_tls13(b, open)) return rc;
+        if (!f.ivs) return fail(SG_E_ARG, "the TLS 1.3 batch needs the write IVs (sg_batch_tls13.ivs)%s");
+    }
+    if (!b) return fail(SG_E_ARG, "batch is NULL%s");
+    if (f.form != RecordForm::kDraft) {
+        if (!t13 && f.xflags) return fail(SG_E_ARG, "sg_batch_rfc8439.flags must be 0%s");
+        if (((uintptr_t)f.ivs & 3u) != 0) return fail(SG_E_ARG, "IV table must be 4-byte aligned%s");
+        if (t13 && open) {
+            if (!f.inner_type || !f.content_len)
+                return fail(SG_E_ARG, "open needs the inner_type and content_len arrays%s");
+            if (((uintptr_t)f.content_len & 3u) != 0) return fail(SG_E_ARG, "content_len must be 4-byte aligned%s");
+        }
+        if (known_flags(b) != SG_OK) return SG_E_ARG;
+        if ((b->flags & SG_BATCH_TLS) && !f.ivs)
             return fail(SG_E_ARG, "RFC 7905 TLS mode needs the write IVs (sg_batch_rfc8439.ivs)%s");
     }
     if (b->count == 0) return SG_OK;
@@ -171,7 +220,7 @@ int validate(const sg_batch* b, bool open, const sg_batch_rfc8439* x) {
     if (((uintptr_t)b->keys & 3u) != 0) return fail(SG_E_ARG, "key table must be 4-byte aligned%s");
     if (b->num_keys == 0) return fail(SG_E_ARG, "num_keys must be >= 1%s");
     if (open && !b->status) return fail(SG_E_ARG, "open requires a status array%s");
-    if (b->flags & ~(SG_BATCH_TLS | SG_BATCH_KEEP_FAILED)) return fail(SG_E_ARG, "unknown flags%s");
+    if (known_flags(b) != SG_OK) return SG_E_ARG;
     if (!(b->flags & SG_BATCH_TLS)) {
         if (!b->nonces) return fail(SG_E_ARG, "explicit mode needs nonces%s");
         if (b->ad_len > SG_MAX_AD_LEN) return fail(SG_E_ARG, "ad_len exceeds SG_MAX_AD_LEN%s");
@@ -186,67 +235,21 @@ int validate(const sg_batch* b, bool open, const sg_batch_rfc8439* x) {
     return SG_OK;
 }
 
-// The wave-per-record kernel (sg_wpr.hip) takes uniform batches of full
-// 16 KiB records in a 16-byte aligned strided layout; everything else runs on
-// the size-class kernels.
-// (RFC 8439 explicit mode reads its 12-byte nonces as three dwords: the same alignment)
-bool wpr_eligible(const sg_batch* b, bool open) {
+// The wave-per-record kernel (sg_wpr.hip) takes uniform batches of full records
+// (wpr_len: 2^14 bytes, or the fragment they seal to in this form) in a 16-byte
+// aligned strided layout; everything else runs on the size-class kernels.
+bool wpr_eligible(const sg_batch* b, RecordForm form, bool open) {
     if (!sg::wpr_enabled() || b->len || b->in_off || b->out_off) return false;
-    if (b->uniform_len != (open ? sg::kWprN + SG_MAC_LEN : sg::kWprN)) return false;
-    // per-record scalars are read as dwords: key index, sequence numbers, nonces
+    if (b->uniform_len != sg::wpr_len(form, open)) return false;
+    // per-record scalars are read as dwords: key index, sequence numbers, nonces (8 or 12 bytes)
     if (((uintptr_t)b->key_index | (uintptr_t)b->seq) % 4u) return false;
     if (!(b->flags & SG_BATCH_TLS) && (uintptr_t)b->nonces % 4u) return false;
     return ((uintptr_t)b->in | (uintptr_t)b->out | b->in_stride | b->out_stride) % 16u == 0u;
 }
 
-// TLS 1.3 record batch (sg_*_batch_tls13): RFC 8446 section 5.1 / 5.2 bounds of a
-// record's content (seal) and of its fragment (open)
-constexpr uint32_t kTls13MaxContent = 1u << 14;
-constexpr uint32_t kTls13MaxFragment = (1u << 14) + 256u;
-
-// What the TLS 1.3 calls check of the batch itself (x aside), before validate().
-int validate_tls13(const sg_batch* b, bool open) {
-    if (!b) return fail(SG_E_ARG, "batch is NULL%s");
-    if (!(b->flags & SG_BATCH_TLS))
-        return fail(SG_E_ARG, "the TLS 1.3 batch builds nonce and AD on the device: SG_BATCH_TLS must be set%s");
-    if (b->flags & ~(SG_BATCH_TLS | SG_BATCH_KEEP_FAILED)) return fail(SG_E_ARG, "unknown flags%s");
-    const uint32_t maxl = b->len ? b->max_len : b->uniform_len;
-    if (!open && maxl > kTls13MaxContent) return fail(SG_E_ARG, "TLS 1.3 content longer than 2^14 bytes%s");
-    if (open && maxl > kTls13MaxFragment) return fail(SG_E_ARG, "TLS 1.3 fragment longer than 2^14 + 256 bytes%s");
-    if (!open && b->content_type == 0)
-        return fail(SG_E_ARG, "the inner content type must be non-zero (a zero byte reads as padding)%s");
-    return SG_OK;
-}
-
-int validate_tls13(const sg_batch* b, const sg_batch_tls13* x, bool open) {
-    if (!x) return fail(SG_E_ARG, "sg_batch_tls13 is NULL%s");
-    if (x->flags) return fail(SG_E_ARG, "sg_batch_tls13.flags must be 0%s");
-    int rc = validate_tls13(b, open);
-    if (rc != SG_OK) return rc;
-    if (!x->ivs) return fail(SG_E_ARG, "the TLS 1.3 batch needs the write IVs (sg_batch_tls13.ivs)%s");
-    if (((uintptr_t)x->ivs & 3u) != 0) return fail(SG_E_ARG, "IV table must be 4-byte aligned%s");
-    if (open) {
-        if (!x->inner_type || !x->content_len)
-            return fail(SG_E_ARG, "open needs the inner_type and content_len arrays%s");
-        if (((uintptr_t)x->content_len & 3u) != 0) return fail(SG_E_ARG, "content_len must be 4-byte aligned%s");
-    }
-    const sg_batch_rfc8439 r = {x->ivs, 0u, 0u};  // ... and whatever the RFC calls reject
-    return validate(b, open, &r);
-}
-
-// The wave-per-record kernel takes uniform TLS 1.3 batches of full records, 2^14
-// content bytes (a fragment of 2^14 + 17), in the layout wpr_eligible asks for.
-bool wpr_eligible_tls13(const sg_batch* b, bool open) {
-    if (!sg::wpr_enabled() || b->len || b->in_off || b->out_off) return false;
-    if (b->uniform_len != (open ? sg::kWprN + 1u + SG_MAC_LEN : sg::kWprN)) return false;
-    if (((uintptr_t)b->key_index | (uintptr_t)b->seq) % 4u) return false;
-    return ((uintptr_t)b->in | (uintptr_t)b->out | b->in_stride | b->out_stride) % 16u == 0u;
-}
-
 // Keying + AEAD launches of one batch on stream s with workspace ws.
-// t: the extension of the TLS 1.3 calls (then x holds its IVs), else NULL
-int launch_batch(const sg_batch* b, const sg_batch_rfc8439* x, const sg_batch_tls13* t, bool open, hipStream_t s,
-                 void* ws) {
+int launch_batch(const sg_batch* b, const BatchForm& f, bool open, hipStream_t s, void* ws) {
+    const bool t13 = f.form == RecordForm::kTls13;
     sg::KParams p;
     std::memset(&p, 0, sizeof p);
     p.keys = b->keys;
@@ -268,25 +271,23 @@ int launch_batch(const sg_batch* b, const sg_batch_rfc8439* x, const sg_batch_tl
     p.uniform_len = b->uniform_len;
     p.count = b->count;
     p.tls = (b->flags & SG_BATCH_TLS) ? 1u : 0u;
-    p.ad_len = t ? 5u : p.tls ? 13u : b->ad_len;
     p.ad_stride = b->ad_stride;
     p.tls_hdr = (uint32_t)b->content_type | ((uint32_t)b->ver_major << 8) | ((uint32_t)b->ver_minor << 16);
-    p.rfc = x ? 1u : 0u;
-    p.ivs = x ? x->ivs : nullptr;
-    p.tls13 = t ? 1u : 0u;
+    p.rfc = sg::construction_of(f.form) == sg::Construction::kRfc8439 ? 1u : 0u;  // the form, for the kernels:
+    p.tls13 = t13 ? 1u : 0u;
+    p.ivs = f.ivs;
+    p.ad_len = p.tls ? sg::tls_ad_len(f.form) : b->ad_len;
     const uint32_t maxl = b->len ? b->max_len : b->uniform_len;
     // (TLS 1.3 seal: the AEAD runs over the inner plaintext, content || type)
-    const uint32_t max_n = open ? (maxl >= 16u ? maxl - 16u : 0u) : maxl + (t ? 1u : 0u);
+    const uint32_t max_n = open ? (maxl >= 16u ? maxl - 16u : 0u) : maxl + sg::seal_extra(f.form);
     const bool uniform = !b->len || sg::size_class(max_n) == 0u;
-    const bool wpr = t ? wpr_eligible_tls13(b, open) : wpr_eligible(b, open);
-    // mixed TLS batches: full-chunk records (4-16 KiB, multiples of 64 bytes)
-    // go to the wave-per-record buckets; not under capture (they are launched
-    // on the populations read back), and the per-record arrays are read as
-    // dwords by the bucket kernels
-    // (the packed kernel, sg_pack.hip, likewise takes the 64 B-4 KiB ones)
-    // (either construction: the routed kernels exist in the draft and the RFC 8439 form)
-    // (TLS 1.3: inner lengths of full chunks + 1 are no multiple of 64; mixed batches stay on the classes)
-    if (!wpr && !uniform && p.tls && !t && ((sg::wpr_enabled() && max_n > 4096u) || (sg::pack_enabled() && max_n >= 64u))) {
+    const bool wpr = wpr_eligible(b, f.form, open);
+    // mixed TLS batches: full-chunk records (4-16 KiB, multiples of 64 bytes) go to the
+    // wave-per-record buckets and the 64 B-4 KiB ones to the packed kernel (sg_pack.hip), in
+    // either construction; not under capture (they are launched on the populations read
+    // back), and the per-record arrays are read as dwords by the routed kernels
+    // (TLS 1.3: inner lengths of full chunks + 1 are no multiple of 64; the routed launchers refuse the form)
+    if (!wpr && !uniform && p.tls && !t13 && ((sg::wpr_enabled() && max_n > 4096u) || (sg::pack_enabled() && max_n >= 64u))) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         SG_HIP(hipStreamIsCapturing(s, &cap));
         const bool ok = cap == hipStreamCaptureStatusNone &&
@@ -296,7 +297,7 @@ int launch_batch(const sg_batch* b, const sg_batch_rfc8439* x, const sg_batch_tl
         p.pack_mix = ok && sg::pack_enabled();
     }
 
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};  // start, between keying and records, end
     bool timing = false;
     {
         std::lock_guard<std::mutex> lk(g_timing_mu);
@@ -309,47 +310,30 @@ int launch_batch(const sg_batch* b, const sg_batch_rfc8439* x, const sg_batch_tl
     // other records' launches (and the timing bookkeeping) still follow it.
     uint32_t over = 0;
     hipError_t he = timing ? hipEventRecord(e[0], s) : hipSuccess;
-    if (he == hipSuccess) {
-        if (wpr)
-            he = sg::launch_wpr(p, open, s, timing ? e[1] : nullptr, timing ? e[2] : nullptr);
-        else
-            he = sg::launch_aead(p, open, max_n, uniform, s, &over, timing ? e[1] : nullptr, timing ? e[2] : nullptr);
-    }
+    if (he == hipSuccess) he = wpr ? sg::launch_wpr(p, open, s, e[1]) : sg::launch_aead(p, open, max_n, uniform, s, &over, e[1]);
     // failed opens hand out no plaintext (chacha20_poly1305.rs:89-93)
     if (he == hipSuccess && open && !(b->flags & SG_BATCH_KEEP_FAILED)) he = sg::launch_scrub(p, s);
     // TLS 1.3: inner type and content length of the records that opened (RFC 8446 section 5.4)
-    if (he == hipSuccess && open && t) he = sg::launch_strip(p, t->inner_type, t->content_len, s);
+    if (he == hipSuccess && open && t13) he = sg::launch_strip(p, f.inner_type, f.content_len, s);
     if (timing) {
-        if (he == hipSuccess) he = hipEventRecord(e[3], s);
+        if (he == hipSuccess) he = hipEventRecord(e[2], s);
         std::lock_guard<std::mutex> lk(g_timing_mu);
-        if (he == hipSuccess) {
-            g_timed.push_back({e[0], e[1], 0});
-            g_timed.push_back({e[2], e[3], open ? 2 : 1});
-        } else {
-            for (auto x : e)
-                if (x) g_event_pool.push_back(x);
-        }
+        if (he == hipSuccess) g_timed.push_back({e[0], e[1], e[2], open});
+        for (auto x : e)
+            if (he != hipSuccess && x) g_event_pool.push_back(x);
     }
     if (he != hipSuccess) return hip_fail(he, "batch launch");
     if (over) return fail(SG_E_ARG, "records longer than max_len were not processed%s");
     return SG_OK;
 }
 
-int run_batch(const sg_batch* b, bool open, const sg_batch_rfc8439* x = nullptr, const sg_batch_tls13* t = nullptr) {
+int run_batch(const sg_batch* b, const BatchForm& f, bool open) {
     sg::routes_reset();  // sg_last_batch_routes speaks of this call from here on
-    int rc = t ? validate_tls13(b, t, open) : validate(b, open, x);
+    int rc = validate(b, f, open);
     if (rc != SG_OK || b->count == 0) return rc;
-    const sg_batch_rfc8439 t_ivs = {t ? t->ivs : nullptr, 0u, 0u};
-    if (t) x = &t_ivs;
 
-    int dev = 0;
-    SG_HIP(hipGetDevice(&dev));
     DeviceState* d = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        rc = device_state(dev, &d);
-    }
-    if (rc != SG_OK) return rc;
+    if ((rc = current_device_state(&d)) != SG_OK) return rc;
     // NULL = the null stream: ordered after the caller's earlier work on it
     // (torch's default stream is the null stream), and the call is synchronous
     hipStream_t s = (hipStream_t)b->stream;
@@ -368,7 +352,7 @@ int run_batch(const sg_batch* b, bool open, const sg_batch_rfc8439* x = nullptr,
         if ((rc = ws_acquire(d, need, s, &cws)) != SG_OK) return rc;
         ws = cws->ptr;
     }
-    rc = launch_batch(b, x, t, open, s, ws);
+    rc = launch_batch(b, f, open, s, ws);
     if (cws) ws_release(cws, s, true);
     // NULL stream: the call returns when the batch is done, whatever it returns
     if (!b->stream) {
@@ -383,14 +367,8 @@ int run_batch(const sg_batch* b, bool open, const sg_batch_rfc8439* x = nullptr,
 namespace sg {
 
 int scratch_acquire(size_t need, hipStream_t s, void** ptr, void** handle) {
-    int dev = 0;
-    SG_HIP(hipGetDevice(&dev));
     DeviceState* d = nullptr;
-    int rc;
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        rc = device_state(dev, &d);
-    }
+    int rc = current_device_state(&d);
     if (rc != SG_OK) return rc;
     CachedWs* w = nullptr;
     if ((rc = ws_acquire(d, need, s, &w)) != SG_OK) return rc;
@@ -553,26 +531,26 @@ int sg_open(sg_ctx* c, const uint8_t* nonce, size_t nonce_len, const uint8_t* in
     return single(c, true, nonce, nonce_len, in, in_len, ad, adlen, out);
 }
 
-int sg_seal_batch(const sg_batch* b) { return run_batch(b, false); }
-int sg_open_batch(const sg_batch* b) { return run_batch(b, true); }
+int sg_seal_batch(const sg_batch* b) { return run_batch(b, {RecordForm::kDraft}, false); }
+int sg_open_batch(const sg_batch* b) { return run_batch(b, {RecordForm::kDraft}, true); }
 
 static int run_batch_rfc8439(const sg_batch* b, const sg_batch_rfc8439* x, bool open) {
     if (!x) return fail(SG_E_ARG, "sg_batch_rfc8439 is NULL%s");
-    return run_batch(b, open, x);
+    return run_batch(b, {RecordForm::kRfc8439, x->flags, x->ivs}, open);
 }
 int sg_seal_batch_rfc8439(const sg_batch* b, const sg_batch_rfc8439* x) { return run_batch_rfc8439(b, x, false); }
 int sg_open_batch_rfc8439(const sg_batch* b, const sg_batch_rfc8439* x) { return run_batch_rfc8439(b, x, true); }
 
 static int run_batch_tls13(const sg_batch* b, const sg_batch_tls13* x, bool open) {
     if (!x) return fail(SG_E_ARG, "sg_batch_tls13 is NULL%s");
-    return run_batch(b, open, nullptr, x);
+    return run_batch(b, {RecordForm::kTls13, x->flags, x->ivs, x->inner_type, x->content_len}, open);
 }
 int sg_seal_batch_tls13(const sg_batch* b, const sg_batch_tls13* x) { return run_batch_tls13(b, x, false); }
 int sg_open_batch_tls13(const sg_batch* b, const sg_batch_tls13* x) { return run_batch_tls13(b, x, true); }
 int sg_batch_tls13_route(const sg_batch* b, int open) {
     const int rc = validate_tls13(b, open != 0);
     if (rc != SG_OK) return rc;
-    return wpr_eligible_tls13(b, open != 0) ? 1 : 0;
+    return wpr_eligible(b, RecordForm::kTls13, open != 0) ? 1 : 0;
 }
 
 int sg_fill_records(uint8_t* buf, uint64_t stride, uint32_t len, uint32_t count, uint64_t seed, uint64_t j0,
@@ -606,9 +584,8 @@ int sg_last_batch_routes(sg_batch_routes* out) {
 int sg_set_timing(int enable) {
     std::lock_guard<std::mutex> lk(g_timing_mu);
     for (auto& t : g_timed) {
-        (void)hipEventSynchronize(t.b);
-        g_event_pool.push_back(t.a);
-        g_event_pool.push_back(t.b);
+        (void)hipEventSynchronize(t.e2);
+        for (hipEvent_t e : {t.e0, t.mid, t.e2}) g_event_pool.push_back(e);
     }
     g_timed.clear();
     g_timing = enable != 0;
@@ -621,11 +598,12 @@ int sg_timing_read(double* seal_ms, double* open_ms, double* keying_ms, uint32_t
     double sum[3] = {0, 0, 0};
     uint32_t cnt[3] = {0, 0, 0};
     for (auto& t : g_timed) {
-        SG_HIP(hipEventSynchronize(t.b));
-        float ms = 0.f;
-        SG_HIP(hipEventElapsedTime(&ms, t.a, t.b));
-        sum[t.kind] += ms;
-        cnt[t.kind] += 1;
+        SG_HIP(hipEventSynchronize(t.e2));
+        float key_ms = 0.f, rec_ms = 0.f;
+        SG_HIP(hipEventElapsedTime(&key_ms, t.e0, t.mid));
+        SG_HIP(hipEventElapsedTime(&rec_ms, t.mid, t.e2));
+        sum[0] += key_ms, sum[t.open ? 2 : 1] += rec_ms;  // kind 0: keying, 1: seal, 2: open
+        cnt[0] += 1, cnt[t.open ? 2 : 1] += 1;
     }
     if (keying_ms) *keying_ms = cnt[0] ? sum[0] / cnt[0] : 0.0;
     if (seal_ms) *seal_ms = cnt[1] ? sum[1] / cnt[1] : 0.0;

@@ -165,13 +165,11 @@ void routes_get(uint32_t out[kRouteWords]) {
 }
 
 hipError_t launch_aead(const KParams& p, bool open, uint32_t max_n, bool uniform, hipStream_t s, uint32_t* over,
-                       hipEvent_t ev_keyed, hipEvent_t ev_start) {
+                       hipEvent_t ev_mid) {
     *over = 0;
     hipError_t e;
     if (uniform) {  // every record in one class: keying, then a direct launch
-        if ((e = launch_keying_all(p, open, s)) != hipSuccess || (e = mark(ev_keyed, s)) != hipSuccess ||
-            (e = mark(ev_start, s)) != hipSuccess)
-            return e;
+        if ((e = launch_keying_all(p, open, s)) != hipSuccess || (e = mark(ev_mid, s)) != hipSuccess) return e;
         KParams q = p;
         const uint32_t c = size_class(max_n);
         q.lds_rec_bytes = lds_rec_bytes(c, q.ad_len, max_n);
@@ -214,8 +212,8 @@ hipError_t launch_aead(const KParams& p, bool open, uint32_t max_n, bool uniform
         if ((e = hipEventRecord(pin.ev, s)) != hipSuccess) return e;
         pin.recorded = true;
         // the batch's record window starts with the packed launch
-        if ((e = mark(ev_keyed, s)) != hipSuccess || (e = mark(ev_start, s)) != hipSuccess) return e;
-        ev_keyed = ev_start = nullptr;
+        if ((e = mark(ev_mid, s)) != hipSuccess) return e;
+        ev_mid = nullptr;
         if (p.pack_mix && (e = launch_pack(p, open, lists + (uint64_t)kPackList * p.count, tail + kPackList,
                                            tail + kTailPackCtr, s)) != hipSuccess)
             return e;
@@ -280,7 +278,7 @@ hipError_t launch_aead(const KParams& p, bool open, uint32_t max_n, bool uniform
             js[1] = side[1].s;
         }
     }
-    if ((e = mark(ev_keyed, s)) != hipSuccess || (e = mark(ev_start, s)) != hipSuccess) return e;
+    if ((e = mark(ev_mid, s)) != hipSuccess) return e;
     if (p.wpr_mix && exact) {  // most chunks first
         for (int b = (int)kWprBuckets - 1; b >= 0; --b)
             if ((e = launch_wpr_list(p, open, kWprMinJ + (uint32_t)b, wl[b], js[b])) != hipSuccess) return e;

@@ -93,9 +93,11 @@ struct KParams {
 // the J = 2..4 buckets and the packed kernel, so a mixed TLS batch takes the
 // same routes (KParams.wpr_mix / pack_mix) in either.
 //
-// The launchers' one selector: calls f(OPEN, C) with the run-time pair (rfc,
-// open) as compile-time constants (OPEN.value a bool, C.value a Construction),
-// so a launcher names its kernel once, as K<OPEN.value, ..., C.value>.
+// The launchers' one selector: calls f(OPEN, C, T13) with the run-time triple
+// (open, p.rfc, p.tls13) as compile-time constants (OPEN.value and T13.value
+// bools, T13 only with C.value == Construction::kRfc8439), so a launcher names
+// its kernel once, as K<OPEN.value, ..., C.value, T13.value>; one without a TLS 1.3
+// form refuses p.tls13 and ignores T13.  The message launchers: (rfc, open), f(OPEN, C).
 template <class F>
 inline void with_form(bool rfc, bool open, F&& f) {
     constexpr std::integral_constant<Construction, Construction::kDraft> D{};
@@ -103,11 +105,8 @@ inline void with_form(bool rfc, bool open, F&& f) {
     if (rfc) open ? f(std::true_type{}, R) : f(std::false_type{}, R);
     else open ? f(std::true_type{}, D) : f(std::false_type{}, D);
 }
-
-// ... and with the TLS 1.3 record form (KParams.tls13; T13.value a bool, true only
-// with Construction::kRfc8439) as a third constant: f(OPEN, C, T13).
 template <class F>
-inline void with_form13(const KParams& p, bool open, F&& f) {
+inline void with_form(const KParams& p, bool open, F&& f) {
     constexpr std::integral_constant<Construction, Construction::kRfc8439> R{};
     if (p.tls13) open ? f(std::true_type{}, R, std::true_type{}) : f(std::false_type{}, R, std::true_type{});
     else with_form(p.rfc != 0u, open, [&](auto OPEN, auto C) { f(OPEN, C, std::false_type{}); });
@@ -152,7 +151,7 @@ __host__ __device__ inline uint32_t lds_rec_bytes(uint32_t cls, uint32_t adlen, 
 // records (n = RECORD_MAX_LEN = 2^14, tls.rs:32, the size TlsWriter::write_data
 // gives every record but a stream's tail), 16-byte aligned strided layout, any
 // AD length.  One wave per record, eight records per 512-thread workgroup.
-constexpr uint32_t kWprN = 16384;
+// (kWprN: sg_layout.h)
 // TLS 1.3 (KParams.tls13): full records of 2^14 content bytes and the inner type
 // byte, n = 16385.  The record kernel runs the 2^14 bytes as above; the keying
 // kernel takes byte 2^14 (keystream block 257) and its MAC block.
@@ -215,7 +214,7 @@ inline hipError_t mark(hipEvent_t ev, hipStream_t s) { return ev ? hipEventRecor
 bool wpr_enabled();  // sg_set_lockstep / SG_LOCKSTEP environment switch
 int set_wpr(int enable);
 // keying pre-pass + record kernel; ev_mid (may be NULL) is recorded between them
-hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_keyed, hipEvent_t ev_start);
+hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_mid);
 // wave-per-record buckets of a mixed batch (wl[b]: J = kWprMinJ + b chunks):
 // one keying launch for every bucket, then the record kernel of one bucket
 hipError_t launch_wpr_keying_lists(const KParams& p, bool open, const WprList* wl, hipStream_t s);
@@ -232,10 +231,10 @@ const char* class_kernel_config();
 // joined into s before the call returns.  The tail's over-long count receives
 // the records longer than max_n, which are skipped (open: status 3); *over
 // receives that count when the populations are read back (not under capture).
-// ev_keyed / ev_start (may be NULL) are recorded after the keying pre-passes
-// (mixed batches: after classify, before the packed launch)  (sg_dispatch.cpp)
+// ev_mid (may be NULL) is recorded once, after the keying pre-passes (mixed
+// batches: after classify, before the packed launch)  (sg_dispatch.cpp)
 hipError_t launch_aead(const KParams& p, bool open, uint32_t max_n, bool uniform, hipStream_t s, uint32_t* over,
-                       hipEvent_t ev_keyed, hipEvent_t ev_start);
+                       hipEvent_t ev_mid);
 // Eligibility of one record of a mixed batch for the wave-per-record buckets:
 // the bucket J (kWprMinJ..4) or 0.  Shared by the classify and keying kernels.
 __host__ __device__ inline uint32_t wpr_bucket_of(uint32_t n, uint64_t in_addr, uint64_t out_addr) {

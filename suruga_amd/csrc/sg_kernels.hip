@@ -615,7 +615,7 @@ __global__ __launch_bounds__(1024) void sg_classify_kernel(const KParams p, uint
 
 hipError_t launch_keying(const KParams& p, bool open, const KeyJobs& jobs, uint32_t grid, hipStream_t s) {
     if (grid == 0) return hipSuccess;
-    with_form13(p, open, [&](auto OPEN, auto C, auto T13) {
+    with_form(p, open, [&](auto OPEN, auto C, auto T13) {
         hipLaunchKernelGGL((sg_keying_kernel<OPEN.value, C.value, T13.value>), dim3(grid), dim3(kKeyingThreads), 0, s, p,
                            jobs);
     });
@@ -645,7 +645,7 @@ template <uint32_t L>
 static hipError_t launch_direct(const KParams& p, bool open, hipStream_t s) {
     constexpr uint32_t RPW = 256u / L;
     const uint32_t grid = (p.count + RPW - 1u) / RPW;
-    with_form13(p, open, [&](auto OPEN, auto C, auto T13) {
+    with_form(p, open, [&](auto OPEN, auto C, auto T13) {
         const size_t lds = RPW * p.lds_rec_bytes;
         hipLaunchKernelGGL((sg_aead_kernel<OPEN.value, L, C.value, T13.value>), dim3(grid), dim3(kThreads), lds, s, p);
     });
@@ -664,7 +664,7 @@ static hipError_t launch_list(const KParams& p, bool open, const uint32_t* list,
     uint32_t grid = ((persist ? p.count : n_exact) + RPW - 1u) / RPW;
     const uint32_t cap = kListGridPerCU * 256u;
     if (persist && grid > cap) grid = cap;
-    with_form13(p, open, [&](auto OPEN, auto C, auto T13) {
+    with_form(p, open, [&](auto OPEN, auto C, auto T13) {
         const dim3 g(grid), b(kThreads);
         constexpr bool O = OPEN.value, T = T13.value;
         if (persist) hipLaunchKernelGGL((sg_aead_list_kernel<O, L, true, C.value, T>), g, b, lds, s, p, list, cnt);

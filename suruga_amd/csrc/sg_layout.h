@@ -1,5 +1,5 @@
-// sg_layout.h -- the two AEAD constructions of the library and the geometry of
-// their MAC streams, in one place for the record kernels (sg_kernels.hip,
+// sg_layout.h -- the two AEAD constructions of the library, the geometry of
+// their MAC streams and the three record forms, in one place for the record kernels (sg_kernels.hip,
 // sg_wpr.hip, sg_pack.hip), the message kernels (sg_msg_device.h) and the
 // host-side plan (sg_msg_plan.h).  No HIP: plain constexpr functions, which
 // hipcc takes as host and device code, so the host-only programs include it too.
@@ -53,5 +53,33 @@ static_assert(ct_offset<Construction::kRfc8439>(13u) == 16u && ct_offset<Constru
 static_assert(stream_bytes<Construction::kRfc8439>(12u, 114u) == 160u, "RFC 8439 section 2.8.2");
 static_assert(stream_bytes<Construction::kRfc8439>(0u, 0u) == 16u, "RFC 8439: the length block alone");
 static_assert(stream_bytes<Construction::kRfc8439, int64_t>(13, 16384) == 16416, "RFC 7905 record, signed");
+
+// The record form of a batch call, on top of its construction: kDraft (sg_*_batch:
+// the draft, TLS 1.2 records), kRfc8439 (sg_*_batch_rfc8439: RFC 8439, in TLS mode
+// RFC 7905's nonce) and kTls13 (sg_*_batch_tls13: RFC 8439 over the inner plaintext
+// content || type of RFC 8446 section 5.2, the 5-byte record header as AD).  The host
+// layer (sg_capi.cpp) carries one such value from the entry point to KParams.rfc /
+// KParams.tls13; with_form (sg_internal.h) makes those the kernels' template arguments.
+enum class RecordForm { kDraft, kRfc8439, kTls13 };
+constexpr uint32_t kWprN = 16384;  // a full record of the wave-per-record kernel (sg_internal.h)
+
+constexpr Construction construction_of(RecordForm f) { return f == RecordForm::kDraft ? Construction::kDraft : Construction::kRfc8439; }
+// AD bytes of a TLS-mode record, and the bytes a seal adds in front of the tag
+constexpr uint32_t tls_ad_len(RecordForm f) { return f == RecordForm::kTls13 ? 5u : 13u; }
+constexpr uint32_t seal_extra(RecordForm f) { return f == RecordForm::kTls13 ? 1u : 0u; }
+// a full wave-per-record record: its content (seal), its fragment with the tag (open)
+constexpr uint32_t wpr_len(RecordForm f, bool open) { return open ? kWprN + seal_extra(f) + 16u : kWprN; }
+// One row per form: construction, TLS AD bytes, bytes in front of the tag, a full record's fragment.
+constexpr bool form_is(RecordForm f, Construction c, uint32_t ad, uint32_t extra, uint32_t fragment) {
+    return construction_of(f) == c && tls_ad_len(f) == ad && seal_extra(f) == extra && wpr_len(f, false) == 16384u &&
+           wpr_len(f, true) == fragment;
+}
+// RFC 5246 section 6.2.3.3: AD = seq_num || type || version || length, 8 + 1 + 2 + 2 bytes; records of 2^14
+// bytes (section 6.2.1) and a tag; RFC 7905 section 2: the same record under RFC 8439's AEAD
+static_assert(form_is(RecordForm::kDraft, Construction::kDraft, 13u, 0u, 16384u + 16u), "the draft's TLS 1.2 record");
+static_assert(form_is(RecordForm::kRfc8439, Construction::kRfc8439, 13u, 0u, 16384u + 16u), "RFC 7905");
+// RFC 8446 section 5.2: AD = opaque_type || legacy_record_version || length, 1 + 2 + 2 bytes, over
+// TLSInnerPlaintext = content || ContentType (|| zeros, none added here), content of 2^14 bytes (section 5.1)
+static_assert(form_is(RecordForm::kTls13, Construction::kRfc8439, 5u, 1u, 16384u + 17u), "RFC 8446 section 5.2");
 
 }  // namespace sg

@@ -520,13 +520,13 @@ void sg_pack_kernel(const KParams p, const uint32_t* __restrict__ list, const ui
 hipError_t launch_pack(const KParams& p, bool open, const uint32_t* list, const uint32_t* count, uint32_t* ctr,
                        hipStream_t s) {
     if (p.count == 0) return hipSuccess;
-    if (!p.tls) return hipErrorInvalidValue;  // the MAC geometry is the 13-byte TLS AD's
+    if (!p.tls || p.tls13) return hipErrorInvalidValue;  // the MAC geometry is the 13-byte TLS AD's
     int cus = 0;
     hipError_t e;
     if ((e = device_cus(&cus)) != hipSuccess) return e;
     const uint32_t most = (p.count + kPackRecs - 1u) / kPackRecs;
     const uint32_t grid = 3u * (uint32_t)cus < most ? 3u * (uint32_t)cus : most;  // three workgroups per CU
-    with_form(p.rfc, open, [&](auto OPEN, auto C) {
+    with_form(p, open, [&](auto OPEN, auto C, auto) {
         hipLaunchKernelGGL((sg_pack_kernel<OPEN.value, C.value>), dim3(grid), dim3(kPackThreads), 0, s, p, list, count,
                            ctr);
     });

@@ -1276,7 +1276,7 @@ static uint32_t wpr_grid(int cus, uint32_t count) {
     return grid < ngroups ? grid : ngroups;
 }
 
-hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_keyed, hipEvent_t ev_start) {
+hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_mid) {
     WprList wl;
     wl.list = nullptr;
     wl.count = p.count;
@@ -1287,30 +1287,26 @@ hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_
     jobs.b[0] = wl;
     jobs.njobs = 1;
     const uint32_t kgrid = (p.count + kWprKeyThreads - 1u) / kWprKeyThreads;
-    with_form13(p, open, [&](auto OPEN, auto C, auto T13) {
+    with_form(p, open, [&](auto OPEN, auto C, auto T13) {
         const dim3 g(kgrid), b(kWprKeyThreads);
         hipLaunchKernelGGL((sg_wpr_keying_kernel<OPEN.value, false, C.value, T13.value>), g, b, 0, s, p, jobs);
     });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if ((e = mark(ev_keyed, s)) != hipSuccess || (e = mark(ev_start, s)) != hipSuccess) return e;
+    if ((e = mark(ev_mid, s)) != hipSuccess) return e;
     int cus = 0;
     if ((e = device_cus(&cus)) != hipSuccess) return e;
     const uint32_t grid = wpr_grid(cus, p.count);
-    with_form13(p, open, [&](auto OPEN, auto C, auto T13) {
-        const dim3 g(grid), b(512);
-        if constexpr (T13.value) {
-            hipLaunchKernelGGL((sg_wpr_kernel<OPEN.value, true, 4, false, C.value, true>), g, b, kWprWgLds, s, p, wl);
-        } else {
-            if (p.tls) hipLaunchKernelGGL((sg_wpr_kernel<OPEN.value, true, 4, false, C.value, false>), g, b, kWprWgLds, s, p, wl);
-            else hipLaunchKernelGGL((sg_wpr_kernel<OPEN.value, false, 4, false, C.value, false>), g, b, kWprWgLds, s, p, wl);
-        }
+    with_form(p, open, [&](auto OPEN, auto C, auto T13) {
+        const dim3 g(grid), b(512);  // (a TLS 1.3 batch is a TLS batch)
+        if (p.tls) hipLaunchKernelGGL((sg_wpr_kernel<OPEN.value, true, 4, false, C.value, T13.value>), g, b, kWprWgLds, s, p, wl);
+        else hipLaunchKernelGGL((sg_wpr_kernel<OPEN.value, false, 4, false, C.value, false>), g, b, kWprWgLds, s, p, wl);
     });
     return hipGetLastError();
 }
 
 hipError_t launch_wpr_keying_lists(const KParams& p, bool open, const WprList* wl, hipStream_t s) {
-    if (!p.tls) return hipErrorInvalidValue;  // buckets are TLS records (of either construction)
+    if (!p.tls || p.tls13) return hipErrorInvalidValue;  // buckets are TLS 1.2 records (of either construction)
     WprKeyJobs jobs = {};
     uint32_t grid = 0;
     for (uint32_t b = 0; b < kWprBuckets; ++b) {
@@ -1321,7 +1317,7 @@ hipError_t launch_wpr_keying_lists(const KParams& p, bool open, const WprList* w
         ++jobs.njobs;
     }
     if (grid == 0) return hipSuccess;
-    with_form(p.rfc, open, [&](auto OPEN, auto C) {
+    with_form(p, open, [&](auto OPEN, auto C, auto) {
         const dim3 g(grid), b(kWprKeyThreads);
         hipLaunchKernelGGL((sg_wpr_keying_kernel<OPEN.value, true, C.value, false>), g, b, 0, s, p, jobs);
     });
@@ -1330,12 +1326,12 @@ hipError_t launch_wpr_keying_lists(const KParams& p, bool open, const WprList* w
 
 hipError_t launch_wpr_list(const KParams& p, bool open, uint32_t J, const WprList& wl, hipStream_t s) {
     if (wl.count == 0) return hipSuccess;
-    if (!p.tls || J < kWprMinJ || J > 4u) return hipErrorInvalidValue;  // buckets are TLS records of 2..4 chunks
+    if (!p.tls || p.tls13 || J < kWprMinJ || J > 4u) return hipErrorInvalidValue;  // TLS 1.2 records of 2..4 chunks
     hipError_t e;
     int cus = 0;
     if ((e = device_cus(&cus)) != hipSuccess) return e;
     const uint32_t grid = wpr_grid(cus, wl.count);
-    with_form(p.rfc, open, [&](auto OPEN, auto C) {
+    with_form(p, open, [&](auto OPEN, auto C, auto) {
         const dim3 g(grid), b(512);
         constexpr bool O = OPEN.value;
         switch (J) {

@@ -6,7 +6,8 @@ A kernel's contract is not only what it writes inside a record but that it
 writes nothing else.  The tests here start every output buffer as sentinel(),
 lay the records out with layout() (margins in front and behind, a cycle of gaps
 between the records) and compare the *whole* buffer afterwards with image():
-the sentinel with the expected bytes of every record laid over it.
+the sentinel with the expected bytes of every record laid over it.  run_whole()
+is that run for every record and message form, Outcome.check() its one check.
 
 The sentinel is position dependent, so that a stray store shows whatever it
 stores: zeros (the scrub kernels), a fill value, keystream, or the sentinel
@@ -21,6 +22,7 @@ eligible for the route it means to exercise.
 from __future__ import annotations
 
 import struct
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -145,6 +147,76 @@ def first_diff(got: np.ndarray, want: np.ndarray, rs=()):
         if rs:
             where = f"{p - rs[-1][1]} bytes behind the last record"
     return f"byte {p}: got {int(got[p]):#04x} want {int(want[p]):#04x} ({where}; {d.size} bytes differ)"
+
+
+# ---------------------------------------------------------------------------
+# one whole-buffer run: the images around a call and their one check
+# ---------------------------------------------------------------------------
+ARRAY_PAD = 64  # sentinel entries behind the `count` entries of a per-record output array
+
+
+def array_start(count: int, salt: int, dtype=np.uint8) -> np.ndarray:
+    """A per-record output array (status, inner_type, content_len) before the call:
+    count entries and ARRAY_PAD behind them, all sentinel."""
+    return sentinel(np.dtype(dtype).itemsize * (count + ARRAY_PAD), salt).view(dtype)
+
+
+@dataclass
+class Array:
+    got: np.ndarray    # the whole array after the call
+    start: np.ndarray  # ... and as it was uploaded
+
+
+@dataclass
+class Outcome:
+    """What a call left behind, whole, beside what it had to leave."""
+
+    out: np.ndarray       # the whole output buffer
+    want_out: np.ndarray
+    out_ranges: list      # the records' nominal output ranges (for the message of a difference)
+    inp: np.ndarray       # the whole input buffer (records in place write here)
+    want_inp: np.ndarray
+    in_ranges: list = ()
+    arrays: dict = field(default_factory=dict)  # name -> Array, in the order check() takes their values
+    ret: object = None    # what the call returned
+
+    def check(self, *want, where=()):
+        """The output is want_out and the input want_inp, byte for byte; array k holds
+        want[k] in its first len(want[k]) entries and is otherwise untouched (no or a
+        None want[k]: the whole array is)."""
+        d = first_diff(self.out, self.want_out, self.out_ranges)
+        assert d is None, (*where, "output", d)
+        d = first_diff(self.inp, self.want_inp, self.in_ranges)
+        assert d is None, (*where, "input", d)
+        assert len(want) <= len(self.arrays)
+        for k, (name, a) in enumerate(self.arrays.items()):
+            w = [int(v) for v in want[k]] if k < len(want) and want[k] is not None else []
+            got = a.got[:len(w)].tolist()
+            assert got == w, (*where, name, [(i, g, v) for i, (g, v) in enumerate(zip(got, w)) if g != v][:8])
+            assert a.got.shape == a.start.shape and np.array_equal(a.got[len(w):], a.start[len(w):]), (*where, name + " tail")
+
+
+def run_whole(call, inp, out, want_out, out_ranges, *, want_inp=None, in_ranges=(), arrays=None, sync=True):
+    """Upload the input image, the output buffer's start image and the named
+    per-record arrays (each 16-byte aligned: gpu_support.dev_u8), call(dev) with the
+    device tensors by name ("inp", "out", the arrays' names; all uint8), wait and
+    download everything into an Outcome.  sync=False: the function that waits and
+    returns it."""
+    import torch
+
+    from gpu_support import dev_u8, host_np
+
+    arrays = arrays or {}
+    dev = {k: dev_u8(v.view(np.uint8)) for k, v in dict(inp=inp, out=out, **arrays).items()}
+    ret = call(dev)
+
+    def finish():
+        torch.cuda.synchronize()
+        got = {k: host_np(t) for k, t in dev.items()}  # (dev: the buffers live until the work is done)
+        return Outcome(got["out"], want_out, out_ranges, got["inp"], inp if want_inp is None else want_inp, in_ranges,
+                       {k: Array(got[k].view(v.dtype), v) for k, v in arrays.items()}, ret)
+
+    return finish() if sync else finish
 
 
 # ---------------------------------------------------------------------------

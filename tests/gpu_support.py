@@ -110,12 +110,12 @@ lockstep, packed, groups = (_switch_fixture(name) for name in SWITCHES)
 # ---------------------------------------------------------------------------
 # the batch case
 # ---------------------------------------------------------------------------
-def slots(lens, align: int, skew=(0, 0)):
-    """Records one behind the other, each length (and length + 16) rounded up to
-    `align` plus skew bytes: in_off, out_off, pt_bytes, ct_bytes."""
+def slots(lens, align: int, skew=(0, 0), tail: int = 16):
+    """Records one behind the other, each length (and length + tail, what it seals
+    to) rounded up to `align` plus skew bytes: in_off, out_off, pt_bytes, ct_bytes."""
     lens = np.asarray(lens).astype(np.uint64)
     step_i = (lens + align - 1) // align * align + skew[0]
-    step_o = (lens + 16 + align - 1) // align * align + skew[1]
+    step_o = (lens + tail + align - 1) // align * align + skew[1]
     in_off = np.zeros(len(lens), dtype=np.uint64)
     out_off = np.zeros(len(lens), dtype=np.uint64)
     in_off[1:] = np.cumsum(step_i[:-1])
@@ -132,12 +132,13 @@ class BatchCase:
     choice is the product's route, so seal_args / open_args pass arrays for the
     one and uniform_len with strides for the other and never look at the lengths.
     clamp_keys: the reference takes key min(kidx, num_keys - 1), as the kernels do.
+    tail: the bytes a seal adds to a record (the tag; a TLS 1.3 record's type byte too).
     """
 
     def __init__(self, lens, pt_h, keys_h=KEY, *, in_off=None, out_off=None, strides=None, kidx=None,
                  clamp_keys=False, seq0=0, seqs=None, content_type=None, version=None, nonces_h=None, ads_h=None,
-                 adlen=None):
-        self.lens = np.asarray(lens).astype(np.uint32)
+                 adlen=None, tail=16):
+        self.lens, self.tail = np.asarray(lens).astype(np.uint32), tail
         self.count = len(self.lens)
         self.strides = strides
         if strides is not None:
@@ -163,7 +164,7 @@ class BatchCase:
 
     def out_range(self, i):
         q = int(self.out_off[i])
-        return q, q + self.n(i) + 16
+        return q, q + self.n(i) + self.tail
 
     def key(self, i) -> bytes:
         k = 0 if self.kidx is None else int(self.kidx[i])
@@ -224,11 +225,11 @@ class BatchCase:
                     out_off=dev_u64(self.out_off))
 
     def open_args(self, olens=None, max_len=None, ads_h=None) -> dict:
-        """The reverse direction: offsets (strides) swapped, lengths + 16 unless olens says otherwise."""
+        """The reverse direction: offsets (strides) swapped, lengths + tail unless olens says otherwise."""
         if self.strides is not None:
-            return dict(self.common(ads_h), uniform_len=self.n(0) + 16, in_stride=self.strides[1],
+            return dict(self.common(ads_h), uniform_len=self.n(0) + self.tail, in_stride=self.strides[1],
                         out_stride=self.strides[0])
-        olens = (self.lens + 16).astype(np.uint32) if olens is None else olens
+        olens = (self.lens + self.tail).astype(np.uint32) if olens is None else olens
         return dict(self.common(ads_h), lens=dev_u32(olens), max_len=int(olens.max()) if max_len is None else max_len,
                     in_off=dev_u64(self.out_off), out_off=dev_u64(self.in_off))
 

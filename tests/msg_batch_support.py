@@ -226,31 +226,6 @@ def gap_layout(lens):
     return [int(o) for o in off], size
 
 
-@dataclass
-class Outcome:
-    out: np.ndarray       # the whole output buffer
-    inp: np.ndarray       # the whole input buffer (in-place messages write here)
-    st: np.ndarray        # count status bytes and 64 behind them
-    want_out: np.ndarray
-    want_inp: np.ndarray
-    out_ranges: list
-    in_ranges: list
-
-    def check(self, want_st=None, where=()):
-        d = fp.first_diff(self.out, self.want_out, self.out_ranges)
-        assert d is None, (*where, "output buffer", d)
-        d = fp.first_diff(self.inp, self.want_inp, self.in_ranges)
-        assert d is None, (*where, "input buffer", d)
-        count = len(self.out_ranges)
-        if want_st is not None:
-            got = self.st[:count].tolist()
-            assert got == list(want_st), (*where, "status", [(i, a, b) for i, (a, b) in
-                                                             enumerate(zip(got, want_st)) if a != b][:5])
-        else:
-            assert (self.st[:count] == 0xFF).all(), (*where, "seal wrote a status")
-        assert (self.st[count:] == 0xFF).all(), (*where, "bytes behind the status array")
-
-
 def run(keys_h: bytes, kidx, nonces, ads, inputs, out_lens, results, *, open_: bool, layout=cycle_layout,
         in_place=(), keep=False, stream=None, workspace=None, salt: int = 0x11, strict: bool = False,
         sync: bool = True):
@@ -259,10 +234,9 @@ def run(keys_h: bytes, kidx, nonces, ads, inputs, out_lens, results, *, open_: b
     results[i] there (None: untouched).  Messages in `in_place` get out == in.
     strict: the salt is searched so that every result's first and last byte
     differ from the sentinel under them (footprint.pick_salt).
-    Returns an Outcome (with sync False: a function that waits and returns it)."""
-    import torch
-
-    from gpu_support import dev_bytes, filled, host_np
+    Returns a footprint.Outcome whose check takes the statuses (none: a seal, which
+    writes no status); with sync False, a function that waits and returns it."""
+    from gpu_support import dev_bytes, dev_u8
     from suruga_amd import msg
 
     count = len(inputs)
@@ -279,33 +253,26 @@ def run(keys_h: bytes, kidx, nonces, ads, inputs, out_lens, results, *, open_: b
     if strict:
         salt, _ = fp.pick_salt(out_size, parts, salt)
     in_img = fp.image(in_size, salt + 1, zip(in_off, inputs))
-    want_out = fp.image(out_size, salt, parts)
     want_inp = in_img.copy()
     for i in in_place:
         if results[i] is not None:
             want_inp[in_off[i]:in_off[i] + len(results[i])] = np.frombuffer(bytes(results[i]), dtype=np.uint8)
-    in_t = torch.from_numpy(in_img.copy()).cuda()
-    out_t = torch.from_numpy(fp.sentinel(out_size, salt)).cuda()
-    ad_t = torch.from_numpy(fp.image(ad_size, salt + 2, zip(ad_off, ads))).cuda()
-    st_t = filled(count + 64, 0xFF)
-    keys_t = dev_bytes(keys_h).view(-1, 32)
-    assert in_t.data_ptr() % 16 == 0 and out_t.data_ptr() % 16 == 0 and ad_t.data_ptr() % 16 == 0
-    items = [msg.MsgItem(kidx[i], nonces[i], in_t[in_off[i]:], in_t[in_off[i]:] if i in in_place else out_t[out_off[i]:],
-                         ad=ad_t[ad_off[i]:], in_len=len(inputs[i]), ad_len=len(ads[i])) for i in range(count)]
-    keep_alive = (in_t, out_t, ad_t, st_t, keys_t)
-    if open_:
-        msg.open_msgs(keys_t, items, st_t, keep_failed=keep, stream=stream, workspace=workspace)
-    else:
-        msg.seal_msgs(keys_t, items, stream=stream, workspace=workspace)
 
-    def finish():
-        torch.cuda.synchronize()
-        assert keep_alive  # (the buffers live until the work is done)
-        return Outcome(host_np(out_t), host_np(in_t), host_np(st_t), want_out, want_inp,
-                       [(out_off[i], out_off[i] + out_lens[i]) for i in range(count)],
-                       [(in_off[i], in_off[i] + in_slot[i]) for i in range(count)])
+    def call(d):
+        ad_t, keys_t = dev_u8(fp.image(ad_size, salt + 2, zip(ad_off, ads))), dev_bytes(keys_h).view(-1, 32)
+        items = [msg.MsgItem(kidx[i], nonces[i], d["inp"][in_off[i]:],
+                             d["inp"][in_off[i]:] if i in in_place else d["out"][out_off[i]:],
+                             ad=ad_t[ad_off[i]:], in_len=len(inputs[i]), ad_len=len(ads[i])) for i in range(count)]
+        if open_:
+            msg.open_msgs(keys_t, items, d["status"], keep_failed=keep, stream=stream, workspace=workspace)
+        else:
+            msg.seal_msgs(keys_t, items, stream=stream, workspace=workspace)
+        return ad_t, keys_t  # (Outcome.ret: they live until the work is done)
 
-    return finish() if sync else finish
+    return fp.run_whole(call, in_img, fp.sentinel(out_size, salt), fp.image(out_size, salt, parts),
+                        [(out_off[i], out_off[i] + out_lens[i]) for i in range(count)], want_inp=want_inp,
+                        in_ranges=[(in_off[i], in_off[i] + in_slot[i]) for i in range(count)],
+                        arrays={"status": np.full(count + fp.ARRAY_PAD, 0xFF, dtype=np.uint8)}, sync=sync)
 
 
 def seal_case(msgs):

@@ -20,11 +20,10 @@ import numpy as np
 
 import footprint as fp
 import rfc8439_ref as R
-from gpu_support import BatchCase, dev_bytes, dev_u8, host_np, slots
+from gpu_support import BatchCase, dev_bytes, slots
 
 P = (1 << 130) - 5
 M = fp.MARGIN
-STATUS_PAD = 64
 KEYS3 = R.KEYS  # three keys
 IVS3 = hashlib.sha256(b"rfc7905 iv 0").digest()[:12] + b"\xff" * 12 + hashlib.sha256(b"rfc7905 iv 2").digest()[:12]
 SEQ_EDGES = (0, 1, 2**32 - 1, 2**32, 2**64 - 1, 2**63, 0x0102030405060708, 2**32 + 1)
@@ -80,12 +79,17 @@ class RfcCase(BatchCase):
             self._expected[i] = super().expected(oracle, i)
         return self._expected[i]
 
-    def common(self, ads_h=None, ivs_h=None) -> dict:
+    def common(self, ads_h=None) -> dict:
         c = super().common(ads_h)
         c["rfc8439"] = True
         if self.tls:
-            c["ivs"] = dev_bytes(self.ivs_h if ivs_h is None else ivs_h).view(self.num_keys, 12)
+            c["ivs"] = dev_bytes(self.ivs_h).view(self.num_keys, 12)
         return c
+
+    def open_args(self, olens=None, max_len=None, ads_h=None, ivs_h=None) -> dict:
+        """BatchCase.open_args; ivs_h: other write IVs for this call."""
+        args = super().open_args(olens, max_len, ads_h)
+        return args if ivs_h is None else dict(args, ivs=dev_bytes(ivs_h).view(self.num_keys, 12))
 
     def decrypted(self, i, data: bytes) -> bytes:
         """The always-computed decryption of `data` (ct || tag) under record i's key and nonce."""
@@ -145,22 +149,16 @@ def seal_whole(case: RfcCase, *, where=(), **extra) -> bytes:
     """Seal into a sentinel buffer with margins; the whole output buffer must be the
     sentinel with every record's reference ct || tag laid over it and the input
     unchanged.  Returns the sealed bytes from the first record's base on."""
-    import torch
-
     from suruga_amd import batch as B
 
-    out_lens = case.lens.astype(np.int64) + 16
-    out_size = M + fp.round_up(_extent(case.out_off, out_lens), 16) + M
+    out_size = M + fp.round_up(_extent(case.out_off, case.lens.astype(np.int64) + 16), 16) + M
     in_img = np.concatenate([fp.sentinel(M, 0x31), np.frombuffer(case.pt_h, dtype=np.uint8), fp.sentinel(M, 0x32)])
     want = fp.image(out_size, 0x5A, [(M + int(case.out_off[i]), case.expected(REF, i)) for i in range(case.count)])
-    d_in, d_out = dev_u8(in_img), dev_u8(fp.sentinel(out_size, 0x5A))
-    B.seal(B.Batch(inp=d_in[M:], out=d_out[M:], **case.seal_args(), **extra))
-    torch.cuda.synchronize()
-    got = host_np(d_out)
     rs = [(M + lo, M + hi) for lo, hi in (case.out_range(i) for i in range(case.count))]
-    assert (d := fp.first_diff(got, want, rs)) is None, (*where, "seal output", d)
-    assert (d := fp.first_diff(host_np(d_in), in_img)) is None, (*where, "seal input changed", d)
-    return got[M:out_size - M].tobytes()
+    o = fp.run_whole(lambda d: B.seal(B.Batch(inp=d["inp"][M:], out=d["out"][M:], **case.seal_args(), **extra)),
+                     in_img, fp.sentinel(out_size, 0x5A), want, rs)
+    o.check(where=(*where, "seal"))
+    return o.out[M:out_size - M].tobytes()
 
 
 def open_whole(case: RfcCase, sealed: bytes, exp_st, *, keep=False, olens=None, where=(), ads_h=None, ivs_h=None,
@@ -169,12 +167,9 @@ def open_whole(case: RfcCase, sealed: bytes, exp_st, *, keep=False, olens=None, 
     whole output is the sentinel with, per record, the plaintext (status 0), exactly n
     zero bytes (status 1), the decryption (status 1 with keep) or nothing (status 2);
     the statuses are exp_st and the bytes behind them untouched."""
-    import torch
-
     from suruga_amd import batch as B
 
     exp_st = bytes(exp_st)
-    olens = (case.lens + 16).astype(np.uint32) if olens is None else olens
     out_size = M + fp.round_up(_extent(case.in_off, case.lens), 16) + M
     in_img = np.concatenate([fp.sentinel(M, 0x33), np.frombuffer(bytes(sealed), dtype=np.uint8), fp.sentinel(M, 0x34)])
     parts = []
@@ -184,26 +179,13 @@ def open_whole(case: RfcCase, sealed: bytes, exp_st, *, keep=False, olens=None, 
             parts.append((M + int(case.in_off[i]), case.pt(i)))
         elif exp_st[i] == 1:
             parts.append((M + int(case.in_off[i]), case.decrypted(i, sealed[lo:hi]) if keep else bytes(case.n(i))))
-    want = fp.image(out_size, 0xA5, parts)
-    d_in, d_out = dev_u8(in_img), dev_u8(fp.sentinel(out_size, 0xA5))
-    d_st = dev_u8(fp.sentinel(case.count + STATUS_PAD, 0x51))
-    if case.strides is not None:
-        args = dict(case.common(ads_h, ivs_h), uniform_len=case.n(0) + 16, in_stride=case.strides[1],
-                    out_stride=case.strides[0])
-    else:
-        from gpu_support import dev_u32, dev_u64
-
-        args = dict(case.common(ads_h, ivs_h), lens=dev_u32(olens), max_len=int(olens.max()),
-                    in_off=dev_u64(case.out_off), out_off=dev_u64(case.in_off))
-    B.open_(B.Batch(inp=d_in[M:], out=d_out[M:], status=d_st, keep_failed=keep, **args, **extra))
-    torch.cuda.synchronize()
-    st = host_np(d_st)
-    assert bytes(st[:case.count]) == exp_st, (*where, "status", [(i, int(a), b) for i, (a, b) in
-                                                                 enumerate(zip(st[:case.count], exp_st)) if a != b][:8])
-    assert np.array_equal(st[case.count:], fp.sentinel(case.count + STATUS_PAD, 0x51)[case.count:]), (*where, "status tail")
+    args = case.open_args(olens, ads_h=ads_h, ivs_h=ivs_h)
     rs = [(M + int(o), M + int(o) + int(n)) for o, n in zip(case.in_off, case.lens)]
-    assert (d := fp.first_diff(host_np(d_out), want, rs)) is None, (*where, "open output", d)
-    assert (d := fp.first_diff(host_np(d_in), in_img)) is None, (*where, "open input changed", d)
+    o = fp.run_whole(lambda d: B.open_(B.Batch(inp=d["inp"][M:], out=d["out"][M:], status=d["status"], keep_failed=keep,
+                                               **args, **extra)),
+                     in_img, fp.sentinel(out_size, 0xA5), fp.image(out_size, 0xA5, parts), rs,
+                     arrays={"status": fp.array_start(case.count, 0x51)})
+    o.check(exp_st, where=(*where, "open"))
 
 
 # ---------------------------------------------------------------------------

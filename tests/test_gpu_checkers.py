@@ -14,6 +14,11 @@ sentinel buffer (tests/footprint.py): the 8-byte path and the byte path with its
 tail guard, odd strides and bases, the stride = 0, count = 1 form of the bench's
 mixed workload, record numbers at and above 2^32, where (j0 + j) << 32 wraps,
 and seeds with the top bit set.  Gaps and the 256-byte margins stay sentinel.
+
+footprint.run_whole, the runner of every whole-buffer test, is given calls that
+write through the device tensors it hands out: the right bytes pass, and a byte
+behind the record, a changed input byte and a touched status tail each fail
+(every way its check can fail: tests/test_gpu_support_model.py, on the CPU).
 """
 from __future__ import annotations
 
@@ -211,3 +216,35 @@ def test_fill_one_long_record_with_stride_zero(gpu, oracle, base):
     for k, j0 in enumerate(FILL_J0):
         check_fill(oracle, 100003, 0, 1, base, FILL_SEEDS[k % len(FILL_SEEDS)], j0)
     check_fill(oracle, 100000, 0, 1, base, FILL_SEEDS[0], 2**32)  # a multiple of 8: the 8-byte path at base 0
+
+
+# ---------------------------------------------------------------------------
+# footprint.run_whole: upload, call, download, check
+# ---------------------------------------------------------------------------
+def test_run_whole_hands_out_the_buffers_and_sees_what_a_call_did(gpu):
+    import torch
+
+    n, size = 40, 2 * M + 48
+    rec = bytes(range(1, n + 1))
+    want, rs = fp.image(size, 0x2B, [(M, rec)]), [(M, M + n)]
+
+    def run(stray):
+        def call(d):
+            assert all(t.dtype == torch.uint8 and t.is_cuda and t.data_ptr() % 16 == 0 for t in d.values())
+            d["out"][M:M + n] = torch.frombuffer(bytearray(rec), dtype=torch.uint8).cuda()
+            d["status"][0] = 0
+            if stray:
+                d[stray[0]][stray[1]] ^= 1
+            return "rc"
+
+        return fp.run_whole(call, fp.sentinel(64, 0x2C), fp.sentinel(size, 0x2B), want, rs,
+                            arrays={"status": fp.array_start(1, 0x51)})
+
+    o = run(None)
+    o.check([0], where=("right",))
+    assert o.ret == "rc" and o.out[M:M + n].tobytes() == rec
+    for stray, label in ((("out", M + n), "output"), (("out", M - 1), "output"), (("inp", 63), "input"),
+                         (("status", 1), "status tail"), (("status", 0), "status")):
+        with pytest.raises(AssertionError) as e:
+            run(stray).check([0], where=(stray,))
+        assert e.value.args[0][:2] == (stray, label)

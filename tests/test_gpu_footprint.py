@@ -65,14 +65,19 @@ def call(gpu, batch, open_: bool) -> int:
     return rc
 
 
-def check_buffers(what, d_in, in_img, d_out, out_img, out_ranges, d_st=None, st_want=None, count=0):
-    assert (d := fp.first_diff(host(d_out), out_img, out_ranges)) is None, f"{what}: output {d}"
-    assert (d := fp.first_diff(host(d_in), in_img)) is None, f"{what}: input changed, {d}"
-    if d_st is not None:
-        st = host(d_st)
-        bad = [i for i in range(count) if st[i] != st_want[i]]
-        assert not bad, f"{what}: status of records {bad[:5]}: {[int(st[i]) for i in bad[:5]]}"
-        assert np.array_equal(st[count:], fp.sentinel(count + STATUS_PAD, 0x51)[count:]), f"{what}: status past count"
+def run_whole(gpu, what, batch_args: dict, open_, in_img, out_size, salt, parts, out_ranges, st_want=None, lead=0):
+    """One batch call on whole images (footprint.run_whole): inp / out from byte `lead` of the
+    uploaded buffers, an open's status array with its sentinel tail; returns the call's code
+    after the whole-buffer check."""
+    from suruga_amd import batch as B
+
+    count = len(out_ranges)
+    arrays = {"status": fp.array_start(count, 0x51)} if open_ else {}
+    o = fp.run_whole(lambda d: call(gpu, B.Batch(inp=d["inp"][lead:], out=d["out"][lead:], status=d.get("status"), **batch_args),
+                                    open_),
+                     in_img, fp.sentinel(out_size, salt), fp.image(out_size, salt, parts), out_ranges, arrays=arrays)
+    o.check(*([st_want] if open_ else []), where=(what,))
+    return o.ret
 
 
 # ---------------------------------------------------------------------------
@@ -82,8 +87,6 @@ def run_listed(gpu, oracle, plan, mode, expect_routes, lockstep_on=True, packed_
     """plan: footprint.Plan -- the ordinary records, a short one (status 2, with a
     nominal output range) at plan.i_short and one longer than max_len at plan.i_long.
     expect_routes(counts): asserts on the route populations of the ordinary records."""
-    from suruga_amd import batch as B
-
     all_lens, count, max_n, i_short, i_long = plan.all_lens, plan.count, plan.max_n, plan.i_short, plan.i_long
     recs = records(oracle, all_lens, mode, seq0)
     tls = mode == "tls"
@@ -96,13 +99,10 @@ def run_listed(gpu, oracle, plan, mode, expect_routes, lockstep_on=True, packed_
     salt, tries = fp.pick_salt(out_size, parts, fp.PLAN_SALT)
     assert tries <= fp.MAX_SALT_TRIES
     in_img = fp.image(in_size, 0x77, [(in_off[i], recs[i].pt) for i in range(count)])
-    out_img = fp.image(out_size, salt, parts)
-    d_in, d_out = to_dev(in_img), to_dev(fp.sentinel(out_size, salt))
     common = common_args(recs, mode, seq0)
-    rc = call(gpu, B.Batch(inp=d_in, out=d_out, lens=dev_u32(in_lens), max_len=max_n, in_off=dev_u64(in_off),
-                           out_off=dev_u64(out_off), **common), False)
+    rc = run_whole(gpu, "seal", dict(lens=dev_u32(in_lens), max_len=max_n, in_off=dev_u64(in_off), out_off=dev_u64(out_off),
+                                     **common), False, in_img, out_size, salt, parts, fp.ranges(out_off, out_lens))
     assert rc == SG_E_ARG, "seal: a record longer than max_len returns SG_E_ARG"
-    check_buffers("seal", d_in, in_img, d_out, out_img, fp.ranges(out_off, out_lens))
 
     # ---- open
     in_lens, out_lens, in_off, out_off, in_size, out_size = plan.open
@@ -114,13 +114,9 @@ def run_listed(gpu, oracle, plan, mode, expect_routes, lockstep_on=True, packed_
         salt, tries = fp.pick_salt(out_size, parts, fp.PLAN_SALT)
         assert tries <= fp.MAX_SALT_TRIES
         in_img = fp.image(in_size, 0x78, [(in_off[i], inputs[i]) for i in range(count)])
-        out_img = fp.image(out_size, salt, parts)
-        d_in, d_out = to_dev(in_img), to_dev(fp.sentinel(out_size, salt))
-        d_st = to_dev(fp.sentinel(count + STATUS_PAD, 0x51))
-        rc = call(gpu, B.Batch(inp=d_in, out=d_out, lens=d_lens, max_len=max_n + 16, in_off=d_io, out_off=d_oo,
-                               status=d_st, keep_failed=keep, **common), True)
+        rc = run_whole(gpu, what, dict(lens=d_lens, max_len=max_n + 16, in_off=d_io, out_off=d_oo, keep_failed=keep, **common),
+                       True, in_img, out_size, salt, parts, fp.ranges(out_off, out_lens), st_want)
         assert rc == SG_E_ARG, f"{what}: a record longer than max_len returns SG_E_ARG"
-        check_buffers(what, d_in, in_img, d_out, out_img, fp.ranges(out_off, out_lens), d_st, st_want, count)
 
 
 @pytest.mark.parametrize("switches", ["default", "off"])
@@ -157,8 +153,6 @@ def test_wave_per_record_buckets(gpu, oracle, lockstep, packed):
 # ---------------------------------------------------------------------------
 def run_uniform(gpu, oracle, n, count, mode, gaps, bases, want_wpr, seq0=77):
     """len = NULL; seal strides n + g -> n + 16 + g, open the reverse, buffers at base b."""
-    from suruga_amd import batch as B
-
     recs = records(oracle, [n] * max(count, max(fp.WPR_COUNTS) if n == fp.WPR_N else 0), mode, seq0)[:count]
     common = common_args(recs, mode, seq0)
 
@@ -170,15 +164,11 @@ def run_uniform(gpu, oracle, n, count, mode, gaps, bases, want_wpr, seq0=77):
         salt, tries = fp.pick_salt(out_size, parts, 0x35)
         assert tries <= fp.MAX_SALT_TRIES
         in_img = fp.image(in_size, 0x79, [(M + b + i * si, x) for i, x in enumerate(inputs)])
-        out_img = fp.image(out_size, salt, parts)
-        d_in, d_out = to_dev(in_img), to_dev(fp.sentinel(out_size, salt))
-        d_st = to_dev(fp.sentinel(count + STATUS_PAD, 0x51)) if open_ else None
-        rc = call(gpu, B.Batch(inp=d_in[M + b:], out=d_out[M + b:], uniform_len=in_len, in_stride=si, out_stride=so,
-                               status=d_st, keep_failed=keep, **common), open_)
         what = f"{what} n={n} count={count} g={g} base={b}"
+        rc = run_whole(gpu, what, dict(uniform_len=in_len, in_stride=si, out_stride=so, keep_failed=keep, **common), open_,
+                       in_img, out_size, salt, parts, [(M + b + i * so, M + b + i * so + out_len) for i in range(count)],
+                       st_want, lead=M + b)
         assert rc == SG_OK, what
-        check_buffers(what, d_in, in_img, d_out, out_img, [(M + b + i * so, M + b + i * so + out_len)
-                                                           for i in range(count)], d_st, st_want, count)
 
     for g in gaps:
         for b in bases:

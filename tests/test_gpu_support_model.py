@@ -5,12 +5,15 @@ they judge the oracle's own output laid out by two small cases -- which must
 pass -- and then the same images with one byte or one status changed, each of
 which must raise.  slots() is held against the formulas the tests wrote out
 before it existed, and the switch context manager against a stand-in library.
+footprint.Outcome.check, the one check of every whole-buffer run, judges numpy
+images of a run that went right and then each way such a run can go wrong.
 """
 from __future__ import annotations
 
 import numpy as np
 import pytest
 
+import footprint as fp
 import gpu_support as G
 
 
@@ -127,6 +130,74 @@ def test_check_opened_sees_statuses_and_outputs(built, oracle):
     G.check_opened(case, zeroed, exp_st, exp_st, keep=False)
     with pytest.raises(AssertionError):
         G.check_opened(case, flipped(ee, o + 1), exp_st, exp_st, keep=False, fill=0xEE)
+
+
+WHOLE_LENS = (5, 16, 33)
+WHOLE_ST, WHOLE_CL = (0, 1, 2), (5, 16, 70000)
+
+
+def whole_outcome():
+    """The images of an open of three records that did everything right: output between
+    margins and gaps, input, a status array and a uint32 content_len array with tails."""
+    off, _, size, _ = fp.layout(WHOLE_LENS, WHOLE_LENS)
+    want = fp.image(size, 0x21, [(o, bytes([0xC0 + i]) * n) for i, (o, n) in enumerate(zip(off, WHOLE_LENS))])
+    inp = fp.sentinel(300, 0x22)
+    st0, cl0 = fp.array_start(3, 0x51), fp.array_start(3, 0x53, np.uint32)
+    st, cl = st0.copy(), cl0.copy()
+    st[:3], cl[:3] = WHOLE_ST, WHOLE_CL
+    o = fp.Outcome(want.copy(), want, fp.ranges(off, WHOLE_LENS), inp.copy(), inp,
+                   arrays={"status": fp.Array(st, st0), "content_len": fp.Array(cl, cl0)})
+    return o, [int(x) for x in off]
+
+
+def test_whole_buffer_check_passes_on_the_right_images():
+    o, _ = whole_outcome()
+    o.check(WHOLE_ST, WHOLE_CL, where=("right",))
+    assert len(o.arrays["status"].got) == 3 + fp.ARRAY_PAD and o.arrays["content_len"].got.dtype == np.uint32
+
+
+WHOLE_FAULTS = {
+    "a wrong byte inside a record": (lambda o, off: o.out.__setitem__(off[1] + 3, o.out[off[1] + 3] ^ 1), "output", "record 1 byte 3 of 16"),
+    "a record's last byte": (lambda o, off: o.out.__setitem__(off[2] + 32, 0), "output", "record 2 byte 32 of 33"),
+    "a byte written just behind a record": (lambda o, off: o.out.__setitem__(off[1] + 16, o.out[off[1] + 16] ^ 0x80), "output",
+                                            "1 bytes before record 2, 0 behind record 1"),
+    "a byte behind the last record": (lambda o, off: o.out.__setitem__(off[2] + 33, o.out[off[2] + 33] ^ 1), "output",
+                                      "0 bytes behind the last record"),
+    "a byte in the front margin": (lambda o, off: o.out.__setitem__(0, o.out[0] ^ 1), "output", "before record 0"),
+    "a changed input byte": (lambda o, off: o.inp.__setitem__(299, o.inp[299] ^ 4), "input", "byte 299"),
+    "a wrong status": (lambda o, off: o.arrays["status"].got.__setitem__(1, 0), "status", None),
+    "a wrong content_len": (lambda o, off: o.arrays["content_len"].got.__setitem__(2, 70000 & 0xFFFF), "content_len", None),
+    "the byte behind the statuses": (lambda o, off: o.arrays["status"].got.__setitem__(3, 0), "status tail", None),
+    "the last entry of an array's tail": (lambda o, off: o.arrays["content_len"].got.__setitem__(3 + fp.ARRAY_PAD - 1, 0),
+                                          "content_len tail", None),
+}
+
+
+@pytest.mark.parametrize("fault", sorted(WHOLE_FAULTS))
+def test_whole_buffer_check_sees(fault):
+    spoil, label, detail = WHOLE_FAULTS[fault]
+    o, off = whole_outcome()
+    spoil(o, off)
+    with pytest.raises(AssertionError) as e:
+        o.check(WHOLE_ST, WHOLE_CL, where=("ctx", 7))
+    msg = e.value.args[0]
+    assert msg[:3] == ("ctx", 7, label), msg  # the caller's context, then which comparison
+    assert detail is None or detail in msg[3], msg
+
+
+def test_whole_buffer_check_wants_an_array_without_values_untouched():
+    """A seal hands check() no statuses: then the status array must be as uploaded."""
+    o, _ = whole_outcome()
+    with pytest.raises(AssertionError) as e:
+        o.check(where=("seal",))
+    assert e.value.args[0][:2] == ("seal", "status tail")
+    with pytest.raises(AssertionError) as e:
+        o.check(WHOLE_ST, where=("no lengths",))
+    assert e.value.args[0][:2] == ("no lengths", "content_len tail")
+    with pytest.raises(AssertionError):  # more values than the run has arrays
+        o.check(WHOLE_ST, WHOLE_CL, WHOLE_ST)
+    o.arrays = {}
+    o.check(where=("no arrays",))
 
 
 @pytest.mark.parametrize("align,skew", [(16, (0, 0)), (1, (0, 0)), (16, (3, 5)), (1, (3, 7))])

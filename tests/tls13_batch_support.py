@@ -18,10 +18,9 @@ import footprint as fp
 import rfc8439_ref as R
 import rfc_batch_support as S
 import tls13_ref as T
-from gpu_support import dev_bytes, dev_u8, dev_u32, dev_u64, host_np
+from gpu_support import slots
 
 M = fp.MARGIN
-PAD = 64          # sentinel entries behind the per-record output arrays
 P = S.P
 KEYS3, IVS3 = S.KEYS3, S.IVS3
 N = 1 << 14
@@ -31,37 +30,25 @@ def key_iv(k: int, ivs: bytes = IVS3, keys: bytes = KEYS3):
     return keys[32 * k:32 * k + 32], ivs[12 * k:12 * k + 12]
 
 
-def slots(lens, skew: int):
-    """Back-to-back slots of the lengths rounded up to 16, plus skew bytes: offsets, size."""
-    lens = np.asarray(lens, dtype=np.uint64)
-    step = (lens + 15) // 16 * 16 + skew
-    off = np.zeros(len(lens), dtype=np.uint64)
-    off[1:] = np.cumsum(step[:-1])
-    return off, int(off[-1] + step[-1])
+class Tls13Case(S.RfcCase):
+    """gpu_support.BatchCase through sg_*_batch_tls13: TLS mode, key, IV and sequence
+    number by index; the layout alone (the records' bytes are the caller's)."""
+
+    def common(self, ads_h=None) -> dict:
+        c = super().common(ads_h)
+        del c["rfc8439"]
+        return c
 
 
-def _layout(in_lens, out_lens, skew, strides):
-    """(in_off, in_size, out_off, out_size); strides = (in_stride, out_stride) for a uniform batch."""
-    count = len(in_lens)
+def _case(lens, tail, kidx, seqs, skew, strides, ivs, keys, ctype=23):
+    """(case, input bytes, output bytes) of a seal of records of `lens` bytes that grow
+    by `tail`: back-to-back slots of 16 bytes plus skew, or strides = (in, out)."""
+    kw = dict(kidx=np.asarray(kidx, dtype=np.uint32), seqs=np.asarray(seqs, dtype=np.uint64), ivs_h=ivs, content_type=ctype,
+              version=(3, 3), tail=tail)
     if strides is not None:
-        assert len(set(in_lens)) == 1
-        idx = np.arange(count, dtype=np.uint64)
-        return idx * strides[0], strides[0] * count, idx * strides[1], strides[1] * count
-    in_off, in_size = slots(in_lens, skew[0])
-    out_off, out_size = slots(out_lens, skew[1])
-    return in_off, in_size, out_off, out_size
-
-
-def _common(count, kidx, seqs, ivs, keys):
-    return dict(count=count, keys=dev_bytes(keys).view(3, 32), ivs=dev_bytes(ivs).view(3, 12),
-                key_index=dev_u32(np.asarray(kidx, dtype=np.uint32)), seq=dev_u64(np.asarray(seqs, dtype=np.uint64)))
-
-
-def _shape(lens, in_off, out_off, strides):
-    if strides is not None:
-        return dict(uniform_len=int(lens[0]), in_stride=strides[0], out_stride=strides[1])
-    return dict(lens=dev_u32(np.asarray(lens, dtype=np.uint32)), max_len=max(int(max(lens)), 1), in_off=dev_u64(in_off),
-                out_off=dev_u64(out_off))
+        return Tls13Case(lens, None, keys, strides=tuple(strides), **kw), strides[0] * len(lens), strides[1] * len(lens)
+    in_off, out_off, in_size, out_size = slots(lens, 16, skew, tail)
+    return Tls13Case(lens, None, keys, in_off=in_off, out_off=out_off, **kw), in_size, out_size
 
 
 def expected_sealed(contents, kidx, seqs, ctype=23, ivs=IVS3, keys=KEYS3):
@@ -81,29 +68,24 @@ def seal_whole(contents, kidx, seqs, *, ctype=23, skew=(0, 0), strides=None, wan
     the sentinel with every record's reference fragment (len + 17 bytes) laid over it and
     the input unchanged.  Returns the fragments as the device wrote them.  route: what
     sg_batch_tls13_route must say of this very batch."""
-    import torch
-
     from suruga_amd import batch as B
 
-    count = len(contents)
     lens = [len(c) for c in contents]
-    in_off, in_size, out_off, out_size = _layout(lens, [n + 17 for n in lens], skew, strides)
+    case, in_size, out_size = _case(lens, 17, kidx, seqs, skew, strides, ivs, keys, ctype)
     want = expected_sealed(contents, kidx, seqs, ctype, ivs, keys) if want is None else want
-    in_img = np.concatenate([fp.sentinel(M, 0x31), fp.image(max(in_size, 1), 0x77, [(int(o), c) for o, c in zip(in_off, contents)]),
+    in_img = np.concatenate([fp.sentinel(M, 0x31), fp.image(max(in_size, 1), 0x77, zip(case.in_off, contents)),
                              fp.sentinel(M, 0x32)])
     size = M + fp.round_up(out_size, 16) + M
-    want_img = fp.image(size, 0x5A, [(M + int(o), w) for o, w in zip(out_off, want)])
-    d_in, d_out = dev_u8(in_img), dev_u8(fp.sentinel(size, 0x5A))
-    batch = B.Batch(inp=d_in[M:], out=d_out[M:], content_type=ctype, **_common(count, kidx, seqs, ivs, keys),
-                    **_shape(lens, in_off, out_off, strides))
-    _check_route(batch, False, route)
-    B.seal_tls13(batch)
-    torch.cuda.synchronize()
-    got = host_np(d_out)
-    rs = [(M + int(o), M + int(o) + n + 17) for o, n in zip(out_off, lens)]
-    assert (d := fp.first_diff(got, want_img, rs)) is None, (*where, "seal output", d)
-    assert (d := fp.first_diff(host_np(d_in), in_img)) is None, (*where, "seal input changed", d)
-    return [got[lo:hi].tobytes() for lo, hi in rs]
+    rs = [(M + lo, M + hi) for lo, hi in map(case.out_range, range(case.count))]
+
+    def call(d):
+        batch = B.Batch(inp=d["inp"][M:], out=d["out"][M:], **case.seal_args(max(max(lens), 1)))
+        _check_route(batch, False, route)
+        B.seal_tls13(batch)
+
+    o = fp.run_whole(call, in_img, fp.sentinel(size, 0x5A), fp.image(size, 0x5A, [(lo, w) for (lo, _), w in zip(rs, want)]), rs)
+    o.check(where=(*where, "seal"))
+    return [o.out[lo:hi].tobytes() for lo, hi in rs]
 
 
 def open_whole(frags, kidx, seqs, *, skew=(0, 0), strides=None, keep=False, ivs=IVS3, keys=KEYS3, route=None, where=()):
@@ -114,43 +96,36 @@ def open_whole(frags, kidx, seqs, *, skew=(0, 0), strides=None, keep=False, ivs=
     2); status, inner_type and content_len are the reference's, and every byte behind them
     is untouched.  Returns the (status, type, content_len) triples; strides = (fragment
     stride, output stride)."""
-    import torch
-
     from suruga_amd import batch as B
 
     count = len(frags)
-    lens = [len(f) for f in frags]
-    in_off, in_size, out_off, out_size = _layout(lens, [max(n - 16, 0) for n in lens], (skew[1], skew[0]), strides)
+    flens = np.array([len(f) for f in frags], dtype=np.uint32)
+    inner = [max(int(n) - 16, 0) for n in flens]
+    # the layout of a seal of the inner plaintexts, run backwards
+    case, out_size, in_size = _case(inner, 16, kidx, seqs, skew, strides and strides[::-1], ivs, keys)
     exp = [T.open(*key_iv(int(k), ivs, keys), int(q), f) for f, k, q in zip(frags, kidx, seqs)]
     parts = []
-    for o, (st, inner, _, _) in zip(out_off, exp):
+    for o, (st, plain, _, _) in zip(case.in_off, exp):
         if st in (T.OK, T.NO_TYPE) or (st == T.BAD_MAC and keep):
-            parts.append((M + int(o), inner))
+            parts.append((M + int(o), plain))
         elif st == T.BAD_MAC:
-            parts.append((M + int(o), bytes(len(inner))))
-    in_img = np.concatenate([fp.sentinel(M, 0x33), fp.image(max(in_size, 1), 0x78, [(int(o), f) for o, f in zip(in_off, frags)]),
+            parts.append((M + int(o), bytes(len(plain))))
+    in_img = np.concatenate([fp.sentinel(M, 0x33), fp.image(max(in_size, 1), 0x78, zip(case.out_off, frags)),
                              fp.sentinel(M, 0x34)])
     size = M + fp.round_up(max(out_size, 1), 16) + M
-    want_img = fp.image(size, 0xA5, parts)
-    d_in, d_out = dev_u8(in_img), dev_u8(fp.sentinel(size, 0xA5))
-    d_st, d_ty = dev_u8(fp.sentinel(count + PAD, 0x51)), dev_u8(fp.sentinel(count + PAD, 0x52))
-    cl0 = fp.sentinel(4 * (count + PAD), 0x53).view(np.uint32)
-    d_cl = dev_u32(cl0)
-    batch = B.Batch(inp=d_in[M:], out=d_out[M:], status=d_st, inner_type=d_ty, content_len=d_cl, keep_failed=keep,
-                    **_common(count, kidx, seqs, ivs, keys), **_shape(lens, in_off, out_off, strides))
-    _check_route(batch, True, route)
-    B.open_tls13(batch)
-    torch.cuda.synchronize()
-    st, ty, cl = host_np(d_st), host_np(d_ty), host_np(d_cl).view(np.uint32)
-    got = [(int(a), int(b), int(c)) for a, b, c in zip(st[:count], ty[:count], cl[:count])]
+    rs = [(M + int(o), M + int(o) + n) for o, n in zip(case.in_off, inner)]
+
+    def call(d):
+        batch = B.Batch(inp=d["inp"][M:], out=d["out"][M:], status=d["status"], inner_type=d["inner_type"],
+                        content_len=d["content_len"], keep_failed=keep, **case.open_args(flens, max(int(flens.max()), 1)))
+        _check_route(batch, True, route)
+        B.open_tls13(batch)
+
+    o = fp.run_whole(call, in_img, fp.sentinel(size, 0xA5), fp.image(size, 0xA5, parts), rs,
+                     arrays={"status": fp.array_start(count, 0x51), "inner_type": fp.array_start(count, 0x52),
+                             "content_len": fp.array_start(count, 0x53, np.uint32)})
     want = [(s, t, c) for s, _, t, c in exp]
-    assert got == want, (*where, "status / type / length", [(i, g, w) for i, (g, w) in enumerate(zip(got, want)) if g != w][:8])
-    assert np.array_equal(st[count:], fp.sentinel(count + PAD, 0x51)[count:]), (*where, "status tail")
-    assert np.array_equal(ty[count:], fp.sentinel(count + PAD, 0x52)[count:]), (*where, "inner_type tail")
-    assert np.array_equal(cl[count:], cl0[count:]), (*where, "content_len tail")
-    rs = [(M + int(o), M + int(o) + max(n - 16, 0)) for o, n in zip(out_off, lens)]
-    assert (d := fp.first_diff(host_np(d_out), want_img, rs)) is None, (*where, "open output", d)
-    assert (d := fp.first_diff(host_np(d_in), in_img)) is None, (*where, "open input changed", d)
+    o.check(*zip(*want), where=(*where, "open"))
     return want
 
 

@@ -14,7 +14,8 @@ per message), for seal and for open:
 Time from HIP events around each call (for ``b``: around the whole loop), median
 of ``--reps`` launches after ``--warmup``; the legs alternate launch by launch in
 one process, so they share the clock the board holds, which the sampler records
-alongside.  ``spread`` of a leg is (max - min) / median over its repeats.
+alongside; every round runs them in another order (a seeded shuffle,
+tools/ab_legs.py), so that no leg always follows the same one.  ``spread`` of a leg is (max - min) / median over its repeats.
 ``a_beats_b``: (b - a) / b exceeds b's spread.
 
 Checked inside the tool: the batch's output equals the loop's byte for byte,
@@ -30,7 +31,6 @@ from __future__ import annotations
 import argparse
 import ctypes as C
 import json
-import statistics
 import sys
 import time
 from pathlib import Path
@@ -40,6 +40,8 @@ import numpy as np
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
+
+import ab_legs  # noqa: E402  (tools/, this script's directory)
 
 ADLEN = 13
 NUM_KEYS = 4
@@ -61,19 +63,12 @@ def lengths_of(shape: str):
     return out
 
 
-def summary(ms: list, n: int) -> dict:
-    med = statistics.median(ms)
-    return {"ms": round(med, 5), "min_ms": round(min(ms), 5), "max_ms": round(max(ms), 5),
-            "spread": round((max(ms) - min(ms)) / med, 4), "gib_s": round(n / 2**30 / (med * 1e-3), 1),
-            "launches": len(ms)}
-
-
 def run_shape(shape: str, reps: int, warmup: int, bus: str) -> dict:
     import torch
 
     from oracle_ffi import oracle
     from suruga_amd import _native as N
-    from suruga_amd import devmon, msg
+    from suruga_amd import msg
 
     lib = N.load()
     lens = lengths_of(shape)
@@ -170,28 +165,16 @@ def run_shape(shape: str, reps: int, warmup: int, bus: str) -> dict:
         "a_open": call(lib.sg_open_msg_batch, a_open), "b_open": loop(lib.sg_open_msg_dev, b_open),
         "c_open": call(lib.sg_open_msg_dev, c_open),
     }
-    times = {k: [] for k in legs}
-    # the clock the board holds while the legs are timed (sysfs, read only); the checks run apart from it
-    sampler = devmon.Sampler(bus, period=0.002).start()
-    t_start = time.perf_counter()
-    for rep in range(warmup + reps):
-        for name, fn in legs.items():  # alternating: every leg once per round
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            fn()
-            b.record(stream)
-            b.synchronize()
-            if rep >= warmup:
-                times[name].append(a.elapsed_time(b))
-    torch.cuda.synchronize()
-    clk = sampler.stop(t_start, time.perf_counter())
+    # the clock the board holds while the legs are timed; the checks run apart from it
+    with ab_legs.clock(bus) as clk:
+        times = ab_legs.timed_legs(legs, reps, warmup, stream)
 
     # ---- checks: statuses, round trips, a == b byte for byte, a sample against the oracle
     assert all(int(s.sum().item()) == 0 for s in st.values()), "open status"
     assert all(torch.equal(back[leg], pt) for leg in "abc"), "round trip"
     assert torch.equal(ct["a"], ct["b"]), "the batch's ciphertext and tags differ from the loop's"
     orc = oracle()
-    sample = sorted(int(i) for i in np.random.default_rng(7).choice(count, size=min(SAMPLE, count), replace=False))
+    sample = ab_legs.sample_indices(count, SAMPLE)
     t0 = time.perf_counter()
     for i in sample:
         got = ct["a"][int(out_off[i]):int(out_off[i]) + lens[i] + 16].cpu().numpy().tobytes()
@@ -202,10 +185,9 @@ def run_shape(shape: str, reps: int, warmup: int, bus: str) -> dict:
     out = {"shape": shape, "count": count, "bytes": total, "adlen": ADLEN, "min_len": min(lens), "max_len": max(lens),
            "plan": {k: plan[k] for k in ("tiles", "tiles_per_group", "groups", "segments")},
            "a_equals_b": True, "oracle_sample": sample, "oracle_s": round(time.perf_counter() - t0, 2),
-           "clock": {"sclk_mhz": clk["sclk_mhz"], "board_power_w": clk["board_power_w"],
-                     "power_cap_w": clk.get("power_cap_w")}}
+           "clock": clk}
     for name, ms in times.items():
-        out[name] = summary(ms, total)
+        out[name] = ab_legs.summary(ms, total)
     for d in ("seal", "open"):
         a, b, c = out[f"a_{d}"], out[f"b_{d}"], out[f"c_{d}"]
         out[f"a_vs_b_{d}"] = round(a["ms"] / b["ms"], 4)
@@ -227,17 +209,12 @@ def main() -> None:
 
     import torch
 
-    from suruga_amd import _build, _native
     from suruga_amd import msg
 
-    _build.build_library()
-    assert torch.cuda.is_available(), "msg_batch_bench needs an MI355X"
+    res, bus = ab_legs.prelude("msg_batch_bench", args.reps, args.warmup)
     if args.groups is not None:
         msg.set_groups(args.groups)
-    props = torch.cuda.get_device_properties(0)
-    bus = f"{props.pci_domain_id:04x}:{props.pci_bus_id:02x}:{props.pci_device_id:02x}.0"
-    res = {"tool": "msg_batch_bench", "device": torch.cuda.get_device_name(0), "lib": _native.loaded_info(),
-           "reps": args.reps, "warmup": args.warmup, "msg_groups": msg.set_groups(-1), "shapes": []}
+    res.update(msg_groups=msg.set_groups(-1), shapes=[])
     for shape in args.shapes.split(","):
         res["shapes"].append(run_shape(shape, args.reps, args.warmup, bus))
         torch.cuda.empty_cache()

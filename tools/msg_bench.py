@@ -19,7 +19,8 @@ EVP "ChaCha20-Poly1305" where libcrypto loads (``rfc_check``), and
 ``rfc_vs_draft_*`` is its time over the draft leg's.
 
 The legs alternate launch by launch in one process, so they share the clock
-the board holds.  ``spread`` of a leg is (max - min) / median over its repeats:
+the board holds; every round runs them in another order (a seeded shuffle,
+tools/ab_legs.py), so that no leg always follows the same one.  ``spread`` of a leg is (max - min) / median over its repeats:
 the yardstick for "no slower than the lockstep-0 leg" at 1 GiB.
 
     python tools/msg_bench.py [--sizes 1048576,67108864,1073741824] [--reps 25] [--groups 0] [--rfc8439]
@@ -28,7 +29,6 @@ from __future__ import annotations
 
 import argparse
 import json
-import statistics
 import sys
 import time
 from pathlib import Path
@@ -37,6 +37,8 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
+import ab_legs  # noqa: E402  (tools/, this script's directory)
+
 HBM_BYTES_PER_S = 8e12
 REC = 16384
 ADLEN = 13
@@ -44,10 +46,9 @@ NONCE12 = bytes([0xC1, 0x52, 0xE3, 0x74, 9, 8, 7, 6, 5, 4, 3, 2])
 
 
 def summary(ms: list, n: int, traffic: int) -> dict:
-    med = statistics.median(ms)
-    return {"ms": round(med, 5), "min_ms": round(min(ms), 5), "max_ms": round(max(ms), 5),
-            "spread": round((max(ms) - min(ms)) / med, 4), "gib_s": round(n / 2**30 / (med * 1e-3), 1),
-            "hbm_fraction": round(traffic / (med * 1e-3) / HBM_BYTES_PER_S, 4), "launches": len(ms)}
+    out = ab_legs.summary(ms, n)
+    out["hbm_fraction"] = round(traffic / (out["ms"] * 1e-3) / HBM_BYTES_PER_S, 4)
+    return out
 
 
 def run_size(n: int, reps: int, warmup: int, rfc8439: bool = False) -> dict:
@@ -103,27 +104,11 @@ def run_size(n: int, reps: int, warmup: int, rfc8439: bool = False) -> dict:
                                                             rfc8439=True))
         legs["msg_rfc_open"] = (None, lambda: msg.open_(key_t, NONCE12, ct_r, back_r, st_r, ad=ad_t, workspace=ws,
                                                         rfc8439=True))
-        # every leg once per round, the two message legs side by side
-        order = ("msg_seal", "msg_rfc_seal", "batch_ls0_seal", "batch_ls1_seal",
-                 "msg_open", "msg_rfc_open", "batch_ls0_open", "batch_ls1_open")
-        legs = {k: legs[k] for k in order}
     prev = lib.sg_set_lockstep(-1)
-    times = {k: [] for k in legs}
     try:
-        for rep in range(warmup + reps):
-            for name, (pre, fn) in legs.items():  # alternating: every leg once per round
-                if pre:
-                    pre()
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                fn()
-                b.record()
-                b.synchronize()
-                if rep >= warmup:
-                    times[name].append(a.elapsed_time(b))
+        times = ab_legs.timed_legs(legs, reps, warmup)
     finally:
         lib.sg_set_lockstep(prev)
-    torch.cuda.synchronize()
     assert int(st.item()) == 0 and int(st_b.sum().item()) == 0, "open status"
     assert torch.equal(back, pt) and torch.equal(back_b, pt), "round trip"
     if rfc8439:
@@ -204,32 +189,19 @@ def main() -> None:
     if args.reps < 20:
         ap.error("--reps must be at least 20")
 
-    import torch
-
-    from suruga_amd import _build, _native
     from suruga_amd import msg
 
-    _build.build_library()
-    assert torch.cuda.is_available(), "msg_bench needs an MI355X"
+    res, bus = ab_legs.prelude("msg_bench", args.reps, args.warmup)
     if args.groups is not None:
         msg.set_groups(args.groups)
-    from suruga_amd import devmon
-
-    # the clock the board holds while the largest size is timed (sysfs, read only)
-    props = torch.cuda.get_device_properties(0)
-    bus = f"{props.pci_domain_id:04x}:{props.pci_bus_id:02x}:{props.pci_device_id:02x}.0"
     sizes = [int(s) for s in args.sizes.split(",")]
-    res = {"tool": "msg_bench", "device": torch.cuda.get_device_name(0), "lib": _native.loaded_info(),
-           "reps": args.reps, "warmup": args.warmup, "msg_groups": msg.set_groups(-1), "sizes": []}
+    res.update(msg_groups=msg.set_groups(-1), sizes=[])
     for n in sizes:
-        sampler = devmon.Sampler(bus, period=0.002).start() if n == max(sizes) else None
-        t0 = time.perf_counter()
-        # the oracle check runs apart from the sampled, timed legs
-        r = run_size(n, args.reps, args.warmup, args.rfc8439)
-        if sampler:
-            clk = sampler.stop(t0, time.perf_counter())
-            res["clock"] = {"sclk_mhz": clk["sclk_mhz"], "board_power_w": clk["board_power_w"],
-                            "power_cap_w": clk.get("power_cap_w")}
+        # the clock the board holds while the largest size is timed; the oracle check runs apart from it
+        with ab_legs.clock(bus, n == max(sizes)) as clk:
+            r = run_size(n, args.reps, args.warmup, args.rfc8439)
+        if clk:
+            res["clock"] = clk
         if not args.no_check:
             r.update(check_size(n))
             if args.rfc8439:

@@ -15,9 +15,9 @@ Two batches, both device-resident TLS records:
   routed RFC time over that leg's.  ``routes`` holds every leg's route populations
   (``sg_last_batch_routes``), and the two RFC legs' sealed images must be equal.
 
-The legs alternate launch by launch in one process (draft seal, RFC seal, class-only
-RFC seal, then the opens in the same order, per round), so they share the clock the
-board holds.
+The legs alternate launch by launch in one process (every seal and every open once
+per round), so they share the clock the board holds; every round runs them in another
+order (a seeded shuffle, tools/ab_legs.py), so that no leg always follows the same one.
 Each leg reports the median of ``--reps`` launches after ``--warmup`` from HIP
 events, GiB/s of payload, and ``spread`` = (max - min) / median.
 ``rfc_vs_draft_*`` is RFC time over draft time.  ``timing`` splits each
@@ -34,7 +34,6 @@ from __future__ import annotations
 
 import argparse
 import json
-import statistics
 import struct
 import sys
 import time
@@ -44,16 +43,11 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
+import ab_legs  # noqa: E402  (tools/, this script's directory)
+
 REC = 16384
 SEED = 0x7266635F
 SAMPLE = 24
-
-
-def summary(ms: list, payload: int) -> dict:
-    med = statistics.median(ms)
-    return {"ms": round(med, 5), "min_ms": round(min(ms), 5), "max_ms": round(max(ms), 5),
-            "spread": round((max(ms) - min(ms)) / med, 4), "gib_s": round(payload / 2**30 / (med * 1e-3), 1),
-            "launches": len(ms)}
 
 
 def tls_nonce(iv: bytes, seq: int) -> bytes:
@@ -160,18 +154,7 @@ def run(w: dict, reps: int, warmup: int) -> dict:
             routes.setdefault(f"{name}_{'open' if d else 'seal'}", B.last_routes())
         return f"{name}_{'open' if d else 'seal'}", fn
 
-    order = [leg(name, d) for d in (0, 1) for name in names]
-    times = {k: [] for k, _ in order}
-    for rep in range(warmup + reps):
-        for name, fn in order:  # alternating: every leg once per round
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if rep >= warmup:
-                times[name].append(a.elapsed_time(b))
-    torch.cuda.synchronize()
+    times = ab_legs.timed_legs(dict(leg(name, d) for d in (0, 1) for name in names), reps, warmup)
     for name in names:
         assert int(w["sts"][name].sum().item()) == 0, f"{name}: open status"
     assert torch.equal(w["back"], w["pt"]), "round trip"
@@ -179,7 +162,7 @@ def run(w: dict, reps: int, warmup: int) -> dict:
         assert torch.equal(a, b), "the routed and the class-only RFC images differ"
     out = {"batch": w["desc"], "payload_bytes": w["payload"]}
     for name, ms in times.items():
-        out[name] = summary(ms, w["payload"])
+        out[name] = ab_legs.summary(ms, w["payload"])
     for d in ("seal", "open"):
         out[f"rfc_vs_draft_{d}"] = round(out[f"rfc_{d}"]["ms"] / out[f"draft_{d}"]["ms"], 4)
         if "rfc_classes" in names:
@@ -203,8 +186,7 @@ def check(w: dict) -> dict:
     """A sample of the RFC leg's sealed records against tests/rfc8439_ref.py."""
     import rfc8439_ref as R
 
-    count = w["count"]
-    idx = sorted({0, 1, count // 2, count - 1} | {(i * 2654435761) % count for i in range(SAMPLE)})
+    idx = ab_legs.sample_indices(w["count"], SAMPLE)
     t0 = time.perf_counter()
     for i in idx:
         key, nonce, ad, pt, sealed = w["record"](i)
@@ -227,31 +209,18 @@ def main() -> None:
 
     import torch
 
-    from suruga_amd import _build, _native, devmon
-
-    _build.build_library()
-    assert torch.cuda.is_available(), "rfc_batch_bench needs an MI355X"
-    props = torch.cuda.get_device_properties(0)
-    bus = f"{props.pci_domain_id:04x}:{props.pci_bus_id:02x}:{props.pci_device_id:02x}.0"
-    res = {"tool": "rfc_batch_bench", "device": torch.cuda.get_device_name(0), "lib": _native.loaded_info(),
-           "reps": args.reps, "warmup": args.warmup}
-    def sampled(w):  # run() with the clock and power while its legs run
-        sampler = devmon.Sampler(bus, period=0.002).start()
-        t0 = time.perf_counter()
-        out = run(w, args.reps, args.warmup)
-        clk = sampler.stop(t0, time.perf_counter())
-        return out, {"sclk_mhz": clk["sclk_mhz"], "board_power_w": clk["board_power_w"],
-                     "power_cap_w": clk.get("power_cap_w")}
-
+    res, bus = ab_legs.prelude("rfc_batch_bench", args.reps, args.warmup)
     if args.records:
         w = make_uniform(args.records)
-        res["uniform"], res["clock"] = sampled(w)
+        with ab_legs.clock(bus) as res["clock"]:
+            res["uniform"] = run(w, args.reps, args.warmup)
         res["uniform"]["check"] = check(w)
         del w
         torch.cuda.empty_cache()
     if args.mixed_records:
         w = make_mixed(args.mixed_records)
-        res["mixed"], clk = sampled(w)
+        with ab_legs.clock(bus) as clk:
+            res["mixed"] = run(w, args.reps, args.warmup)
         res["mixed"]["clock"] = clk
         res["mixed"]["check"] = check(w)
     print(json.dumps(res))

@@ -15,9 +15,9 @@ one key, sequential sequence numbers.  Three legs:
 
 The legs alternate launch by launch in one process (the three seals and the three
 opens once per round), so they share the clock the board holds; every round runs them
-in another order (a seeded shuffle), so that no leg always follows the same one (the
-board is power-managed: a launch behind the slow class-only leg finds a higher clock
-than one behind a wave-per-record leg).  Each leg reports the
+in another order (a seeded shuffle, tools/ab_legs.py), so that no leg always follows
+the same one (the board is power-managed: a launch behind the slow class-only leg finds
+a higher clock than one behind a wave-per-record leg).  Each leg reports the
 median of ``--reps`` launches after ``--warmup`` from HIP events, GiB/s of content, and
 ``spread`` = (max - min) / median.  ``routed_vs_classes_*`` and ``routed_vs_rfc7905_*``
 are time ratios; ``route_kept`` says whether the routed leg beats the class-only leg by
@@ -35,8 +35,6 @@ from __future__ import annotations
 
 import argparse
 import json
-import random
-import statistics
 import sys
 import time
 from pathlib import Path
@@ -45,18 +43,13 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
+import ab_legs  # noqa: E402  (tools/, this script's directory)
+
 REC = 16384
 SEED = 0x746C7313
 SAMPLE = 24
 CTYPE = 23
 SEQ0 = 7
-
-
-def summary(ms: list, payload: int) -> dict:
-    med = statistics.median(ms)
-    return {"ms": round(med, 5), "min_ms": round(min(ms), 5), "max_ms": round(max(ms), 5),
-            "spread": round((max(ms) - min(ms)) / med, 4), "gib_s": round(payload / 2**30 / (med * 1e-3), 1),
-            "launches": len(ms)}
 
 
 def make(count: int):
@@ -123,18 +116,7 @@ def run(w: dict, reps: int, warmup: int) -> dict:
                 call(w["legs"][name][d])
         return f"{name}_{'open' if d else 'seal'}", fn
 
-    order = [leg(name, d) for d in (0, 1) for name in names]
-    times = {k: [] for k, _ in order}
-    for rep in range(warmup + reps):
-        for name, fn in random.Random(rep).sample(order, len(order)):  # every leg once per round, in a shuffled order
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if rep >= warmup:
-                times[name].append(a.elapsed_time(b))
-    torch.cuda.synchronize()
+    times = ab_legs.timed_legs(dict(leg(name, d) for d in (0, 1) for name in names), reps, warmup)
     count = w["count"]
     for name in names:
         assert int(w["sts"][name].sum().item()) == 0, f"{name}: open status"
@@ -150,7 +132,7 @@ def run(w: dict, reps: int, warmup: int) -> dict:
     assert routes["tls13_seal"] == routes["tls13_open"] == 1 and routes["tls13_classes_seal"] == routes["tls13_classes_open"] == 0
     out = {"batch": w["desc"], "payload_bytes": w["payload"]}
     for name, ms in times.items():
-        out[name] = summary(ms, w["payload"])
+        out[name] = ab_legs.summary(ms, w["payload"])
     kept = True
     for d in ("seal", "open"):
         out[f"routed_vs_classes_{d}"] = round(out[f"tls13_{d}"]["ms"] / out[f"tls13_classes_{d}"]["ms"], 4)
@@ -179,8 +161,7 @@ def check(w: dict) -> dict:
     import rfc8439_ref as R
     import tls13_ref as T
 
-    count = w["count"]
-    idx = sorted({0, 1, count // 2, count - 1} | {(i * 2654435761) % count for i in range(SAMPLE)})
+    idx = ab_legs.sample_indices(w["count"], SAMPLE)
     t0 = time.perf_counter()
     for i in idx:
         key, iv, seq, content, frag = w["record"](i)
@@ -201,22 +182,10 @@ def main() -> None:
     ap.add_argument("--out", type=Path, default=None, help="also write the JSON here")
     args = ap.parse_args()
 
-    import torch
-
-    from suruga_amd import _build, _native, devmon
-
-    _build.build_library()
-    assert torch.cuda.is_available(), "tls13_batch_bench needs an MI355X"
-    props = torch.cuda.get_device_properties(0)
-    bus = f"{props.pci_domain_id:04x}:{props.pci_bus_id:02x}:{props.pci_device_id:02x}.0"
-    res = {"tool": "tls13_batch_bench", "device": torch.cuda.get_device_name(0), "lib": _native.loaded_info(),
-           "reps": args.reps, "warmup": args.warmup}
+    res, bus = ab_legs.prelude("tls13_batch_bench", args.reps, args.warmup)
     w = make(args.records)
-    sampler = devmon.Sampler(bus, period=0.002).start()
-    t0 = time.perf_counter()
-    res["uniform"] = run(w, args.reps, args.warmup)
-    clk = sampler.stop(t0, time.perf_counter())
-    res["clock"] = {"sclk_mhz": clk["sclk_mhz"], "board_power_w": clk["board_power_w"], "power_cap_w": clk.get("power_cap_w")}
+    with ab_legs.clock(bus) as res["clock"]:
+        res["uniform"] = run(w, args.reps, args.warmup)
     res["uniform"]["check"] = check(w)
     line = json.dumps(res)
     if args.out:
