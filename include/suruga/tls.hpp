@@ -383,6 +383,65 @@ inline size_t complete_records(const uint8_t* wire, size_t n, size_t max_records
     return count ? recs[count - 1].offset + recs[count - 1].frag_len : 0;
 }
 
+// TLS 1.3 (RFC 8446 section 5) over the batched path: thin wrappers of
+// sg_write_records_tls13 / sg_read_records_tls13 on a context that has its
+// write IV.  One direction each; a KeyUpdate is a new object.
+class Tls13Context {
+public:
+    Tls13Context(const uint8_t key[32], const uint8_t iv[12], int device = 0) : ctx_(sg_ctx_new(key, device)) {
+        if (!ctx_) throw std::runtime_error(sg_last_error());
+        const int rc = sg_ctx_set_iv(ctx_, iv);
+        if (rc != SG_OK) {
+            sg_ctx_free(ctx_);
+            check_sg(rc);
+        }
+    }
+    ~Tls13Context() { sg_ctx_free(ctx_); }
+    Tls13Context(const Tls13Context&) = delete;
+    Tls13Context& operator=(const Tls13Context&) = delete;
+    sg_ctx* handle() const { return ctx_; }
+
+    // Appends the records of `data` (2^14-byte fragments, inner type `inner_type`,
+    // no padding) to `wire`; returns the number of records.
+    uint64_t write_data(uint8_t inner_type, Slice data, Bytes& wire) {
+        const size_t base = wire.size();
+        wire.resize(base + sg_wire_bound_tls13(data.size));
+        size_t wl = 0;
+        const int64_t nrec = sg_write_records_tls13(ctx_, count, inner_type, data.data, data.size, wire.data() + base,
+                                                    wire.size() - base, &wl);
+        wire.resize(base + (nrec < 0 ? 0 : wl));
+        check_sg(static_cast<int>(nrec < 0 ? nrec : 0));
+        count += static_cast<uint64_t>(nrec);
+        return static_cast<uint64_t>(nrec);
+    }
+
+    // Opens the complete records at the start of `buf`, appends their contents to
+    // `out` and returns (inner type, content length) of each; *consumed = their wire
+    // bytes.  Throws the first failing record's TlsError after the records before it.
+    std::vector<std::pair<uint8_t, uint32_t>> read(const uint8_t* buf, size_t n, Bytes& out, size_t* consumed,
+                                                   size_t max_records = 1u << 16) {
+        std::vector<uint8_t> types(max_records);
+        std::vector<uint32_t> lens(max_records);
+        const size_t base = out.size();
+        out.resize(base + n);
+        sg_read_result res;
+        check_sg(sg_read_records_tls13(ctx_, count, buf, n, out.data() + base, n, types.data(), lens.data(), max_records,
+                                       &res));
+        out.resize(base + res.out_len);
+        std::vector<std::pair<uint8_t, uint32_t>> recs;
+        for (uint64_t i = 0; i < res.records; ++i) recs.emplace_back(types[i], lens[i]);
+        if (consumed) *consumed = res.consumed;
+        count += res.records;
+        if (res.error != SG_OK) throw detail::record_error(res.error);
+        return recs;
+    }
+
+    uint64_t count = 0;  // write_count or read_count: the next record's sequence number
+
+private:
+    sg_ctx* ctx_;
+};
+
 }  // namespace suruga
 
 #endif  // SURUGA_TLS_HPP

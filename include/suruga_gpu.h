@@ -26,9 +26,14 @@
  * Construction: draft-agl-tls-chacha20poly1305-04 as implemented by suruga
  * (64-bit nonce, 32-bit block counter in state word 12 only, Poly1305 key =
  * keystream block 0, MAC over ad || le64(|ad|) || ct || le64(|ct|) with no
- * padding).  NOT RFC 7539 / RFC 8439: this holds for every record call
- * (sg_seal / sg_open, sg_seal_batch / sg_open_batch, sg_write_records /
- * sg_read_records), which speak only the draft.
+ * padding).  NOT RFC 7539 / RFC 8439: this holds for sg_seal / sg_open,
+ * sg_seal_batch / sg_open_batch and sg_write_records / sg_read_records, which
+ * speak only the draft.  The suites deployed peers negotiate have calls of
+ * their own beside each of the last two: the record batch as
+ * sg_*_batch_rfc8439 (RFC 7905) and sg_*_batch_tls13 (RFC 8446), the record
+ * layer over host memory as sg_write_records_rfc7905 / sg_read_records_rfc7905
+ * and sg_write_records_tls13 / sg_read_records_tls13, on a context that has
+ * its write IV (sg_ctx_set_iv).
  *
  * The message calls (sg_*_msg*, further below) speak the draft by default and,
  * with SG_MSG_RFC8439 or through sg_seal_msg_rfc8439 / sg_open_msg_rfc8439,
@@ -576,6 +581,105 @@ int sg_parse_records(const uint8_t* wire, size_t wire_len, size_t max_records, s
  * the bytes over the host link themselves and all device time counts as
  * kernels) and in host-side framing memcpy. */
 int sg_record_timing(double* h2d_ms, double* kernel_ms, double* d2h_ms, double* host_ms);
+
+/* ---- the record layer in RFC 7905 and TLS 1.3 -----------------------------
+ * The calls above speak draft-agl-04 (suite 0xCC13).  The ones below carry the
+ * same byte streams in the suites deployed peers negotiate, through the same
+ * pipeline: sg_host_register, SG_ZERO_COPY, the direct pipeline,
+ * sg_record_timing and the rule that calls on two contexts run concurrently
+ * apply unchanged.  Each of them needs the context's write IV and returns
+ * SG_E_ARG before any GPU work on a context that has none. */
+
+/* Gives the context its 12-byte write IV (RFC 7905 section 2, RFC 8446 section
+ * 5.3): a host copy and a 4-byte aligned device copy.  May be called again
+ * (the last value holds; not while another call uses the context's records).
+ * sg_ctx_new and every draft call behave as before, with or without an IV. */
+int sg_ctx_set_iv(sg_ctx* ctx, const uint8_t iv[12]);
+
+/* RFC 7905 (TLS 1.2 suites 0xCCA8 / 0xCCA9): the signatures, wire format,
+ * header checks, 13-byte AD, error order and sg_read_result of
+ * sg_write_records / sg_read_records; the sealing is the RFC 8439 record batch
+ * with nonce = iv XOR (00 00 00 00 || be64(seq)).  A read chunk whose records
+ * differ in type or version runs in explicit mode with 12-byte nonces built on
+ * the host from the context's IV. */
+int64_t sg_write_records_rfc7905(sg_ctx* ctx, uint64_t seq0, uint8_t content_type, uint8_t ver_major,
+                                 uint8_t ver_minor, const uint8_t* data, size_t len, uint8_t* wire,
+                                 size_t wire_cap, size_t* wire_len);
+int sg_read_records_rfc7905(sg_ctx* ctx, uint64_t seq0, const uint8_t* wire, size_t wire_len, uint8_t* out,
+                            size_t out_cap, uint8_t* types, uint32_t* frag_lens, size_t max_records,
+                            sg_read_result* res);
+
+/* TLS 1.3 write (RFC 8446 section 5.1 - 5.3): `data` is cut into 2^14-byte
+ * fragments (len == 0 writes no record); record i is
+ *   17 03 03 be16(n_i + 17) || ct(content_i || inner_type) || tag
+ * with seq = seq0 + i and no padding, so exactly len + 22 * nrec ==
+ * sg_wire_bound_tls13(len) wire bytes are written.  inner_type == 0 is
+ * SG_E_ARG (a zero would read as padding).  Returns the records written or
+ * < 0; *wire_len = bytes written. */
+size_t  sg_wire_bound_tls13(size_t len);
+int64_t sg_write_records_tls13(sg_ctx* ctx, uint64_t seq0, uint8_t inner_type, const uint8_t* data, size_t len,
+                               uint8_t* wire, size_t wire_cap, size_t* wire_len);
+
+/* The header checks of sg_read_records_tls13 alone, host only; arguments and
+ * results as sg_parse_records.  In this order: outer type other than 23 ->
+ * SG_E_UNEXPECTED_MESSAGE, length above 2^14 + 256 -> SG_E_RECORD_OVERFLOW,
+ * length below 16 -> SG_E_SHORT.  The version bytes are reported, not checked:
+ * the additional data is built as 17 03 03 be16(length), so a record with
+ * other version bytes fails its tag. */
+int sg_parse_records_tls13(const uint8_t* wire, size_t wire_len, size_t max_records, sg_wire_record* recs,
+                           size_t* count, int32_t* error);
+
+/* TLS 1.3 read: every complete record at the start of `wire` is opened with
+ * seq = seq0 + i and stripped of its inner type and padding; types[r] receives
+ * the inner type, frag_lens[r] the content length, and the contents of the
+ * delivered records lie back to back in `out`.  Processing stops at the first
+ * record that fails its tag (SG_E_BAD_MAC), has no non-zero inner byte
+ * (SG_E_UNEXPECTED_MESSAGE, RFC 8446 section 5.4) or has content longer than
+ * 2^14 (SG_E_RECORD_OVERFLOW); records, consumed, out_len and error as in
+ * sg_read_records.  out_cap must cover the sum of frag_len - 17 over the parsed
+ * records with frag_len >= 17 (else SG_E_ARG).  On return no byte of `out`
+ * beyond out_len holds plaintext and no byte outside [out, out + out_cap) has
+ * been written: the contents are packed on the device (sg_gather_records'
+ * kernel), chunk after chunk on one stream, and nothing behind the first
+ * failing record leaves device memory on the zero-copy path. */
+int sg_read_records_tls13(sg_ctx* ctx, uint64_t seq0, const uint8_t* wire, size_t wire_len, uint8_t* out,
+                          size_t out_cap, uint8_t* types, uint32_t* frag_lens, size_t max_records,
+                          sg_read_result* res);
+
+/* The device step of the TLS 1.3 read on its own (tests, and callers of
+ * sg_open_batch_tls13 that want its output packed): count <= 256 opened
+ * records, record i at src + i * stride (src 16-byte aligned, stride a
+ * multiple of 16 and >= 2^14), their status and content_len as
+ * sg_open_batch_tls13 leaves them.  With ok = the first record whose status is
+ * not SG_OK or whose content_len exceeds 2^14 (count if none; 0 if in->stopped)
+ * and pre[i] = the content bytes before record i:
+ *   dst[base + pre[i], + content_len[i]) <- the record's first content_len[i]
+ *       bytes for i < ok, base = in->offset if use_base else 0; no other byte
+ *       of dst is written; dst may have any alignment
+ *   *out    = {in->offset + pre[ok], in->stopped | (ok < count)}
+ *   result  = {ok, pre[ok]}
+ * Every pointer is device memory (or device-visible host memory); in != out.
+ * Asynchronous on `stream` (NULL: the null stream, and the call waits).
+ * SG_OK, SG_E_ARG or SG_E_HIP. */
+typedef struct sg_gather_cursor {
+    uint64_t offset;
+    uint32_t stopped;
+    uint32_t _pad;
+} sg_gather_cursor;
+int sg_gather_records(const uint8_t* src, uint32_t stride, const uint8_t* status, const uint32_t* content_len,
+                      uint32_t count, uint8_t* dst, int use_base, const sg_gather_cursor* in,
+                      sg_gather_cursor* out, uint32_t* result, void* stream);
+
+/* How a TLS 1.3 read chunk that goes through the library's pinned staging
+ * (unregistered buffers) leaves it: 1 = the gather kernel packs the chunk's
+ * contents into the pinned output and the host makes one memcpy per chunk,
+ * 0 = the host copies record by record from the content lengths, as the draft
+ * path does.  Calls on registered buffers gather on the device either way.
+ * Same bytes and results in both; an A/B and test switch like sg_set_lockstep.
+ * Initial value: environment SG_RECORD13_GATHER ("0"/"1"), else 0 (by
+ * measurement).  Returns the previous setting; a negative
+ * argument only queries. */
+int sg_set_record13_gather(int enable);
 
 /* ---- TLS 1.2 key schedule on the host (cipher/prf.rs, client.rs:130-225) --
  * Produces the per-connection key tables the batch calls take.  CPU only

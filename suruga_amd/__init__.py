@@ -8,6 +8,8 @@ Layout:
   suruga_amd/batch.py        device-resident batch seal/open (record-layer batching)
   suruga_amd/msg.py          one long message (any data / AD length) over the whole chip,
                              in the draft construction or (rfc8439=True) RFC 8439
+  suruga_amd/tls13.py        TLS 1.3 protected stream (Tls13Writer / Tls13StreamReader) over
+                             sg_write_records_tls13 / sg_read_records_tls13
   suruga_amd/_native.py      ctypes binding of libsuruga_gpu.so
 
 The HIP library is the only compute path; importing the cipher classes works

@@ -44,6 +44,9 @@ EXPORTS = [
     "sg_last_batch_routes",
     "sg_wire_bound", "sg_write_records", "sg_read_records", "sg_parse_records", "sg_record_timing",
     "sg_host_register", "sg_host_unregister",
+    "sg_ctx_set_iv", "sg_write_records_rfc7905", "sg_read_records_rfc7905", "sg_wire_bound_tls13",
+    "sg_write_records_tls13", "sg_parse_records_tls13", "sg_read_records_tls13", "sg_gather_records",
+    "sg_set_record13_gather",
     "sg_sha256", "sg_hmac_sha256", "sg_prf_new", "sg_prf_get_bytes", "sg_prf_free",
     "sg_derive_keys", "sg_derive_keys_ivs", "sg_finished_verify_data",
     "sg_msg_workspace_size", "sg_seal_msg_dev", "sg_open_msg_dev", "sg_seal_msg", "sg_open_msg",
@@ -196,6 +199,12 @@ class SgReadResult(C.Structure):
                 ("error", C.c_int32), ("_pad", C.c_uint32)]
 
 
+class SgGatherCursor(C.Structure):
+    """Mirror of ``struct sg_gather_cursor``."""
+
+    _fields_ = [("offset", C.c_uint64), ("stopped", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class SgWireRecord(C.Structure):
     """Mirror of ``struct sg_wire_record``."""
 
@@ -307,6 +316,25 @@ def _declare(lib: C.CDLL) -> None:
                                      C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
     lib.sg_record_timing.restype = C.c_int
     lib.sg_record_timing.argtypes = [d, d, d, d]
+    lib.sg_ctx_set_iv.restype = C.c_int
+    lib.sg_ctx_set_iv.argtypes = [C.c_void_p, C.c_char_p]
+    lib.sg_write_records_rfc7905.restype = C.c_int64
+    lib.sg_write_records_rfc7905.argtypes = lib.sg_write_records.argtypes
+    lib.sg_wire_bound_tls13.restype = C.c_size_t
+    lib.sg_wire_bound_tls13.argtypes = [C.c_size_t]
+    lib.sg_write_records_tls13.restype = C.c_int64
+    lib.sg_write_records_tls13.argtypes = [C.c_void_p, C.c_uint64, C.c_uint8, C.c_void_p, C.c_size_t, C.c_void_p,
+                                           C.c_size_t, C.POINTER(C.c_size_t)]
+    for f in (lib.sg_read_records_rfc7905, lib.sg_read_records_tls13):
+        f.restype = C.c_int
+        f.argtypes = lib.sg_read_records.argtypes
+    lib.sg_parse_records_tls13.restype = C.c_int
+    lib.sg_parse_records_tls13.argtypes = lib.sg_parse_records.argtypes
+    lib.sg_gather_records.restype = C.c_int
+    lib.sg_gather_records.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sg_set_record13_gather.restype = C.c_int
+    lib.sg_set_record13_gather.argtypes = [C.c_int]
     vp = C.c_void_p
     lib.sg_sha256.restype = None
     lib.sg_sha256.argtypes = [vp, C.c_size_t, vp]

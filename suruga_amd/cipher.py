@@ -205,6 +205,33 @@ class ChaCha20Poly1305Rfc8439Decryptor(_GpuCtx, Decryptor):
         return N.SG_MAC_LEN
 
 
+def _set_iv(ctx: _GpuCtx, iv: bytes) -> None:
+    iv = bytes(iv)
+    if len(iv) != N.SG_RFC8439_NONCE_LEN:
+        raise ValueError(f"write IV must be {N.SG_RFC8439_NONCE_LEN} bytes, got {len(iv)}")
+    N.check(ctx._lib.sg_ctx_set_iv(ctx._ptr, iv))
+    ctx.iv = iv
+
+
+class ChaCha20Poly1305Rfc7905Encryptor(ChaCha20Poly1305Rfc8439Encryptor):
+    """RFC 7905 (TLS 1.2 suites 0xCCA8 / 0xCCA9): the RFC 8439 context with its
+    write IV set.  ``encrypt`` takes the caller's 12-byte nonce as its base class;
+    ``TlsWriter.write_data`` routes it to ``sg_write_records_rfc7905``, which
+    derives nonce = iv XOR (0^4 || be64(seq)) itself."""
+
+    def __init__(self, key: bytes, iv: bytes, device: int = 0):
+        super().__init__(key, device)
+        _set_iv(self, iv)
+
+
+class ChaCha20Poly1305Rfc7905Decryptor(ChaCha20Poly1305Rfc8439Decryptor):
+    """The read side: ``RecordStreamReader`` routes it to ``sg_read_records_rfc7905``."""
+
+    def __init__(self, key: bytes, iv: bytes, device: int = 0):
+        super().__init__(key, device)
+        _set_iv(self, iv)
+
+
 class ChaCha20Poly1305Rfc8439(Aead):
     """The ``Aead`` of RFC 8439: key 32, fixed IV 12 (RFC 7905 section 2), tag
     16.  Nonces are the caller's 12 bytes; RFC 7905's derivation (write IV XOR

@@ -465,6 +465,34 @@ void sg_ctx_free(sg_ctx* c) {
     delete c;
 }
 
+int sg_ctx_set_iv(sg_ctx* c, const uint8_t iv[12]) {
+    if (!c || !iv) return fail(SG_E_ARG, "NULL argument%s");
+    std::lock_guard<std::mutex> lk(c->mu);
+    sg::DeviceGuard dg(c->device);
+    if (!dg.ok) return fail(SG_E_HIP, "hipSetDevice failed%s");
+    SG_HIP(hipMemcpy(c->d_key + sg::kIvOff, iv, 12, hipMemcpyHostToDevice));
+    std::memcpy(c->iv, iv, 12);
+    c->has_iv = true;
+    return SG_OK;
+}
+
+int sg_gather_records(const uint8_t* src, uint32_t stride, const uint8_t* status, const uint32_t* content_len,
+                      uint32_t count, uint8_t* dst, int use_base, const sg_gather_cursor* in, sg_gather_cursor* out,
+                      uint32_t* result, void* stream) {
+    if (count > 256u) return fail(SG_E_ARG, "at most 256 records per gather%s");
+    if (!in || !out || in == out || !result) return fail(SG_E_ARG, "NULL cursor or result%s");
+    if (count && (!src || !status || !content_len)) return fail(SG_E_ARG, "NULL argument%s");
+    if (count && (stride < SG_RECORD_MAX_LEN || (stride & 15u) || ((uintptr_t)src & 15u)))
+        return fail(SG_E_ARG, "src must be 16-byte aligned, stride a multiple of 16 and at least 2^14%s");
+    if (((uintptr_t)content_len & 3u) || ((uintptr_t)result & 3u) || (((uintptr_t)in | (uintptr_t)out) & 7u))
+        return fail(SG_E_ARG, "misaligned content_len, result or cursor%s");
+    if (count == 0) return fail(SG_E_ARG, "an empty gather has no result: count must be 1..256%s");
+    SG_HIP(sg::launch_gather(src, stride, status, content_len, count, dst, use_base != 0, in, out, result,
+                             (uint64_t)count * SG_RECORD_MAX_LEN, (hipStream_t)stream));
+    if (!stream) SG_HIP(hipStreamSynchronize(nullptr));
+    return SG_OK;
+}
+
 static int single(sg_ctx* c, bool open, const uint8_t* nonce, size_t nonce_len, const uint8_t* in,
                   size_t in_len, const uint8_t* ad, size_t adlen, uint8_t* out) {
     if (!c) return fail(SG_E_ARG, "context is NULL%s");

@@ -59,6 +59,7 @@ namespace sg {
 constexpr size_t kSingleAdOff = 16;
 constexpr size_t kSingleInOff = 512;
 constexpr size_t kSingleOutOff = 64;
+constexpr size_t kIvOff = 48;  // in d_key's 64 bytes: key @0, the message path's status @32, the IV @48
 }  // namespace sg
 struct sg_ctx {
     int device = 0;
@@ -76,5 +77,9 @@ struct sg_ctx {
     size_t m_cap = 0;
     uint8_t* m_ad = nullptr;
     size_t m_ad_cap = 0;
+    // the write IV (sg_ctx_set_iv) of the RFC 7905 / TLS 1.3 record calls: the
+    // host copy (explicit-mode nonces); the device copy is d_key + kIvOff
+    uint8_t iv[12] = {0};
+    bool has_iv = false;
     std::mutex mu;
 };

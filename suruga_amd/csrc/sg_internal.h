@@ -12,6 +12,8 @@
 
 #include "sg_layout.h"
 
+struct sg_gather_cursor;  // suruga_gpu.h
+
 namespace sg {
 
 constexpr uint32_t kThreads = 256;        // one record per 256-thread workgroup
@@ -275,6 +277,12 @@ hipError_t launch_unframe(const uint8_t* src, uint32_t pitch, uint8_t* dst, uint
 // dst[0, n) <- src[0, n) by a kernel (dst: the caller's registered host memory,
 // written over the host link; src 4-byte aligned)
 hipError_t launch_copy_out(const uint8_t* src, uint8_t* dst, uint64_t n, hipStream_t s);
+// TLS 1.3 read: the contents of the chunk's records before its first failing one, back to
+// back at dst (+ cin->offset with use_base); cout and result as sg_gather_records
+// (suruga_gpu.h) documents them.  capacity: the most the chunk can deliver (sizes the grid).
+hipError_t launch_gather(const uint8_t* src, uint32_t stride, const uint8_t* status, const uint32_t* content_len,
+                         uint32_t count, uint8_t* dst, bool use_base, const sg_gather_cursor* cin,
+                         sg_gather_cursor* cout, uint32_t* result, uint64_t capacity, hipStream_t s);
 hipError_t launch_fill(uint8_t* buf, uint64_t stride, uint32_t len, uint32_t count, uint64_t seed,
                        uint64_t j0, hipStream_t s);
 hipError_t launch_compare(const uint8_t* a, uint64_t sa, const uint8_t* b, uint64_t sb, uint32_t len,

@@ -7,6 +7,7 @@
 //   sg_copy_out_kernel                   (sg_record.cpp, zero-copy path)
 //   sg_scrub_kernel                      zeroes the output of failed opens
 //   sg_strip_kernel                      TLS 1.3 open: inner type and content length
+//   sg_gather_kernel                     TLS 1.3 read: the opened records' contents back to back
 #include "sg_internal.h"
 #include "../../include/suruga_gpu.h"  // SG_HEADER_LEN (record-layer framing kernels)
 
@@ -259,7 +260,137 @@ __global__ __launch_bounds__(256) void sg_strip_kernel(const KParams p, uint8_t*
     content_len[rec] = cl;
 }
 
+// TLS 1.3 read (sg_record.cpp): the contents of a chunk's opened records, back
+// to back.  A record's content length exists only after the open and the strip,
+// and its type byte (and padding) lies between its content and the next
+// record's, so the host cannot fix output offsets before the kernels run as it
+// does for the TLS 1.2 forms.  One launch per chunk of count <= 256 records,
+// after the strip, on the chunk's stream:
+//   ok      the first record whose status is not 0 or whose content is longer
+//           than 2^14 (count if none; 0 if the incoming cursor has stopped)
+//   pre[i]  the content bytes of the records before i (i <= ok)
+//   dst[base + pre[i], + content_len[i]) <- record i's first content_len[i]
+//           bytes, i < ok; base = the incoming cursor's offset (use_base) or 0
+//   cout    {cin.offset + pre[ok], cin.stopped | (ok < count)}
+//   result  {ok, pre[ok]}
+// and no other byte of dst is written.  The chunks of a call run in order on
+// one stream and hand the cursor on, so nothing behind a call's first failing
+// record ever leaves device memory.
+// Every workgroup scans the lengths into LDS; the grid then strides over the
+// 4-byte aligned words of dst.  A word finds its record by binary search in the
+// prefix; inside a record its source is two aligned words, funnel-shifted
+// (ld_u32_unaligned's form, the second word only where the shift needs it: no
+// load leaves the record's content rounded up to a word, which lies inside its
+// slot as stride >= 2^14 is a multiple of 16); a word across a record seam,
+// and the bytes before dst's first and after its last aligned word, are put
+// together byte by byte.
+constexpr uint32_t kGatherMax = 256;
+static_assert(kGatherMax == 256, "one thread per record of a chunk");
+
+// the byte at `pos` of the packed contents (pos < pre[kGatherMax])
+__device__ __forceinline__ uint32_t gather_rec(const uint32_t* pre, uint32_t pos) {
+    uint32_t r = 0u;  // the last record with pre[r] <= pos: it is not empty
+    for (uint32_t step = kGatherMax / 2u; step; step >>= 1)
+        if (pre[r + step] <= pos) r += step;
+    return r;
+}
+__device__ __forceinline__ uint8_t gather_byte(const uint8_t* src, uint32_t stride, const uint32_t* pre,
+                                               uint32_t pos) {
+    const uint32_t r = gather_rec(pre, pos);
+    return src[(uint64_t)r * stride + (pos - pre[r])];
+}
+
+__global__ __launch_bounds__(256) void sg_gather_kernel(const uint8_t* __restrict__ src, uint32_t stride,
+                                                        const uint8_t* __restrict__ status,
+                                                        const uint32_t* __restrict__ content_len, uint32_t count,
+                                                        uint8_t* __restrict__ dst, uint32_t use_base,
+                                                        const sg_gather_cursor* __restrict__ cin,
+                                                        sg_gather_cursor* __restrict__ cout,
+                                                        uint32_t* __restrict__ result) {
+    __shared__ uint32_t pre[kGatherMax + 1u];
+    __shared__ uint32_t first_bad;
+    const uint32_t t = threadIdx.x;
+    uint32_t cl = 0u;
+    bool bad = false;
+    if (t < count) {
+        cl = content_len[t];
+        bad = status[t] != 0u || cl > SG_RECORD_MAX_LEN;
+    }
+    if (t == 0u) first_bad = count;
+    __syncthreads();
+    if (bad) atomicMin(&first_bad, t);
+    __syncthreads();
+    const uint64_t base0 = cin->offset;
+    const uint32_t stopped = cin->stopped;
+    const uint32_t ok = stopped ? 0u : first_bad;
+    // inclusive scan of the delivered records' lengths: pre[i + 1] = pre[i] + len_i
+    if (t == 0u) pre[0] = 0u;
+    pre[t + 1u] = t < ok ? cl : 0u;
+    __syncthreads();
+    for (uint32_t d = 1u; d < kGatherMax; d <<= 1) {
+        const uint32_t x = t >= d ? pre[t + 1u - d] : 0u;
+        __syncthreads();
+        pre[t + 1u] += x;
+        __syncthreads();
+    }
+    const uint32_t total = pre[kGatherMax];  // == pre[ok]: nothing is counted from record ok on
+
+    uint8_t* d = dst + (use_base ? base0 : 0ull);
+    const uint32_t a0 = (uint32_t)((4u - ((uintptr_t)d & 3u)) & 3u);
+    const uint32_t a = a0 < total ? a0 : total;  // bytes before d's first aligned word
+    const uint32_t nw = (total - a) >> 2;        // whole aligned words of d
+    const uint32_t tid = blockIdx.x * 256u + t, nth = gridDim.x * 256u;
+    if (tid < a) d[tid] = gather_byte(src, stride, pre, tid);
+    uint32_t* d32 = reinterpret_cast<uint32_t*>(d + a);
+    for (uint32_t w = tid; w < nw; w += nth) {
+        const uint32_t b = a + 4u * w;  // packed offset of the word's first byte
+        const uint32_t r = gather_rec(pre, b);
+        const uint32_t o = b - pre[r];
+        uint32_t v;
+        if (o + 4u <= pre[r + 1u] - pre[r]) {  // inside one record
+            const uint32_t* q = reinterpret_cast<const uint32_t*>(src + (uint64_t)r * stride + (o & ~3u));
+            const uint32_t lo = q[0];
+            const uint32_t hi = (o & 3u) ? q[1] : 0u;
+            v = __builtin_amdgcn_alignbyte(hi, lo, o & 3u);
+        } else {  // a record seam (empty records between its two sides are skipped)
+            v = 0u;
+            uint32_t rr = r;
+            for (uint32_t k = 0; k < 4u; ++k) {
+                const uint32_t pos = b + k;  // < total = pre[kGatherMax]: the walk ends
+                while (pre[rr + 1u] <= pos) ++rr;
+                v |= (uint32_t)src[(uint64_t)rr * stride + (pos - pre[rr])] << (8u * k);
+            }
+        }
+        d32[w] = v;
+    }
+    const uint32_t t0 = a + 4u * nw;  // the byte tail
+    if (tid < 4u && t0 + tid < total) d[t0 + tid] = gather_byte(src, stride, pre, t0 + tid);
+    if (tid == 0u) {
+        cout->offset = base0 + total;
+        cout->stopped = (stopped || ok < count) ? 1u : 0u;
+        cout->_pad = 0u;
+        result[0] = ok;
+        result[1] = total;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_gather(const uint8_t* src, uint32_t stride, const uint8_t* status, const uint32_t* content_len,
+                         uint32_t count, uint8_t* dst, bool use_base, const sg_gather_cursor* cin,
+                         sg_gather_cursor* cout, uint32_t* result, uint64_t capacity, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    if (count > kGatherMax || stride < SG_RECORD_MAX_LEN || (stride & 15u) || ((uintptr_t)src & 15u) ||
+        ((uintptr_t)content_len & 3u) || ((uintptr_t)result & 3u) || (((uintptr_t)cin | (uintptr_t)cout) & 7u) ||
+        !src || !status || !content_len || !cin || !cout || cin == cout || !result)
+        return hipErrorInvalidValue;
+    // capacity: the most the chunk can deliver; every thread a few words of it
+    uint64_t grid = (capacity / 4u + 255u) / 256u;
+    grid = grid < 256u ? (grid ? grid : 1u) : 256u;
+    hipLaunchKernelGGL(sg_gather_kernel, dim3((uint32_t)grid), dim3(256), 0, s, src, stride, status, content_len, count,
+                       dst, use_base ? 1u : 0u, cin, cout, result);
+    return hipGetLastError();
+}
 
 hipError_t launch_scrub(const KParams& p, hipStream_t s) {
     if (p.count == 0) return hipSuccess;

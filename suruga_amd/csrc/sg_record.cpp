@@ -84,6 +84,14 @@ const Switches& switches() {
     static const Switches s{};
     return s;
 }
+// SG_RECORD13_GATHER / sg_set_record13_gather (sg_env.h)
+EnvSwitch g_gather13{"SG_RECORD13_GATHER", -1, kRecord13GatherDefault};
+
+// TLS 1.3 read: a slot's pinned block beside its statuses, written by the strip
+// and gather kernels over the host link: content_len[kChunk], the gather's
+// result {ok, bytes}, inner_type[kChunk]
+constexpr size_t kT13ResOff = (size_t)kChunk * 4u, kT13TypeOff = kT13ResOff + 16u;
+constexpr size_t kT13Bytes = kT13TypeOff + kChunk;
 }  // namespace
 
 struct RecordStaging {
@@ -97,6 +105,10 @@ struct RecordStaging {
         // direct pipeline's kernels read and write the record staging there
         uint8_t *dh_in = nullptr, *dh_out = nullptr, *dh_meta = nullptr, *dh_status = nullptr;
         uint32_t* dh_len = nullptr;
+        uint8_t *h_t13 = nullptr, *dh_t13 = nullptr;  // TLS 1.3 read (host_staging13, on first use)
+        uint32_t* clen(bool dev) const { return (uint32_t*)(dev ? dh_t13 : h_t13); }
+        uint32_t* result(bool dev) const { return (uint32_t*)((dev ? dh_t13 : h_t13) + kT13ResOff); }
+        uint8_t* itype(bool dev) const { return (dev ? dh_t13 : h_t13) + kT13TypeOff; }
         void* d_ws = nullptr;
         hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start, after H2D, after kernels, after D2H
         uint32_t nrec = 0;       // records in flight on this slot
@@ -108,6 +120,9 @@ struct RecordStaging {
     } slot[kMaxSlots];
     hipStream_t krn = nullptr;  // the copy-engine pipeline's kernel stream
     hipStream_t kst = nullptr;  // the direct pipeline's stream
+    // TLS 1.3 read: the call's cursor table, one entry per chunk and one more (sg_gather_kernel)
+    sg_gather_cursor* d_cur = nullptr;
+    size_t cur_cap = 0;
 };
 using Slot = RecordStaging::Slot;
 
@@ -175,6 +190,7 @@ void record_staging_free(RecordStaging* rs) {
         (void)hipHostFree(s.h_meta);
         (void)hipHostFree(s.h_status);
         (void)hipHostFree(s.h_len);
+        (void)hipHostFree(s.h_t13);
         (void)hipFree(s.d_in);
         (void)hipFree(s.d_out);
         (void)hipFree(s.d_wire);
@@ -182,6 +198,7 @@ void record_staging_free(RecordStaging* rs) {
         for (auto& e : s.ev)
             if (e) (void)hipEventDestroy(e);
     }
+    (void)hipFree(rs->d_cur);
     delete rs;
 }
 
@@ -196,7 +213,7 @@ int staging(sg_ctx* c, RecordStaging** out) {
         // the order that the rates depend on)
         for (int i = 0; i < switches().slots; ++i) {  // (h_in / h_out: host_staging, on first use)
             auto& s = rs->slot[i];
-            SG_HIP(hipHostMalloc((void**)&s.h_meta, (size_t)kChunk * kMetaBytes, hipHostMallocMapped));
+            SG_HIP(hipHostMalloc((void**)&s.h_meta, (size_t)kChunk * kMetaBytesMax, hipHostMallocMapped));
             SG_HIP(hipHostMalloc((void**)&s.h_status, kChunk, hipHostMallocMapped));
             SG_HIP(hipHostMalloc((void**)&s.h_len, kChunk * 4u, hipHostMallocMapped));
             SG_HIP(hipHostGetDevicePointer((void**)&s.dh_meta, s.h_meta, 0));
@@ -225,6 +242,27 @@ int host_staging(Slot& s) {
         SG_HIP(hipHostMalloc((void**)&s.h_out, bytes, hipHostMallocMapped));
         SG_HIP(hipHostGetDevicePointer((void**)&s.dh_out, s.h_out, 0));
     }
+    return SG_OK;
+}
+
+// The TLS 1.3 read's pinned block of a slot and the call's cursor table (no
+// kernel of the context is in flight here: a call drains its slots before it
+// returns), its first entry {0, not stopped} on stream ks.
+int host_staging13(Slot& s) {
+    if (s.h_t13) return SG_OK;
+    SG_HIP(hipHostMalloc((void**)&s.h_t13, kT13Bytes, hipHostMallocMapped));
+    SG_HIP(hipHostGetDevicePointer((void**)&s.dh_t13, s.h_t13, 0));
+    return SG_OK;
+}
+int cursor_table(RecordStaging* rs, uint64_t chunks, hipStream_t ks) {
+    if (rs->cur_cap < chunks + 1) {
+        (void)hipFree(rs->d_cur);
+        rs->d_cur = nullptr;
+        rs->cur_cap = 0;
+        SG_HIP(hipMalloc((void**)&rs->d_cur, (size_t)(chunks + 1) * sizeof(sg_gather_cursor)));
+        rs->cur_cap = chunks + 1;
+    }
+    SG_HIP(hipMemsetAsync(rs->d_cur, 0, sizeof(sg_gather_cursor), ks));
     return SG_OK;
 }
 
@@ -521,16 +559,67 @@ int sg_record_timing(double* h2d_ms, double* kernel_ms, double* d2h_ms, double* 
     return SG_OK;
 }
 
-int64_t sg_write_records(sg_ctx* c, uint64_t seq0, uint8_t content_type, uint8_t ver_major, uint8_t ver_minor,
-                         const uint8_t* data, size_t len, uint8_t* wire, size_t wire_cap, size_t* wire_len) {
-    using namespace sg;
+int sg_set_record13_gather(int enable) { return sg::g_gather13.set(enable); }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// The writer and the reader, one body each for the three record forms
+// (RecordForm, sg_layout.h; the per-form wire values: sg_wire.h).  kDraft is
+// sg_write_records / sg_read_records, kRfc8439 the *_rfc7905 calls -- the same
+// wire with the RFC 8439 batch under it -- and kTls13 the *_tls13 calls.
+// ---------------------------------------------------------------------------
+namespace sg {
+namespace {
+
+// the context's write IV on the device (sg_ctx_set_iv)
+const uint8_t* dev_iv(const sg_ctx* c) { return c->d_key + kIvOff; }
+
+// the batch entry point of a chunk in its form
+int seal_chunk(RecordForm f, const sg_ctx* c, const sg_batch* b) {
+    if (f == RecordForm::kDraft) return sg_seal_batch(b);
+    if (f == RecordForm::kRfc8439) {
+        const sg_batch_rfc8439 x = {dev_iv(c), 0u, 0u};
+        return sg_seal_batch_rfc8439(b, &x);
+    }
+    const sg_batch_tls13 x = {dev_iv(c), nullptr, nullptr, 0u, 0u};
+    return sg_seal_batch_tls13(b, &x);
+}
+int open_chunk(RecordForm f, const sg_ctx* c, const sg_batch* b, const Slot& s) {
+    if (f == RecordForm::kDraft) return sg_open_batch(b);
+    if (f == RecordForm::kRfc8439) {
+        const sg_batch_rfc8439 x = {dev_iv(c), 0u, 0u};
+        return sg_open_batch_rfc8439(b, &x);
+    }
+    const sg_batch_tls13 x = {dev_iv(c), s.itype(true), s.clen(true), 0u, 0u};
+    return sg_open_batch_tls13(b, &x);
+}
+
+int needs_iv(RecordForm f, const sg_ctx* c) {
+    if (f != RecordForm::kDraft && !c->has_iv)
+        return fail(SG_E_ARG, "the context has no write IV: call sg_ctx_set_iv first%s");
+    return SG_OK;
+}
+
+// content_type: the record type of the TLS 1.2 forms; the inner type of TLS 1.3,
+// whose header is 17 03 03 whatever the caller's version
+int64_t write_records(RecordForm form, sg_ctx* c, uint64_t seq0, uint8_t content_type, uint8_t ver_major,
+                      uint8_t ver_minor, const uint8_t* data, size_t len, uint8_t* wire, size_t wire_cap,
+                      size_t* wire_len) {
     if (!c || (!data && len) || !wire_len) return fail(SG_E_ARG, "NULL argument%s");
+    if (needs_iv(form, c) != SG_OK) return SG_E_ARG;
+    const bool t13 = form == RecordForm::kTls13;
+    if (t13 && content_type == 0)
+        return fail(SG_E_ARG, "the inner content type must be non-zero (a zero byte reads as padding)%s");
     *wire_len = 0;
     t_h2d = t_kernel = t_d2h = t_host = 0;
-    const WritePlan plan(len);  // tls.rs:137-147: 2^14-byte fragments
+    const WritePlan plan(len, form);  // tls.rs:137-147: 2^14-byte fragments
     const uint64_t nrec = plan.nrec;
     if (nrec == 0) return 0;
-    if (!wire || wire_cap < sg_wire_bound(len)) return fail(SG_E_ARG, "wire buffer too small%s");
+    if (!wire || wire_cap < plan.wire_need()) return fail(SG_E_ARG, "wire buffer too small%s");
+    // the header's bytes
+    const uint8_t h_type = t13 ? 23 : content_type, h_major = t13 ? 3 : ver_major, h_minor = t13 ? 3 : ver_minor;
+    const uint32_t extra = frag_extra(form);  // fragment bytes beyond the plaintext
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard dg(c->device);
     if (!dg.ok) return fail(SG_E_HIP, "hipSetDevice failed%s");
@@ -597,12 +686,12 @@ int64_t sg_write_records(sg_ctx* c, uint64_t seq0, uint8_t content_type, uint8_t
         b.out_stride = kSlot;
         b.max_len = SG_RECORD_MAX_LEN;
         int r;
-        if ((r = sg_seal_batch(&b)) != SG_OK) return r;
+        if ((r = seal_chunk(form, c, &b)) != SG_OK) return r;
         if (s.zc) {
-            const uint32_t hdr = content_type | ((uint32_t)ver_major << 8) | ((uint32_t)ver_minor << 16);
+            const uint32_t hdr = h_type | ((uint32_t)h_major << 8) | ((uint32_t)h_minor << 16);
             uint8_t* img = kd2h ? reg_dev(wire + plan.wire_off(s.first)) : s.d_wire;
-            SG_HIP(launch_frame(s.d_out, kSlot, img, (uint32_t)kWireRec, k, SG_RECORD_MAX_LEN + SG_MAC_LEN,
-                                last + SG_MAC_LEN, hdr, P.krn));
+            SG_HIP(launch_frame(s.d_out, kSlot, img, (uint32_t)wire_rec(form), k, SG_RECORD_MAX_LEN + extra,
+                                last + extra, hdr, P.krn));
         }
         SG_HIP(hipEventRecord(s.ev[2], P.krn));
         return SG_OK;
@@ -615,7 +704,7 @@ int64_t sg_write_records(sg_ctx* c, uint64_t seq0, uint8_t content_type, uint8_t
         }
         if (s.zc)
             return d2h(s, wire + plan.wire_off(s.first), s.d_wire,
-                       (size_t)(k - 1) * kWireRec + SG_HEADER_LEN + plan.rec_len(s.first + k - 1) + SG_MAC_LEN, P.d2h);
+                       (size_t)(k - 1) * wire_rec(form) + SG_HEADER_LEN + plan.frag_len(s.first + k - 1), P.d2h);
         return d2h(s, s.h_out, s.d_out, (size_t)k * kSlot, P.d2h);
     };
     // frame the chunk's records into the wire (tls.rs:126-130): the headers and
@@ -625,14 +714,14 @@ int64_t sg_write_records(sg_ctx* c, uint64_t seq0, uint8_t content_type, uint8_t
         if (!s.zc) {
             copy_run(s.nrec, [&](uint32_t i) {
                 const uint64_t r = s.first + i;
-                const uint32_t flen = plan.rec_len(r) + SG_MAC_LEN;
+                const uint32_t flen = plan.frag_len(r);
                 uint8_t* h = wire + plan.wire_off(r);
-                put_header(h, content_type, ver_major, ver_minor, flen);
+                put_header(h, h_type, h_major, h_minor, flen);
                 std::memcpy(h + SG_HEADER_LEN, s.h_out + (size_t)i * kSlot, flen);
             });
         }
         const uint64_t last = s.first + s.nrec - 1;
-        wpos = plan.wire_off(last) + SG_HEADER_LEN + plan.rec_len(last) + SG_MAC_LEN;
+        wpos = plan.wire_off(last) + SG_HEADER_LEN + plan.frag_len(last);
         t_host += now_ms() - t0;
         return SG_OK;
     };
@@ -644,10 +733,19 @@ int64_t sg_write_records(sg_ctx* c, uint64_t seq0, uint8_t content_type, uint8_t
     return (int64_t)nrec;
 }
 
-int sg_read_records(sg_ctx* c, uint64_t seq0, const uint8_t* wire, size_t wire_len, uint8_t* out, size_t out_cap,
-                    uint8_t* types, uint32_t* frag_lens, size_t max_records, sg_read_result* res) {
-    using namespace sg;
+// the read error of a TLS 1.3 record that the gather stopped at
+int32_t tls13_error(uint8_t status, uint32_t content_len) {
+    if (status == 0) return content_len > SG_RECORD_MAX_LEN ? SG_E_RECORD_OVERFLOW : SG_OK;
+    if (status == 2) return SG_E_SHORT;
+    if (status == SG_STATUS_NO_TYPE) return SG_E_UNEXPECTED_MESSAGE;  // RFC 8446 section 5.4
+    return SG_E_BAD_MAC;
+}
+
+int read_records(RecordForm form, sg_ctx* c, uint64_t seq0, const uint8_t* wire, size_t wire_len, uint8_t* out,
+                 size_t out_cap, uint8_t* types, uint32_t* frag_lens, size_t max_records, sg_read_result* res) {
     if (!c || (!wire && wire_len) || !res) return fail(SG_E_ARG, "NULL argument%s");
+    if (needs_iv(form, c) != SG_OK) return SG_E_ARG;
+    const bool t13 = form == RecordForm::kTls13;
     std::memset(res, 0, sizeof *res);
     t_h2d = t_kernel = t_d2h = t_host = 0;
 
@@ -655,9 +753,9 @@ int sg_read_records(sg_ctx* c, uint64_t seq0, const uint8_t* wire, size_t wire_l
     // (sg_wire.cpp: host-only, run under ASan/UBSan by tests/test_sanitizers.py)
     using Rec = WireRec;
     std::vector<Rec> recs;
-    const int32_t header_error = parse_wire(wire, wire_len, max_records, recs);
+    const int32_t header_error = parse_wire(form, wire, wire_len, max_records, recs);
     size_t need = 0;
-    for (const Rec& r : recs) need += r.flen - SG_MAC_LEN;
+    for (const Rec& r : recs) need += frag_capacity(form, r.flen);
     if (need > out_cap || (need && !out)) return fail(SG_E_ARG, "out buffer too small%s");
     if (recs.empty()) {
         res->error = header_error;
@@ -681,16 +779,23 @@ int sg_read_records(sg_ctx* c, uint64_t seq0, const uint8_t* wire, size_t wire_l
     int32_t error = SG_OK;
     // registered caller buffers: the fragments come in by DMA from the wire and
     // the plaintext leaves by DMA into `out` at its final offset (prefix sum of
-    // the plaintext lengths, as if every record opens)
+    // the plaintext lengths, as if every record opens; TLS 1.3: at the offset
+    // the gather kernels' cursor has reached)
     const bool zc = sw.zero_copy && registered(wire, wire_len) && registered(out, need);
     const bool direct = sw.direct && !zc;
     const bool kd2h = zc && sw.kd2h;  // zero-copy chunks: a copy-out kernel writes `out`
+    // TLS 1.3: the contents are packed by the gather kernel, in a zero-copy call
+    // always (every chunk, so that the cursor runs through the staged ones too),
+    // else by the switch; off: the host copies record by record
+    const bool gather = t13 && (zc || g_gather13.on());
+    uint64_t gpos = 0;  // TLS 1.3, copy-engine pipeline: content bytes of the chunks copied out so far
     // Zero-copy: plaintext DMA'd into `out` beyond the delivered records is
     // cleared on every exit (the reference releases none of it, tls.rs:268):
     // collect() clears it chunk by chunk, and an early return (a launch or copy
     // error) clears everything from the first undelivered record to the end of
     // the chunks issued.  Declared before the SlotReset, so that it runs after
-    // the pipeline's streams have drained.
+    // the pipeline's streams have drained.  (TLS 1.3: only delivered bytes ever
+    // reach `out`, so there is nothing to clear.)
     struct ScrubOut {
         uint8_t* out;
         const uint64_t *opos, *issued;
@@ -698,12 +803,51 @@ int sg_read_records(sg_ctx* c, uint64_t seq0, const uint8_t* wire, size_t wire_l
         ~ScrubOut() {
             if (armed && *issued > *opos) std::memset(out + *opos, 0, *issued - *opos);
         }
-    } scrub{out, &opos, &issued, zc};
+    } scrub{out, &opos, &issued, zc && !t13};
     SlotReset slot_reset(rs);
     PipeStreams& P = slot_reset.ps;
     if ((rc = pipe_streams(c, rs, direct, &P)) != SG_OK) return rc;
+    if (gather && (rc = cursor_table(rs, (nrec + kChunk - 1) / kChunk, P.krn)) != SG_OK) return rc;
 
+    // TLS 1.3: the chunk's records before its first failing one, their contents
+    // packed by the gather kernel (one memcpy) or copied record by record
+    auto collect13 = [&](Slot& s) -> int {
+        if (error != SG_OK) return SG_OK;  // stopped earlier: the chunk delivered nothing anywhere
+        const double t0 = now_ms();
+        const uint32_t* cl = s.clen(false);
+        const uint8_t* ty = s.itype(false);
+        uint32_t hpre[kChunk + 1];
+        uint32_t ok = 0;
+        hpre[0] = 0;
+        for (; ok < s.nrec; ++ok) {
+            if (tls13_error(s.h_status[ok], cl[ok]) != SG_OK) break;
+            hpre[ok + 1] = hpre[ok] + cl[ok];
+        }
+        const uint32_t bytes = hpre[ok];
+        if (gather && (s.result(false)[0] != ok || s.result(false)[1] != bytes))
+            return fail(SG_E_HIP, "the gather kernel's result disagrees with the chunk's statuses%s");
+        if (ok < s.nrec) error = tls13_error(s.h_status[ok], cl[ok]);
+        if (!s.zc) {
+            if (gather) {
+                if (bytes) std::memcpy(out + opos, s.h_out, bytes);
+            } else {
+                copy_run(ok, [&](uint32_t i) {
+                    std::memcpy(out + opos + hpre[i], s.h_out + (size_t)i * kSlot, cl[i]);
+                });
+            }
+        }
+        for (uint32_t i = 0; i < ok; ++i) {
+            if (types) types[s.first + i] = ty[i];
+            if (frag_lens) frag_lens[s.first + i] = cl[i];
+        }
+        good += ok;
+        opos += bytes;
+        if (ok) consumed = recs[s.first + ok - 1].off + recs[s.first + ok - 1].flen;
+        t_host += now_ms() - t0;
+        return SG_OK;
+    };
     auto collect = [&](Slot& s) -> int {
+        if (t13) return collect13(s);
         const double t0 = now_ms();
         const uint32_t* pre = s.shape.pre;
         if (error != SG_OK) {  // stopped earlier: nothing of this chunk is delivered
@@ -744,12 +888,14 @@ int sg_read_records(sg_ctx* c, uint64_t seq0, const uint8_t* wire, size_t wire_l
         const uint32_t k = chunk_count(nrec, next);
         const double t0 = now_ms();
         const Rec* R = &recs[next];
-        chunk_shape(R, k, &s.shape);
+        chunk_shape(R, k, &s.shape, form);
         // zero-copy for chunks of equal, back-to-back records (a stream of
         // full records); any other chunk goes through the staging
         s.zc = zc && s.shape.same && s.shape.dense;
+        int r;
+        if (t13 && (r = host_staging13(s)) != SG_OK) return r;
+        // (a zero-copy call's staged chunks leave through the device chunk buffer and h_out)
         if (!s.zc) {
-            int r;
             if ((r = host_staging(s)) != SG_OK) return r;
             copy_run(k, [&](uint32_t i) {
                 std::memcpy(s.h_in + (size_t)i * kSlot, wire + R[i].off, R[i].flen);
@@ -757,15 +903,16 @@ int sg_read_records(sg_ctx* c, uint64_t seq0, const uint8_t* wire, size_t wire_l
             });
         }
         // TLS mode (nonce and AD built on the device, tls.rs:250-265) when the
-        // chunk's records share type and version; else explicit nonce / AD
+        // chunk's records share type and version; else explicit nonce / AD.
+        // TLS 1.3: the header is a constant, whatever version bytes the peer sent.
+        if (t13) s.shape.tls = true;
         if (!s.shape.tls)
-            for (uint32_t i = 0; i < k; ++i) put_explicit_meta(s.h_meta, i, seq0 + next + i, R[i]);
+            for (uint32_t i = 0; i < k; ++i) put_explicit_meta(s.h_meta, i, seq0 + next + i, R[i], form, c->iv);
         t_host += now_ms() - t0;
         if (!direct) {  // (direct: the kernels read the staging themselves)
             // zero-copy: the chunk's wire image in one contiguous copy, taken apart in HBM
-            const int r = s.zc ? h2d(s, s.d_wire, wire + R[0].off - SG_HEADER_LEN,
-                                     (size_t)k * (SG_HEADER_LEN + R[0].flen), P.h2d)
-                               : h2d(s, s.d_in, s.h_in, (size_t)k * kSlot, P.h2d);
+            r = s.zc ? h2d(s, s.d_wire, wire + R[0].off - SG_HEADER_LEN, (size_t)k * (SG_HEADER_LEN + R[0].flen), P.h2d)
+                     : h2d(s, s.d_in, s.h_in, (size_t)k * kSlot, P.h2d);
             if (r != SG_OK) return r;
         }
         s.out0 = issued;
@@ -790,30 +937,54 @@ int sg_read_records(sg_ctx* c, uint64_t seq0, const uint8_t* wire, size_t wire_l
             b.ver_minor = R0.minor;
         } else {
             b.nonces = s.dh_meta;
-            b.ads = s.dh_meta + kNonceLen * kChunk;
+            b.ads = s.dh_meta + explicit_nonce_len(form) * kChunk;
             b.ad_len = kAdLen;
             b.ad_stride = kAdLen;
         }
         b.in_stride = kSlot;
-        // zero-copy: plaintext back to back, as it lands in `out`
-        b.out_stride = s.zc ? (size_t)(flen - SG_MAC_LEN) : kSlot;
-        b.max_len = SG_ENC_RECORD_MAX_LEN;
+        // zero-copy: plaintext back to back, as it lands in `out` (TLS 1.3: in
+        // the records' slots; the gather kernel packs the contents)
+        b.out_stride = s.zc && !t13 ? (size_t)(flen - SG_MAC_LEN) : kSlot;
+        b.max_len = max_fragment(form);
         b.status = s.dh_status;
         // staged: the reader delivers nothing from a failed record (it stops
         // there), so no device scrub of failed records' output; zero-copy: the
         // output goes to the caller's memory by DMA, so failed records are
-        // scrubbed on the device first
-        if (!s.zc) b.flags |= SG_BATCH_KEEP_FAILED;
+        // scrubbed on the device first (TLS 1.3: the gather stops in front of them)
+        if (!s.zc || t13) b.flags |= SG_BATCH_KEEP_FAILED;
+        // TLS 1.3 with the gather: the inner plaintexts stay in HBM
+        if (gather) b.out = s.d_out;
         int r;
-        if ((r = sg_open_batch(&b)) != SG_OK) return r;
-        if (s.zc && kd2h) SG_HIP(launch_copy_out(s.d_out, reg_dev(out + s.out0), s.shape.pre[k], P.krn));
+        if ((r = open_chunk(form, c, &b, s)) != SG_OK) return r;
+        if (gather) {
+            // into the caller's registered `out` at the cursor's offset, into the slot's
+            // pinned output, or into the device chunk buffer (the wire image is consumed)
+            const bool to_out = s.zc && kd2h;
+            uint8_t* dst = to_out ? reg_dev(out) : (direct ? s.dh_out : s.d_wire);
+            const sg_gather_cursor* cur = rs->d_cur + s.first / kChunk;
+            SG_HIP(launch_gather(s.d_out, kSlot, s.dh_status, s.clen(true), k, dst, to_out, cur, rs->d_cur + s.first / kChunk + 1,
+                                 s.result(true), s.shape.pre[k], P.krn));
+        } else if (s.zc && kd2h) {
+            SG_HIP(launch_copy_out(s.d_out, reg_dev(out + s.out0), s.shape.pre[k], P.krn));
+        }
         SG_HIP(hipEventRecord(s.ev[2], P.krn));
         return SG_OK;
     };
     auto copy_out = [&](Slot& s) -> int {
-        if (s.zc && kd2h) {  // the copy-out kernel has written `out` already
+        if (s.zc && kd2h) {  // the copy-out (TLS 1.3: gather) kernel has written `out` already
             SG_HIP(hipEventRecord(s.ev[3], P.krn));
             return SG_OK;
+        }
+        if (gather) {
+            // the chunk's kernels have completed: exactly the bytes it delivers leave the device
+            const uint32_t bytes = s.result(false)[1];
+            uint8_t* dst = s.zc ? out + gpos : s.h_out;
+            gpos += bytes;
+            if (!bytes) {
+                SG_HIP(hipEventRecord(s.ev[3], P.krn));
+                return SG_OK;
+            }
+            return d2h(s, dst, s.d_wire, bytes, P.d2h);
         }
         if (s.zc) return d2h(s, out + s.out0, s.d_out, s.shape.pre[s.nrec], P.d2h);
         return d2h(s, s.h_out, s.d_out, (size_t)s.nrec * kSlot, P.d2h);
@@ -830,4 +1001,42 @@ int sg_read_records(sg_ctx* c, uint64_t seq0, const uint8_t* wire, size_t wire_l
     return SG_OK;
 }
 
+}  // namespace
+}  // namespace sg
+
+extern "C" {
+
+int64_t sg_write_records(sg_ctx* c, uint64_t seq0, uint8_t content_type, uint8_t ver_major, uint8_t ver_minor,
+                         const uint8_t* data, size_t len, uint8_t* wire, size_t wire_cap, size_t* wire_len) {
+    return sg::write_records(sg::RecordForm::kDraft, c, seq0, content_type, ver_major, ver_minor, data, len, wire,
+                             wire_cap, wire_len);
+}
+int64_t sg_write_records_rfc7905(sg_ctx* c, uint64_t seq0, uint8_t content_type, uint8_t ver_major, uint8_t ver_minor,
+                                 const uint8_t* data, size_t len, uint8_t* wire, size_t wire_cap, size_t* wire_len) {
+    return sg::write_records(sg::RecordForm::kRfc8439, c, seq0, content_type, ver_major, ver_minor, data, len, wire,
+                             wire_cap, wire_len);
+}
+int64_t sg_write_records_tls13(sg_ctx* c, uint64_t seq0, uint8_t inner_type, const uint8_t* data, size_t len,
+                               uint8_t* wire, size_t wire_cap, size_t* wire_len) {
+    return sg::write_records(sg::RecordForm::kTls13, c, seq0, inner_type, 3, 3, data, len, wire, wire_cap, wire_len);
+}
+
+int sg_read_records(sg_ctx* c, uint64_t seq0, const uint8_t* wire, size_t wire_len, uint8_t* out, size_t out_cap,
+                    uint8_t* types, uint32_t* frag_lens, size_t max_records, sg_read_result* res) {
+    return sg::read_records(sg::RecordForm::kDraft, c, seq0, wire, wire_len, out, out_cap, types, frag_lens,
+                            max_records, res);
+}
+int sg_read_records_rfc7905(sg_ctx* c, uint64_t seq0, const uint8_t* wire, size_t wire_len, uint8_t* out,
+                            size_t out_cap, uint8_t* types, uint32_t* frag_lens, size_t max_records,
+                            sg_read_result* res) {
+    return sg::read_records(sg::RecordForm::kRfc8439, c, seq0, wire, wire_len, out, out_cap, types, frag_lens,
+                            max_records, res);
+}
+int sg_read_records_tls13(sg_ctx* c, uint64_t seq0, const uint8_t* wire, size_t wire_len, uint8_t* out, size_t out_cap,
+                          uint8_t* types, uint32_t* frag_lens, size_t max_records, sg_read_result* res) {
+    return sg::read_records(sg::RecordForm::kTls13, c, seq0, wire, wire_len, out, out_cap, types, frag_lens,
+                            max_records, res);
+}
+
 }  // extern "C"
+

@@ -26,7 +26,8 @@ import struct
 from dataclasses import dataclass
 
 from . import _native as N
-from .cipher import ChaCha20Poly1305Decryptor, ChaCha20Poly1305Encryptor, TlsError, TlsErrorKind
+from .cipher import (ChaCha20Poly1305Decryptor, ChaCha20Poly1305Encryptor, ChaCha20Poly1305Rfc7905Decryptor,
+                     ChaCha20Poly1305Rfc7905Encryptor, TlsError, TlsErrorKind)
 
 TLS_VERSION = (3, 3)                       # tls.rs:17
 RECORD_MAX_LEN = 1 << 14                   # tls.rs:32
@@ -108,13 +109,18 @@ class TlsWriter:
 
     def write_data(self, ty: ContentType, data: bytes) -> None:  # tls.rs:137-147
         major, minor = TLS_VERSION
-        if isinstance(self.encryptor, ChaCha20Poly1305Encryptor) and len(data) > 0:
+        write = None
+        if isinstance(self.encryptor, ChaCha20Poly1305Encryptor):
+            write = N.load().sg_write_records
+        elif isinstance(self.encryptor, ChaCha20Poly1305Rfc7905Encryptor):
+            write = N.load().sg_write_records_rfc7905  # the same wire, RFC 8439 under it
+        if write is not None and len(data) > 0:
             wire = (C.c_uint8 * N.load().sg_wire_bound(len(data)))()
             wl = C.c_size_t(0)
             src = (C.c_uint8 * len(data)).from_buffer_copy(data) if not isinstance(data, bytearray) else \
                 (C.c_uint8 * len(data)).from_buffer(data)
-            nrec = N.check(N.load().sg_write_records(self.encryptor._ptr, self.write_count, int(ty), major, minor,
-                                                     src, len(data), wire, len(wire), C.byref(wl)))
+            nrec = N.check(write(self.encryptor._ptr, self.write_count, int(ty), major, minor,
+                                 src, len(data), wire, len(wire), C.byref(wl)))
             self._write(bytes(memoryview(wire)[:wl.value]))
             self.write_count += nrec
             return
@@ -251,8 +257,11 @@ class RecordStreamReader:
         src = (C.c_uint8 * len(self.buf)).from_buffer(self.buf)
         out = (C.c_uint8 * max(len(self.buf), 1))()
         res = N.SgReadResult()
-        N.check(lib.sg_read_records(self.dec._ptr, self.read_count, src, len(self.buf), out, len(out),
-                                    self.types, self.lens, self.max_records, C.byref(res)))
+        read = lib.sg_read_records
+        if isinstance(self.dec, ChaCha20Poly1305Rfc7905Decryptor):
+            read = lib.sg_read_records_rfc7905
+        N.check(read(self.dec._ptr, self.read_count, src, len(self.buf), out, len(out),
+                     self.types, self.lens, self.max_records, C.byref(res)))
         del src
         msgs, pos = [], 0
         for i in range(res.records):
