@@ -251,7 +251,8 @@ int sg_open_batch_rfc8439(const sg_batch* b, const sg_batch_rfc8439* x);
  * Seal: len_i is the content length, 0..2^14.  b->content_type is the inner
  *   type of every record of the call and must be non-zero (a zero would read
  *   as padding).  Record i reads len_i bytes and writes len_i + 17:
- *   ct(content || type) || tag.  Seal adds no padding.
+ *   ct(content || type) || tag.  This call adds no padding and gives every
+ *   record the one type; sg_seal_batch_tls13_ex below does both.
  * Open: len_i is the fragment length, at most 2^14 + 256; below 16 the status
  *   is SG_E_SHORT.  The len_i - 16 inner bytes go to `out` as in the RFC call.
  *   Then, for every record whose status is SG_OK, the last non-zero inner byte
@@ -269,8 +270,14 @@ int sg_open_batch_rfc8439(const sg_batch* b, const sg_batch_rfc8439* x);
  * Routes: a uniform batch of full records (uniform_len 2^14 on seal, 2^14 + 17
  * on open; bases and strides 16-byte aligned, no len / offset arrays) runs on
  * the wave-per-record kernel, whose keying pre-pass takes the type byte and
- * its MAC block; every other batch on the size classes (inner lengths are
- * never multiples of 64, so mixed batches take no packed or bucket route). */
+ * its MAC block.  In every other batch with a len array, a record whose inner
+ * length (seal: as sealed; open: len_i - 16) is a multiple of 64 in 64..4096
+ * and whose input and output addresses are 16-byte aligned runs on the packed
+ * kernel in its TLS 1.3 form -- on seal that needs padding (below), on open a
+ * peer that pads so -- under the conditions of the RFC call (not under capture,
+ * per-record arrays 4-byte aligned, sg_set_packed); everything else, padded
+ * records above 4 KiB included, on the size classes.  sg_last_batch_routes
+ * reports where the records of a mixed call went. */
 typedef struct sg_batch_tls13 {
     const uint8_t* ivs;          /* device [num_keys][12], 4-byte aligned, required        */
     uint8_t*       inner_type;   /* open: device, count bytes, required; seal: not read    */
@@ -281,10 +288,43 @@ typedef struct sg_batch_tls13 {
 int sg_seal_batch_tls13(const sg_batch* b, const sg_batch_tls13* x);
 int sg_open_batch_tls13(const sg_batch* b, const sg_batch_tls13* x);
 #define SG_STATUS_NO_TYPE 5      /* open: tag good, inner plaintext all zero (or empty)    */
-/* Which route a TLS 1.3 batch would take (host only, no GPU call): 0 = size
- * classes, 1 = wave-per-record kernel, SG_E_ARG for a batch the calls above
- * reject on its own fields; honours sg_set_lockstep. */
+/* Which route a TLS 1.3 batch would take (host only, no GPU call): 1 = the
+ * uniform wave-per-record kernel, 0 = not that route (the size classes and,
+ * for the eligible records of a mixed batch, the packed kernel: those are
+ * chosen per record on the device, see sg_last_batch_routes), SG_E_ARG for a
+ * batch the calls above reject on its own fields; honours sg_set_lockstep. */
 int sg_batch_tls13_route(const sg_batch* b, int open);
+
+/* TLS 1.3 seal with record padding (RFC 8446 section 5.4) and a type per record.
+ * `b` and `x` are those of sg_seal_batch_tls13.  Record i reads len_i content
+ * bytes -- no byte of `in` at or beyond len_i, except that a record on the packed
+ * kernel may load the aligned 16-byte unit holding its last content byte whole --
+ * and writes exactly inner_i + 16 bytes:
+ *   ct(content_i || type_i || zeros) || tag,  inner_i = sg_tls13_inner_len(len_i, pad_to)
+ * under the AD 17 03 03 be16(inner_i + 16).  Room in `out` (strides, offsets) for
+ * the padded fragments is the caller's to provide; max_len / uniform_len still
+ * bound the content lengths, and the library derives the largest inner length.
+ * type_i is inner_types[i], or b->content_type for every record when inner_types
+ * is NULL.  With {NULL, 0 or 1, 0} the call is sg_seal_batch_tls13 byte for byte,
+ * routes included.  A seal with inner_types never takes the uniform wave-per-record
+ * route (its pre-pass appends the call's one type); at 2^14 content bytes padding
+ * changes nothing.  Padding to a multiple of 64 makes every record of up to 4095
+ * content bytes eligible for the packed kernel (above).
+ * SG_E_ARG before any GPU work: o NULL, o->flags non-zero, pad_to above 2^14, and
+ * everything sg_seal_batch_tls13 rejects -- a zero b->content_type only when
+ * inner_types is NULL. */
+#define SG_TLS13_MAX_INNER (16384u + 1u)
+/* inner plaintext length of a record of `len` (<= 2^14) content bytes under pad_to:
+ * pad_to <= 1: len + 1;  else min(roundup(len + 1, pad_to), 2^14 + 1).  Host only. */
+uint32_t sg_tls13_inner_len(uint32_t len, uint32_t pad_to);
+
+typedef struct sg_tls13_seal_opts {
+    const uint8_t* inner_types; /* device, count bytes, or NULL: b->content_type for every record.
+                                   Entries must be non-zero; not checked (device memory) */
+    uint32_t       pad_to;      /* 0 or 1: no padding; else 2..2^14, any value (no power-of-two rule) */
+    uint32_t       flags;       /* 0; anything else SG_E_ARG */
+} sg_tls13_seal_opts;           /* 16 bytes */
+int sg_seal_batch_tls13_ex(const sg_batch* b, const sg_batch_tls13* x, const sg_tls13_seal_opts* o);
 
 /* ---- long messages: any data and AD length, one message over the whole chip
  * Encryptor::encrypt / Decryptor::decrypt take data and additional data of any

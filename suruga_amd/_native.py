@@ -38,7 +38,7 @@ EXPORTS = [
     "sg_key_size", "sg_fixed_iv_len", "sg_mac_len", "sg_abi_version",
     "sg_ctx_new", "sg_ctx_free", "sg_seal", "sg_open",
     "sg_workspace_size", "sg_seal_batch", "sg_open_batch", "sg_seal_batch_rfc8439", "sg_open_batch_rfc8439",
-    "sg_seal_batch_tls13", "sg_open_batch_tls13", "sg_batch_tls13_route",
+    "sg_seal_batch_tls13", "sg_open_batch_tls13", "sg_batch_tls13_route", "sg_seal_batch_tls13_ex", "sg_tls13_inner_len",
     "sg_fill_records", "sg_compare_records",
     "sg_last_error", "sg_build_info", "sg_source_hash", "sg_set_timing", "sg_timing_read", "sg_set_lockstep", "sg_set_packed",
     "sg_last_batch_routes",
@@ -105,6 +105,15 @@ class SgBatchTls13(C.Structure):
 
     _fields_ = [("ivs", C.c_void_p), ("inner_type", C.c_void_p), ("content_len", C.c_void_p), ("flags", C.c_uint32),
                 ("_pad", C.c_uint32)]
+
+
+class SgTls13SealOpts(C.Structure):
+    """Mirror of ``struct sg_tls13_seal_opts``."""
+
+    _fields_ = [("inner_types", C.c_void_p), ("pad_to", C.c_uint32), ("flags", C.c_uint32)]
+
+
+SG_TLS13_MAX_INNER = (1 << 14) + 1
 
 
 class SgBatchRoutes(C.Structure):
@@ -276,6 +285,10 @@ def _declare(lib: C.CDLL) -> None:
     for f in (lib.sg_seal_batch_tls13, lib.sg_open_batch_tls13):
         f.restype = C.c_int
         f.argtypes = [C.POINTER(SgBatch), C.POINTER(SgBatchTls13)]
+    lib.sg_seal_batch_tls13_ex.restype = C.c_int
+    lib.sg_seal_batch_tls13_ex.argtypes = [C.POINTER(SgBatch), C.POINTER(SgBatchTls13), C.POINTER(SgTls13SealOpts)]
+    lib.sg_tls13_inner_len.restype = C.c_uint32
+    lib.sg_tls13_inner_len.argtypes = [C.c_uint32, C.c_uint32]
     lib.sg_batch_tls13_route.restype = C.c_int
     lib.sg_batch_tls13_route.argtypes = [C.POINTER(SgBatch), C.c_int]
     lib.sg_fill_records.restype = C.c_int

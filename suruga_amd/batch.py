@@ -13,7 +13,9 @@ RFC 7905 nonce (the key's write IV in ``ivs`` XOR the sequence number).
 
 ``seal_tls13`` / ``open_tls13`` run it as TLS 1.3 records (RFC 8446 section 5.2,
 ``sg_seal_batch_tls13`` / ``sg_open_batch_tls13``): the device appends the
-inner type byte on seal and returns ``inner_type`` / ``content_len`` on open.
+inner type byte on seal and returns ``inner_type`` / ``content_len`` on open;
+``seal_tls13(batch, pad_to=, inner_types=)`` pads the records (RFC 8446 section 5.4)
+and takes a type per record (``sg_seal_batch_tls13_ex``).
 
 Tensors are torch tensors on the GPU (PyTorch is used here only for device
 memory and streams); all arithmetic runs in the gfx950 kernels.
@@ -157,11 +159,25 @@ def open_(batch: Batch) -> None:
     N.check(N.load().sg_open_batch(C.byref(cb)))
 
 
-def seal_tls13(batch: Batch) -> None:
-    """Seal every record as a TLS 1.3 record: out_i = ct(content_i || type) || tag_i,
-    len_i + 17 bytes; the type is ``batch.content_type`` (RFC 8446 section 5.2)."""
+def seal_tls13(batch: Batch, pad_to: int = 0, inner_types=None) -> None:
+    """Seal every record as a TLS 1.3 record: out_i = ct(content_i || type_i || zeros) || tag_i,
+    ``tls13_inner_len(len_i, pad_to) + 16`` bytes (RFC 8446 section 5.2, 5.4).  The type is
+    ``batch.content_type``, or ``inner_types[i]`` (uint8 [count], device) where given.  Without
+    ``pad_to`` and ``inner_types`` this is ``sg_seal_batch_tls13`` (len_i + 17 bytes), otherwise
+    ``sg_seal_batch_tls13_ex``."""
     cb, xb = batch.to_c(), batch.to_c_tls13()
-    N.check(N.load().sg_seal_batch_tls13(C.byref(cb), C.byref(xb)))
+    if not pad_to and inner_types is None:
+        N.check(N.load().sg_seal_batch_tls13(C.byref(cb), C.byref(xb)))
+        return
+    o = N.SgTls13SealOpts()
+    o.inner_types, o.pad_to, o.flags = _ptr(inner_types), pad_to, 0
+    N.check(N.load().sg_seal_batch_tls13_ex(C.byref(cb), C.byref(xb), C.byref(o)))
+
+
+def tls13_inner_len(n: int, pad_to: int) -> int:
+    """Length of the inner plaintext a TLS 1.3 seal builds of ``n`` content bytes under ``pad_to``
+    (``sg_tls13_inner_len``): n + 1, rounded up to a multiple of pad_to, at most 2^14 + 1."""
+    return int(N.load().sg_tls13_inner_len(n, pad_to))
 
 
 def open_tls13(batch: Batch) -> None:
@@ -175,8 +191,9 @@ def open_tls13(batch: Batch) -> None:
 
 
 def tls13_route(batch: Batch, open: bool) -> int:  # noqa: A002  (the C argument's name)
-    """The route ``seal_tls13`` / ``open_tls13`` would take, without any GPU call:
-    0 the size classes, 1 the wave-per-record kernel (``sg_batch_tls13_route``)."""
+    """The route ``seal_tls13`` / ``open_tls13`` would take, without any GPU call: 1 the uniform
+    wave-per-record kernel, 0 not that route -- the size classes and, for the eligible records
+    of a mixed batch, the packed kernel, which ``last_routes`` reports (``sg_batch_tls13_route``)."""
     cb = batch.to_c()
     return N.check(N.load().sg_batch_tls13_route(C.byref(cb), 1 if open else 0))
 
@@ -207,7 +224,7 @@ def timing_read() -> dict:
 
 
 def last_routes() -> dict:
-    """Where the records of this thread's last ``seal`` / ``open_`` went
+    """Where the records of this thread's last ``seal`` / ``open_`` / ``seal_tls13`` / ``open_tls13`` went
     (``sg_last_batch_routes``): ``known`` is False unless that call was a mixed
     batch whose list populations the dispatcher read back."""
     r = N.SgBatchRoutes()

@@ -171,6 +171,10 @@ struct BatchForm {
     const uint8_t* ivs = nullptr;     // write IVs: RFC 8439 TLS mode and TLS 1.3
     uint8_t* inner_type = nullptr;    // TLS 1.3 open
     uint32_t* content_len = nullptr;  // TLS 1.3 open
+    // TLS 1.3 seal options (sg_seal_batch_tls13_ex); the plain seal is {NULL, 0, 0}
+    const uint8_t* inner_types = nullptr;  // per-record inner types, or NULL: b->content_type
+    uint32_t pad_to = 0u;                  // tls13_inner_len's policy (sg_layout.h)
+    uint32_t oflags = 0u;                  // sg_tls13_seal_opts.flags (must be 0)
 };
 int known_flags(const sg_batch* b) {
     return (b->flags & ~(SG_BATCH_TLS | SG_BATCH_KEEP_FAILED)) ? fail(SG_E_ARG, "unknown flags%s") : SG_OK;
@@ -180,7 +184,8 @@ int known_flags(const sg_batch* b) {
 constexpr uint32_t kTls13MaxContent = 1u << 14;
 constexpr uint32_t kTls13MaxFragment = (1u << 14) + 256u;
 // What the TLS 1.3 calls check of the batch itself: all sg_batch_tls13_route checks.
-int validate_tls13(const sg_batch* b, bool open) {
+// typed: the records bring their own inner types, so b->content_type is not read.
+int validate_tls13(const sg_batch* b, bool open, bool typed = false) {
     if (!b) return fail(SG_E_ARG, "batch is NULL%s");
     if (!(b->flags & SG_BATCH_TLS))
         return fail(SG_E_ARG, "the TLS 1.3 batch builds nonce and AD on the device: SG_BATCH_TLS must be set%s");
@@ -188,7 +193,7 @@ int validate_tls13(const sg_batch* b, bool open) {
     const uint32_t maxl = b->len ? b->max_len : b->uniform_len;
     if (!open && maxl > kTls13MaxContent) return fail(SG_E_ARG, "TLS 1.3 content longer than 2^14 bytes%s");
     if (open && maxl > kTls13MaxFragment) return fail(SG_E_ARG, "TLS 1.3 fragment longer than 2^14 + 256 bytes%s");
-    if (!open && b->content_type == 0)
+    if (!open && !typed && b->content_type == 0)
         return fail(SG_E_ARG, "the inner content type must be non-zero (a zero byte reads as padding)%s");
     return SG_OK;
 }
@@ -199,7 +204,9 @@ int validate(const sg_batch* b, const BatchForm& f, bool open) {
     const bool t13 = f.form == RecordForm::kTls13;
     if (t13) {
         if (f.xflags) return fail(SG_E_ARG, "sg_batch_tls13.flags must be 0%s");
-        if (const int rc = validate_tls13(b, open)) return rc;
+        if (f.oflags) return fail(SG_E_ARG, "sg_tls13_seal_opts.flags must be 0%s");
+        if (f.pad_to > kTls13MaxContent) return fail(SG_E_ARG, "pad_to above 2^14%s");
+        if (const int rc = validate_tls13(b, open, f.inner_types != nullptr)) return rc;
         if (!f.ivs) return fail(SG_E_ARG, "the TLS 1.3 batch needs the write IVs (sg_batch_tls13.ivs)%s");
     }
     if (!b) return fail(SG_E_ARG, "batch is NULL%s");
@@ -238,7 +245,8 @@ int validate(const sg_batch* b, const BatchForm& f, bool open) {
 // The wave-per-record kernel (sg_wpr.hip) takes uniform batches of full records
 // (wpr_len: 2^14 bytes, or the fragment they seal to in this form) in a 16-byte
 // aligned strided layout; everything else runs on the size-class kernels.
-bool wpr_eligible(const sg_batch* b, RecordForm form, bool open) {
+bool wpr_eligible(const sg_batch* b, RecordForm form, bool open, bool typed = false) {
+    if (typed) return false;  // TLS 1.3 seal: its keying pre-pass appends the call's one type
     if (!sg::wpr_enabled() || b->len || b->in_off || b->out_off) return false;
     if (b->uniform_len != sg::wpr_len(form, open)) return false;
     // per-record scalars are read as dwords: key index, sequence numbers, nonces (8 or 12 bytes)
@@ -277,23 +285,31 @@ int launch_batch(const sg_batch* b, const BatchForm& f, bool open, hipStream_t s
     p.tls13 = t13 ? 1u : 0u;
     p.ivs = f.ivs;
     p.ad_len = p.tls ? sg::tls_ad_len(f.form) : b->ad_len;
+    if (t13) {  // the seal options, in the slots of nonces and ad_stride (explicit mode only; sg_internal.h)
+        p.inner_types = f.inner_types;
+        p.pad_to = f.pad_to;
+    }
     const uint32_t maxl = b->len ? b->max_len : b->uniform_len;
-    // (TLS 1.3 seal: the AEAD runs over the inner plaintext, content || type)
-    const uint32_t max_n = open ? (maxl >= 16u ? maxl - 16u : 0u) : maxl + sg::seal_extra(f.form);
+    // (TLS 1.3 seal: the AEAD runs over the inner plaintext, content || type || zeros; the
+    // largest one sizes the keying geometry, the classify bound and the LDS slots)
+    const uint32_t max_n = open ? (maxl >= 16u ? maxl - 16u : 0u) : t13 ? sg::tls13_inner_len(maxl, f.pad_to) : maxl;
+    static_assert(sg::tls13_inner_len(100u, 0u) == 100u + sg::seal_extra(RecordForm::kTls13), "no padding: the one type byte");
     const bool uniform = !b->len || sg::size_class(max_n) == 0u;
-    const bool wpr = wpr_eligible(b, f.form, open);
+    const bool wpr = wpr_eligible(b, f.form, open, f.inner_types != nullptr);
     // mixed TLS batches: full-chunk records (4-16 KiB, multiples of 64 bytes) go to the
     // wave-per-record buckets and the 64 B-4 KiB ones to the packed kernel (sg_pack.hip), in
     // either construction; not under capture (they are launched on the populations read
     // back), and the per-record arrays are read as dwords by the routed kernels
-    // (TLS 1.3: inner lengths of full chunks + 1 are no multiple of 64; the routed launchers refuse the form)
-    if (!wpr && !uniform && p.tls && !t13 && ((sg::wpr_enabled() && max_n > 4096u) || (sg::pack_enabled() && max_n >= 64u))) {
+    // (TLS 1.3: the packed kernel alone, for inner lengths that are multiples of 64 -- a seal padded
+    // so, a peer's fragments padded so; the J = 2..4 buckets have no TLS 1.3 form)
+    const bool buckets = sg::wpr_enabled() && max_n > 4096u && !t13;
+    if (!wpr && !uniform && p.tls && (buckets || (sg::pack_enabled() && max_n >= 64u))) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         SG_HIP(hipStreamIsCapturing(s, &cap));
         const bool ok = cap == hipStreamCaptureStatusNone &&
                         ((uintptr_t)b->key_index | (uintptr_t)b->seq | (uintptr_t)b->len | (uintptr_t)b->in_off |
                          (uintptr_t)b->out_off) % 4u == 0u;
-        p.wpr_mix = ok && sg::wpr_enabled() && max_n > 4096u;
+        p.wpr_mix = ok && buckets;
         p.pack_mix = ok && sg::pack_enabled();
     }
 
@@ -574,6 +590,16 @@ static int run_batch_tls13(const sg_batch* b, const sg_batch_tls13* x, bool open
     return run_batch(b, {RecordForm::kTls13, x->flags, x->ivs, x->inner_type, x->content_len}, open);
 }
 int sg_seal_batch_tls13(const sg_batch* b, const sg_batch_tls13* x) { return run_batch_tls13(b, x, false); }
+int sg_seal_batch_tls13_ex(const sg_batch* b, const sg_batch_tls13* x, const sg_tls13_seal_opts* o) {
+    if (!x) return fail(SG_E_ARG, "sg_batch_tls13 is NULL%s");
+    if (!o) return fail(SG_E_ARG, "sg_tls13_seal_opts is NULL%s");
+    BatchForm f{RecordForm::kTls13, x->flags, x->ivs, x->inner_type, x->content_len};
+    f.inner_types = o->inner_types;
+    f.pad_to = o->pad_to;
+    f.oflags = o->flags;
+    return run_batch(b, f, false);
+}
+uint32_t sg_tls13_inner_len(uint32_t len, uint32_t pad_to) { return sg::tls13_inner_len(len, pad_to); }
 int sg_open_batch_tls13(const sg_batch* b, const sg_batch_tls13* x) { return run_batch_tls13(b, x, true); }
 int sg_batch_tls13_route(const sg_batch* b, int open) {
     const int rc = validate_tls13(b, open != 0);

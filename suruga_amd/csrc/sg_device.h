@@ -497,6 +497,12 @@ __device__ __forceinline__ uint8_t tls13_ad_byte(uint32_t L, uint32_t i) {
     return (uint8_t)L;
 }
 
+// The inner type byte that a TLS 1.3 seal puts behind record rec's content: the record's
+// own (sg_tls13_seal_opts.inner_types) or the call's content_type
+__device__ __forceinline__ uint8_t tls13_inner_type(const KParams& p, uint32_t rec) {
+    return p.inner_types ? p.inner_types[rec] : (uint8_t)p.tls_hdr;
+}
+
 // Byte i (< ct_offset<C>(adlen)) of the MAC stream in front of the ciphertext:
 // ad || le64(|ad|) in the draft (chacha20_poly1305.rs:24-26), ad and its zero
 // padding in RFC 8439.

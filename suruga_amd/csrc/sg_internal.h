@@ -62,7 +62,11 @@ struct KParams {
     uint32_t num_keys;       // >= 1; key indices are clamped to num_keys - 1 (no read outside the table)
     const uint64_t* seq;
     uint64_t seq0;
-    const uint8_t* nonces;
+    union {                  // (one kernarg slot: the TLS 1.3 form is TLS mode and never reads nonces)
+        const uint8_t* nonces;       // explicit mode
+        const uint8_t* inner_types;  // TLS 1.3 seal (sg_seal_batch_tls13_ex): the records' inner types [count], or
+                                     // NULL: tls_hdr's low byte for every record
+    };
     const uint8_t* ads;
     const uint8_t* in;
     const uint64_t* in_off;
@@ -76,7 +80,11 @@ struct KParams {
     uint32_t uniform_len;
     uint32_t count;
     uint32_t ad_len;         // explicit mode
-    uint32_t ad_stride;
+    union {                  // (likewise: the TLS 1.3 AD is the record header, built on the device)
+        uint32_t ad_stride;  // explicit mode
+        uint32_t pad_to;     // TLS 1.3 seal: the inner plaintext is tls13_inner_len(len, pad_to) bytes,
+                             // content || type || zeros
+    };
     uint32_t tls;            // 1 = SG_BATCH_TLS
     uint32_t tls_hdr;        // content_type | major << 8 | minor << 16
     uint32_t lds_rec_bytes;  // LDS bytes per record slot of the launched size class
@@ -89,6 +97,10 @@ struct KParams {
     uint32_t tls13;          // 1: rfc and tls are 1 too; AD = 17 03 03 be16(fragment length), seal appends
                              // the inner type byte (tls_hdr's low byte) to every record
 };
+// The TLS 1.3 seal options share the slots of two explicit-mode fields, so the struct is the
+// size it was and every kernel argument behind it stays where it was: the kernels of the
+// other record forms are the same code objects byte for byte, kernarg offsets included.
+static_assert(sizeof(KParams) == 184, "KParams: the kernarg layout of every record kernel");
 
 // Every record kernel exists in both constructions (Construction,
 // sg_layout.h): the size classes, the uniform 16 KiB wave-per-record launch,
@@ -99,7 +111,7 @@ struct KParams {
 // (open, p.rfc, p.tls13) as compile-time constants (OPEN.value and T13.value
 // bools, T13 only with C.value == Construction::kRfc8439), so a launcher names
 // its kernel once, as K<OPEN.value, ..., C.value, T13.value>; one without a TLS 1.3
-// form refuses p.tls13 and ignores T13.  The message launchers: (rfc, open), f(OPEN, C).
+// form (the J = 2..4 buckets) refuses p.tls13 and ignores T13.  The message launchers: (rfc, open), f(OPEN, C).
 template <class F>
 inline void with_form(bool rfc, bool open, F&& f) {
     constexpr std::integral_constant<Construction, Construction::kDraft> D{};
@@ -126,7 +138,8 @@ constexpr uint32_t kNumClasses = 8;
 constexpr uint32_t kWprBuckets = 3;
 constexpr uint32_t kWprMinJ = 2;
 // ... and TLS records of 64 B <= n <= 4 KiB, n a multiple of 64, 16-byte
-// aligned, to the packed kernel (sg_pack.hip): list kPackList.
+// aligned, to the packed kernel (sg_pack.hip): list kPackList.  The TLS 1.3
+// form takes this route alone (n: the inner length); it has no buckets.
 constexpr uint32_t kPackList = kNumClasses + kWprBuckets;
 constexpr uint32_t kNumLists = kPackList + 1u;
 constexpr uint32_t kListGridPerCU = 8;   // workgroups per CU for list-driven launches

@@ -43,10 +43,13 @@
 // T13 (KParams.tls13, sg_*_batch_tls13; with Construction::kRfc8439 only) is the
 // TLS 1.3 record form of RFC 8446 section 5.2: the AD is the 5-byte record header
 // 17 03 03 be16(fragment length) (tls13_ad_byte, sg_device.h), and on seal the
-// AEAD input is the record's content and the inner type byte behind it, one byte
-// more than the record's length: the keying and classify kernels count it, and
-// the block that holds it takes the byte path.  The instantiations without it
-// compile to what they were before the parameter.
+// AEAD input is the inner plaintext: the record's content, the inner type byte
+// behind it (the call's, or the record's own: tls13_inner_type) and zeros up to
+// tls13_inner_len(len, pad_to) bytes (sg_layout.h).  The keying and classify
+// kernels count that length; the block that holds the type byte takes the byte
+// path, a block of padding alone reads nothing, and no byte of the input at or
+// beyond len is read.  The instantiations without T13 compile to what they were
+// before the parameter.
 //
 // The launchers at the end are what the rest of the library sees of this file
 // (sg_internal.h); the dispatcher of a batch is sg_dispatch.cpp.
@@ -150,7 +153,7 @@ __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const Ke
     recs[lane] = rec;
     uint32_t* out = stage + lane * kKeyLdsStride;
     const uint32_t len = act ? record_len(p, rec) : 0u;
-    const uint32_t n = OPEN ? (len >= 16u ? len - 16u : 0u) : len + (T13 ? 1u : 0u);
+    const uint32_t n = OPEN ? (len >= 16u ? len - 16u : 0u) : T13 ? tls13_inner_len(len, p.pad_to) : len;
     out[kKeyRecWords] = 0u;  // nothing to write unless keyed below
     if (act) {
         const RecKey rk = record_key<C>(p, rec);
@@ -216,8 +219,9 @@ __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const Ke
 //   [0, S) virtual-block space | S: ad | le64(adlen) | A: ct (n) | le64(n) | zeros
 // ---------------------------------------------------------------------------
 // T13 (TLS 1.3, RFC 8446 section 5.2): n is the inner plaintext length; seal
-// reads len = n - 1 content bytes and appends the inner type byte, so the block
-// that holds it takes the byte path; the AD is the 5-byte record header.
+// reads len content bytes, appends the inner type byte and pads with zeros to n,
+// so the block that holds the type takes the byte path; the AD is the 5-byte
+// record header.
 template <bool OPEN, uint32_t L, Construction C, bool T13>
 __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec, const bool active,
                                             uint8_t* lds, const uint32_t t) {
@@ -227,7 +231,7 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
     bool work = active;
     const uint32_t len = active ? record_len(p, rec) : 0u;
     if (active) {
-        n = len + (T13 && !OPEN ? 1u : 0u);
+        n = T13 && !OPEN ? tls13_inner_len(len, p.pad_to) : len;
         if constexpr (OPEN) {
             if (len < 16u) {  // chacha20_poly1305.rs:68-70 "message too short"
                 if (t == 0) p.status[rec] = 2u;
@@ -240,6 +244,7 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
     uint8_t* out = nullptr;
     constexpr bool RFC = C == Construction::kRfc8439;
     RecKey rk = {};
+    uint8_t type = 0u;  // T13 seal: the inner type byte behind the content
     const uint32_t adlen = T13 ? 5u : p.tls ? 13u : p.ad_len;
     // RFC 8439: [Z, A) ad and its zero padding | A: ct (n) | zeros to 16 | le64(adlen) le64(n)
     // A = Z + 16 ceil(ct_offset<C>(adlen) / 16) and S = A - ct_offset<C>(adlen) (sg_layout.h), spelt by
@@ -254,6 +259,7 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
         in = p.in + rec_in_off(p, rec);
         out = p.out + rec_out_off(p, rec);
         rk = record_key<C>(p, rec);
+        if constexpr (T13 && !OPEN) type = tls13_inner_type(p, rec);
 
         // ---- phase 1: keystream XOR, 64 bytes per lane-block ----------------
         const bool vec_ok = (((uintptr_t)in | (uintptr_t)out) & 15u) == 0u;
@@ -262,9 +268,16 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
         if constexpr (L >= 64u) pre = chacha_pre(rk.k, rk.n13, rk.n14, rk.n15);
         for (uint32_t b = t; b < nblocks; b += L) {
             const uint32_t off = b << 6;
-            if (vec_ok && off + 64u <= (T13 && !OPEN ? len : n)) {
-                const u32x4 d0 = ld16(in + off), d1 = ld16(in + off + 16);
-                const u32x4 d2 = ld16(in + off + 32), d3 = ld16(in + off + 48);
+            // (T13 seal: a block of content alone; or one of padding alone, which reads nothing)
+            const bool zeros = T13 && !OPEN && off > len;
+            if (vec_ok && (off + 64u <= (T13 && !OPEN ? len : n) || (zeros && off + 64u <= n))) {
+                u32x4 d0 = {}, d1 = {}, d2 = {}, d3 = {};
+                if (!zeros) {
+                    d0 = ld16(in + off);
+                    d1 = ld16(in + off + 16);
+                    d2 = ld16(in + off + 32);
+                    d3 = ld16(in + off + 48);
+                }
                 uint32_t ks[16];
                 // data uses blocks 1.. (chacha20_poly1305.rs:52)
                 if constexpr (L >= 64u) chacha_block_pre(ks, pre, rk.k, b + 1u, rk.n13, rk.n14, rk.n15);
@@ -300,7 +313,7 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
                         const uint32_t idx = off + 4u * w + k;
                         if (idx < n) {
                             uint8_t x;
-                            if constexpr (T13 && !OPEN) x = idx < len ? in[idx] : (uint8_t)p.tls_hdr;  // content || type
+                            if constexpr (T13 && !OPEN) x = idx < len ? in[idx] : idx == len ? type : (uint8_t)0u;  // content || type || zeros
                             else x = in[idx];
                             const uint8_t y = x ^ (uint8_t)(ks[w] >> (8u * k));
                             out[idx] = y;
@@ -554,7 +567,7 @@ __global__ __launch_bounds__(256) void sg_aead_list_kernel(const KParams p, cons
 constexpr uint32_t kClassifyThreads = 1024;
 constexpr uint32_t kClassifyPerThread = 4;
 
-// (T13: a TLS 1.3 seal's class is that of its inner length, one byte more)
+// (T13: a TLS 1.3 seal's class and routes are those of its inner length, tls13_inner_len)
 template <bool OPEN, bool T13>
 __global__ __launch_bounds__(1024) void sg_classify_kernel(const KParams p, uint32_t* __restrict__ lists,
                                                            uint32_t* __restrict__ counts, const uint32_t max_n) {
@@ -571,7 +584,7 @@ __global__ __launch_bounds__(1024) void sg_classify_kernel(const KParams p, uint
         cls[i] = kNumLists;
         if (rec < p.count) {
             const uint32_t len = record_len(p, rec);
-            const uint32_t n = OPEN ? (len >= 16u ? len - 16u : 0u) : len + (T13 ? 1u : 0u);
+            const uint32_t n = OPEN ? (len >= 16u ? len - 16u : 0u) : T13 ? tls13_inner_len(len, p.pad_to) : len;
             if (n <= max_n) {
                 const uint32_t J = rec_wpr_bucket(p, rec, n);
                 cls[i] = J ? kNumClasses + J - kWprMinJ : rec_pack(p, rec, n) ? kPackList : size_class(n);

@@ -79,7 +79,27 @@ constexpr bool form_is(RecordForm f, Construction c, uint32_t ad, uint32_t extra
 static_assert(form_is(RecordForm::kDraft, Construction::kDraft, 13u, 0u, 16384u + 16u), "the draft's TLS 1.2 record");
 static_assert(form_is(RecordForm::kRfc8439, Construction::kRfc8439, 13u, 0u, 16384u + 16u), "RFC 7905");
 // RFC 8446 section 5.2: AD = opaque_type || legacy_record_version || length, 1 + 2 + 2 bytes, over
-// TLSInnerPlaintext = content || ContentType (|| zeros, none added here), content of 2^14 bytes (section 5.1)
+// TLSInnerPlaintext = content || ContentType || zeros (tls13_inner_len below), content of 2^14 bytes (section 5.1);
+// seal_extra is the one byte of a seal without padding, which a full record's fragment always is
 static_assert(form_is(RecordForm::kTls13, Construction::kRfc8439, 5u, 1u, 16384u + 17u), "RFC 8446 section 5.2");
+
+// Length of the TLSInnerPlaintext that a TLS 1.3 seal builds of `len` content bytes under
+// the padding policy pad_to (sg_tls13_seal_opts, RFC 8446 section 5.4): content, the type
+// byte, then zeros up to the next multiple of pad_to, but never beyond the 2^14 + 1 bytes
+// of section 5.2.  pad_to 0 and 1 pad nothing.  The host (max_n, sg_tls13_inner_len), the
+// keying and classify kernels, the size classes and the packed kernel all take it from
+// here.  (A length above 2^14, which no call accepts, stays len + 1: over-long, as it was.)
+constexpr uint32_t kTls13MaxInner = 16384u + 1u;
+constexpr uint32_t tls13_inner_len(uint32_t len, uint32_t pad_to) {
+    if (pad_to <= 1u || len >= kTls13MaxInner - 1u) return len + 1u;
+    const uint32_t up = (len + pad_to) / pad_to * pad_to;  // len + 1 rounded up
+    return up < kTls13MaxInner ? up : kTls13MaxInner;
+}
+static_assert(tls13_inner_len(0u, 0u) == 1u && tls13_inner_len(16384u, 1u) == 16385u, "no padding: content || type");
+static_assert(tls13_inner_len(0u, 64u) == 64u && tls13_inner_len(63u, 64u) == 64u, "type byte in the content's last block");
+static_assert(tls13_inner_len(64u, 64u) == 128u, "the type byte opens a block of its own");
+static_assert(tls13_inner_len(16384u, 64u) == 16385u && tls13_inner_len(16383u, 16384u) == 16384u, "section 5.2's bound");
+static_assert(tls13_inner_len(16320u, 4096u) == 16384u && tls13_inner_len(16383u, 100u) == 16385u, "capped, not rounded");
+static_assert(tls13_inner_len(100u, 100u) == 200u && tls13_inner_len(99u, 100u) == 100u, "any pad_to, no power-of-two rule");
 
 }  // namespace sg

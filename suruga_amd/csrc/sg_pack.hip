@@ -78,6 +78,28 @@
 // 2 (at most 1).  The draft's fifth value, which could push h4 to 5, is gone,
 // so the RFC stream holds these bounds with more room than the draft's.
 // tests/test_pack_mac_model_rfc8439.py pins the decomposition and the bounds.
+//
+// T13 (sg_seal_batch_tls13_ex / sg_open_batch_tls13, with Construction::kRfc8439
+// only): TLS 1.3 records (RFC 8446 section 5.2) whose inner plaintext content ||
+// type || zeros is a multiple of 64 bytes in 64..4096 -- what a seal under
+// pad_to = 64 builds of every record of up to 4095 content bytes, and what a peer
+// that pads so sends.  The MAC stream is AD(5) || 0^11 || ct || le64(5) || le64(n),
+// n = 64 nb the inner length: block 0 the record header 17 03 03 be16(n + 16) and
+// eleven zero bytes, then the RFC form's all-full-block stream, B = 4 nb + 2.  The
+// lane Horner, the weights and their tables are the RFC form's; the constant term is
+//   (block0 + 2^128) r^B + (5 + n 2^64 + 2^128) r.
+// The lane terms are the RFC form's terms (a lane's Q depends on its ciphertext and r
+// alone), so the bounds argued above for the RFC stream hold unchanged; the
+// constant term is one fully carried product sum in either form.  On seal the
+// lanes build the inner plaintext: the lane whose block holds the content's end
+// loads the 16-byte units that hold a content byte (the last one whole, at most 15
+// bytes behind the content in an aligned unit, hence on the content's page),
+// clears the rest and sets the type byte; lanes behind it load nothing and encrypt
+// zeros; with no content nothing is read.  The content length and the type reach
+// the chunk lanes in the slot word that holds nb.  Open is the RFC form's with
+// n = len - 16 and the other constant term; sg_strip_kernel (sg_plumb.hip) finds
+// type and content length afterwards.  tests/test_pack_mac_model_tls13.py pins the
+// decomposition and the bounds for this stream.
 #include "sg_internal.h"
 #include "sg_device.h"
 #include "sg_chacha_grp.inc"  // grouped ChaCha20 double round (tools/gen_chacha_grp.py --product)
@@ -243,12 +265,27 @@ __device__ unsigned long long g_pack_prof[kProfWgs][kProfStamps];
 #define SG_STAMP(w, k)
 #endif
 
+// T13 seal: the slot word kSNb also carries what the chunk lanes need to build the inner
+// plaintext -- nb (<= 64) in bits 0-6, the content length (< 4096: the inner length is at
+// most 4096 and holds the type byte) in bits 8-19, the inner type in bits 24-31 -- so the
+// slot keeps its stride and PackLds its three workgroups per CU.
+constexpr uint32_t kNbMask = 0x7fu, kClenShift = 8u, kClenMask = 0xfffu, kTypeShift = 24u;
+static_assert(kPackBlocks / kPackRecs <= kNbMask && 4096u - 1u <= kClenMask, "slot word of the TLS 1.3 seal");
+template <bool T13SEAL>
+__device__ __forceinline__ uint32_t slot_nb(const uint32_t* sl) {
+    if constexpr (T13SEAL) return sl[kSNb] & kNbMask;
+    else return sl[kSNb];
+}
+
 // One run: records first .. first + nrec - 1 of the packed list.
-template <bool OPEN, Construction C>
+// T13 (with Construction::kRfc8439 only): the TLS 1.3 record form, header comment.
+template <bool OPEN, Construction C, bool T13>
 __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __restrict__ list, const uint32_t first,
                                          const uint32_t nrec, PackLds& L, const uint32_t tid, const uint32_t lane,
                                          const uint32_t wave) {
     constexpr bool RFC = C == Construction::kRfc8439;
+    static_assert(!T13 || RFC, "TLS 1.3 records are RFC 8439");
+    constexpr bool T13SEAL = T13 && !OPEN;
 
     SG_STAMP(0u, 0);
     for (uint32_t i = tid; i < kPackBlocks / 32u; i += kPackThreads) L.bits[i] = 0u;
@@ -271,7 +308,8 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
             const uint64_t io = rec_in_off(p, rec);
             const uint64_t oo = rec_out_off(p, rec);
             const RecKey rk = record_key<C>(p, rec);
-            const uint32_t n = OPEN ? len - 16u : len;  // listed records: 64 <= n <= 4096, n % 64 == 0
+            // listed records: 64 <= n <= 4096, n % 64 == 0 (T13 seal: the inner length, as classified)
+            const uint32_t n = OPEN ? len - 16u : T13 ? tls13_inner_len(len, p.pad_to) : len;
             nb = n >> 6;
 #if SG_PACK_PROFILE
             if (rk.k[0] == 0x12345678u && rk.seq == 1u) g_pack_prof[0][11] = io + oo;  // wait for the loads
@@ -289,7 +327,9 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
             sl[kSIn] = (uint32_t)io; sl[kSIn + 1] = (uint32_t)(io >> 32);
             sl[kSOut] = (uint32_t)oo; sl[kSOut + 1] = (uint32_t)(oo >> 32);
             sl[kSS + 0] = pk.s[0]; sl[kSS + 1] = pk.s[1]; sl[kSS + 2] = pk.s[2]; sl[kSS + 3] = pk.s[3];
-            sl[kSNb] = nb;
+            if constexpr (T13SEAL)
+                sl[kSNb] = nb | (len << kClenShift) | ((uint32_t)tls13_inner_type(p, rec) << kTypeShift);
+            else sl[kSNb] = nb;
             if constexpr (RFC) sl[kSN13] = rk.n13;
             else sl[kSRec] = rec;
             // hi[a] = r^(1 + 32 a), lo[b] = R^b (R = r^4), two product chains
@@ -317,7 +357,14 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
             const F26 rB = fmul(fmul(wl, R), r);
             // block 0: be64(seq) || type || major || minor || be16(n) || le64(13)[0..3] (tls.rs:103-112)
             const uint32_t w2 = (p.tls_hdr & 0x00ffffffu) | (((n >> 8) & 0xffu) << 24);
-            if constexpr (RFC) {
+            if constexpr (T13) {
+                // block 0: the record header 17 03 03 be16(n + 16) and eleven zero bytes (RFC 8446
+                // section 5.2); last block: le64(5) || le64(n)
+                const uint32_t L = n + 16u;
+                const F26 blk0 = words_to_f26(0x00030317u | ((L >> 8) << 24), L & 0xffu, 0u, 0u, 1u);  // + the pad 2^128
+                const F26 sfx = words_to_f26(5u, 0u, n, 0u, 1u);                                       // 5 + n 2^64 + 2^128
+                store_f26(sl + kSCtot, fmul_add(blk0, rB, fmul(sfx, r)));
+            } else if constexpr (RFC) {
                 // block 0: the AD and three zero bytes; its be64(seq) from the sequence number
                 // (the nonce words carry the write IV, RFC 7905); last block: le64(13) || le64(n)
                 const uint32_t a0 = bswap32((uint32_t)(rk.seq >> 32)), a1 = bswap32((uint32_t)rk.seq);
@@ -403,7 +450,38 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
         const uint64_t io = (uint64_t)sl[kSIn] | ((uint64_t)sl[kSIn + 1] << 32);
         const uint64_t oo = (uint64_t)sl[kSOut] | ((uint64_t)sl[kSOut + 1] << 32);
         u32x4 d0 = {}, d1 = {}, d2 = {}, d3 = {};
-        if (valid) {
+        if constexpr (T13SEAL) {
+            // The lane's block of the inner plaintext content || type || zeros: e content bytes
+            // from the block's start on (e <= 0: none).  A block of content alone loads as in
+            // the other forms; the block with the content's end loads the 16-byte units that
+            // hold a content byte (the last one whole: at most 15 bytes behind the content, in
+            // an aligned unit and so on the content's page), clears what is not content and
+            // sets the type byte; a block of padding alone loads nothing.
+            const uint32_t w = sl[kSNb];
+            const int32_t e = (int32_t)((w >> kClenShift) & kClenMask) - (int32_t)(64u * j);
+            if (valid && e > 0) {
+                const uint8_t* src = p.in + io + 64u * j;
+                d0 = pld16(src);
+                if (e > 16) d1 = pld16(src + 16);
+                if (e > 32) d2 = pld16(src + 32);
+                if (e > 48) d3 = pld16(src + 48);
+            }
+            if (valid && e >= 0 && e < 64) {
+                const uint32_t type = w >> kTypeShift;
+                uint32_t iw[16] = {d0[0], d0[1], d0[2], d0[3], d1[0], d1[1], d1[2], d1[3],
+                                   d2[0], d2[1], d2[2], d2[3], d3[0], d3[1], d3[2], d3[3]};
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int32_t k = e - 4 * i;  // content bytes of word i, if in 0..3: the type byte follows them
+                    const uint32_t keep = k >= 4 ? 0xffffffffu : k <= 0 ? 0u : (1u << (8 * k)) - 1u;
+                    iw[i] = (iw[i] & keep) | (k >= 0 && k < 4 ? type << (8 * k) : 0u);
+                }
+                d0 = u32x4{iw[0], iw[1], iw[2], iw[3]};
+                d1 = u32x4{iw[4], iw[5], iw[6], iw[7]};
+                d2 = u32x4{iw[8], iw[9], iw[10], iw[11]};
+                d3 = u32x4{iw[12], iw[13], iw[14], iw[15]};
+            }
+        } else if (valid) {
             const uint8_t* src = p.in + io + 64u * j;
             // (plain policy: the nontemporal one measured -1.3 % on C2 for this
             // kernel's 64-byte lane stride, round 3)
@@ -449,7 +527,7 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
             H32 h;
             lane_mac<C>(h, cw, r0, r1, r2, r3, r1 + (r1 >> 2), r2 + (r2 >> 2), r3 + (r3 >> 2));
             const F26 Q = words_to_f26(h.h0, h.h1, h.h2, h.h3, h.h4);
-            const uint32_t i = sl[kSNb] - 1u - j;
+            const uint32_t i = slot_nb<T13SEAL>(sl) - 1u - j;
             const uint32_t* tb = L.tab + m * kTabWords;
             const F26 W = tab_weight(tb, i);
             uint32_t* ac = L.acc + kAccWords * m;
@@ -469,7 +547,7 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
     // ---- finish: one lane per record (waves 0-1) --------------------------------
     if (act) {
         const uint32_t* sl = L.slot + m0 * kSlotWords;
-        const uint32_t n = 64u * sl[kSNb];
+        const uint32_t n = 64u * slot_nb<T13SEAL>(sl);
         uint32_t rec = 0u;  // (open: the status index)
         if constexpr (!RFC) rec = sl[kSRec];
         else if constexpr (OPEN) rec = list[first + m0];  // the slot word holds n13
@@ -497,7 +575,7 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
 // population is read from the workspace tail (the host does not need it, so
 // the launch goes ahead of the population readback) and the 128-record runs
 // come from a device counter, so that the runs' different lengths even out.
-template <bool OPEN, Construction C>
+template <bool OPEN, Construction C, bool T13>
 __global__ __launch_bounds__(kPackThreads) __attribute__((amdgpu_waves_per_eu(6)))
 void sg_pack_kernel(const KParams p, const uint32_t* __restrict__ list, const uint32_t* __restrict__ cnt, uint32_t* ctr) {
     __shared__ PackLds L;
@@ -510,7 +588,7 @@ void sg_pack_kernel(const KParams p, const uint32_t* __restrict__ list, const ui
         const uint32_t run = __builtin_amdgcn_readfirstlane(L.run);
         if (run >= nruns) break;  // (workgroup-uniform)
         const uint32_t first = run * kPackRecs;
-        pack_run<OPEN, C>(p, list, first, count - first < kPackRecs ? count - first : kPackRecs, L, tid, lane, wave);
+        pack_run<OPEN, C, T13>(p, list, first, count - first < kPackRecs ? count - first : kPackRecs, L, tid, lane, wave);
         __syncthreads();  // the finish read the slots that the next run's setup rewrites, and L.run
     }
 }
@@ -520,14 +598,14 @@ void sg_pack_kernel(const KParams p, const uint32_t* __restrict__ list, const ui
 hipError_t launch_pack(const KParams& p, bool open, const uint32_t* list, const uint32_t* count, uint32_t* ctr,
                        hipStream_t s) {
     if (p.count == 0) return hipSuccess;
-    if (!p.tls || p.tls13) return hipErrorInvalidValue;  // the MAC geometry is the 13-byte TLS AD's
+    if (!p.tls) return hipErrorInvalidValue;  // the MAC geometry is a TLS record's: 13-byte AD, or TLS 1.3's 5
     int cus = 0;
     hipError_t e;
     if ((e = device_cus(&cus)) != hipSuccess) return e;
     const uint32_t most = (p.count + kPackRecs - 1u) / kPackRecs;
     const uint32_t grid = 3u * (uint32_t)cus < most ? 3u * (uint32_t)cus : most;  // three workgroups per CU
-    with_form(p, open, [&](auto OPEN, auto C, auto) {
-        hipLaunchKernelGGL((sg_pack_kernel<OPEN.value, C.value>), dim3(grid), dim3(kPackThreads), 0, s, p, list, count,
+    with_form(p, open, [&](auto OPEN, auto C, auto T13) {
+        hipLaunchKernelGGL((sg_pack_kernel<OPEN.value, C.value, T13.value>), dim3(grid), dim3(kPackThreads), 0, s, p, list, count,
                            ctr);
     });
     return hipGetLastError();
@@ -547,8 +625,10 @@ bool pack_enabled() { return g_pack.on(); }
 int set_pack(int enable) { return g_pack.set(enable); }
 
 const char* pack_kernel_config() {
-    return "sg_pack_kernel v6 (draft and RFC 8439 / RFC 7905 forms; RFC: word-13 nonce, block-aligned 4-step lane "
-           "Horner without a fifth value, AD / length constant term of the RFC stream): mixed-batch TLS records of "
+    return "sg_pack_kernel v7 (draft, RFC 8439 / RFC 7905 and TLS 1.3 forms; RFC: word-13 nonce, block-aligned 4-step lane "
+           "Horner without a fifth value, AD / length constant term of the RFC stream; TLS 1.3: the RFC form over the "
+           "padded inner plaintext, 5-byte AD in the constant term, seal builds content || type || zeros in the lanes): "
+           "mixed-batch TLS records of "
            "64 B-4 KiB (multiples of 64 B) packed 64-byte block per lane "
            "across 128-record runs (512-thread workgroups on a persistent grid taking runs from a device counter, launched "
            "ahead of the population readback; chunk rounds, lock-step grouped ChaCha20 rounds with EXEC limited "

@@ -50,7 +50,7 @@ DRAFT_ARG = ", (sg::Construction)0"  # Construction::kDraft as c++filt prints it
 # The record kernels that take the TLS 1.3 record form as their last template argument
 # (T13 / TLS13, a bool): "..., false>(" is the form they had before it.
 T13_KERNELS = ("sg_wpr_kernel<", "sg_wpr_keying_kernel<", "sg_aead_kernel<", "sg_aead_list_kernel<", "sg_keying_kernel<",
-               "sg_classify_kernel<")
+               "sg_classify_kernel<", "sg_pack_kernel<")
 T13_OFF = ", false>("
 
 
