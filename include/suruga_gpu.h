@@ -276,8 +276,14 @@ int sg_open_batch_rfc8439(const sg_batch* b, const sg_batch_rfc8439* x);
  * kernel in its TLS 1.3 form -- on seal that needs padding (below), on open a
  * peer that pads so -- under the conditions of the RFC call (not under capture,
  * per-record arrays 4-byte aligned, sg_set_packed); everything else, padded
- * records above 4 KiB included, on the size classes.  sg_last_batch_routes
- * reports where the records of a mixed call went. */
+ * records above 4 KiB included, on the size classes.  Under
+ * sg_set_tls13_buckets(1) (off by default) a record whose inner length is a
+ * multiple of 64 in 4160..2^14, addresses 16-byte aligned, runs on the
+ * wave-per-record buckets J = 2..4 instead, under the conditions of the RFC
+ * call's buckets (sg_set_lockstep, not under capture, per-record arrays 4-byte
+ * aligned); a full record in such a batch (inner length 2^14 + 1) stays on the
+ * size classes.  sg_last_batch_routes reports where the records of a mixed call
+ * went. */
 typedef struct sg_batch_tls13 {
     const uint8_t* ivs;          /* device [num_keys][12], 4-byte aligned, required        */
     uint8_t*       inner_type;   /* open: device, count bytes, required; seal: not read    */
@@ -298,7 +304,8 @@ int sg_batch_tls13_route(const sg_batch* b, int open);
 /* TLS 1.3 seal with record padding (RFC 8446 section 5.4) and a type per record.
  * `b` and `x` are those of sg_seal_batch_tls13.  Record i reads len_i content
  * bytes -- no byte of `in` at or beyond len_i, except that a record on the packed
- * kernel may load the aligned 16-byte unit holding its last content byte whole --
+ * kernel or on a wave-per-record bucket (sg_set_tls13_buckets) may load the
+ * aligned 16-byte unit holding its last content byte whole --
  * and writes exactly inner_i + 16 bytes:
  *   ct(content_i || type_i || zeros) || tag,  inner_i = sg_tls13_inner_len(len_i, pad_to)
  * under the AD 17 03 03 be16(inner_i + 16).  Room in `out` (strides, offsets) for
@@ -801,6 +808,17 @@ int sg_set_lockstep(int enable);
  * environment SG_PACK ("0"/"1"), else 1.  Returns the previous setting; a
  * negative argument only queries. */
 int sg_set_packed(int enable);
+
+/* Route of the padded TLS 1.3 records of 4-16 KiB in mixed batches
+ * (sg_seal_batch_tls13_ex, sg_open_batch_tls13): 1 = a record whose inner length
+ * is a multiple of 64 in 4160..2^14 and whose input and output addresses are
+ * 16-byte aligned runs on the wave-per-record buckets J = 2..4 in their TLS 1.3
+ * form, under the conditions of the RFC call's buckets (sg_set_lockstep on, not
+ * under capture, per-record arrays 4-byte aligned); 0 = on the size classes.
+ * Both are bit-exact.  Initial value: environment SG_TLS13_BUCKETS ("0"/"1"),
+ * else 0 -- unlike the two switches above this one is off unless asked for.
+ * Returns the previous setting; a negative argument only queries. */
+int sg_set_tls13_buckets(int enable);
 
 /* Where the records of a mixed batch went (host-only bookkeeping of the
  * dispatcher: no device work, no wait, no kernel argument).  The counts are

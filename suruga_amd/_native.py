@@ -41,6 +41,7 @@ EXPORTS = [
     "sg_seal_batch_tls13", "sg_open_batch_tls13", "sg_batch_tls13_route", "sg_seal_batch_tls13_ex", "sg_tls13_inner_len",
     "sg_fill_records", "sg_compare_records",
     "sg_last_error", "sg_build_info", "sg_source_hash", "sg_set_timing", "sg_timing_read", "sg_set_lockstep", "sg_set_packed",
+    "sg_set_tls13_buckets",
     "sg_last_batch_routes",
     "sg_wire_bound", "sg_write_records", "sg_read_records", "sg_parse_records", "sg_record_timing",
     "sg_host_register", "sg_host_unregister",
@@ -306,6 +307,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.sg_set_lockstep.argtypes = [C.c_int]
     lib.sg_set_packed.restype = C.c_int
     lib.sg_set_packed.argtypes = [C.c_int]
+    lib.sg_set_tls13_buckets.restype = C.c_int
+    lib.sg_set_tls13_buckets.argtypes = [C.c_int]
     lib.sg_last_batch_routes.restype = C.c_int
     lib.sg_last_batch_routes.argtypes = [C.POINTER(SgBatchRoutes)]
     lib.sg_timing_read.restype = C.c_int

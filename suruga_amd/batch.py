@@ -198,6 +198,13 @@ def tls13_route(batch: Batch, open: bool) -> int:  # noqa: A002  (the C argument
     return N.check(N.load().sg_batch_tls13_route(C.byref(cb), 1 if open else 0))
 
 
+def set_tls13_buckets(enable: int) -> int:
+    """``sg_set_tls13_buckets``: 1 routes the padded TLS 1.3 records of 4-16 KiB inner length of a
+    mixed batch to the wave-per-record buckets, 0 (the default) to the size classes; negative only
+    queries.  Returns the previous setting."""
+    return int(N.load().sg_set_tls13_buckets(enable))
+
+
 def fill_records(buf, stride: int, length: int, count: int, seed: int, j0: int = 0, stream=None) -> None:
     """Synthetic records generated on the device (splitmix64 rule)."""
     N.check(N.load().sg_fill_records(_ptr(buf), stride, length, count, seed & (2**64 - 1), j0,

@@ -300,9 +300,9 @@ int launch_batch(const sg_batch* b, const BatchForm& f, bool open, hipStream_t s
     // wave-per-record buckets and the 64 B-4 KiB ones to the packed kernel (sg_pack.hip), in
     // either construction; not under capture (they are launched on the populations read
     // back), and the per-record arrays are read as dwords by the routed kernels
-    // (TLS 1.3: the packed kernel alone, for inner lengths that are multiples of 64 -- a seal padded
-    // so, a peer's fragments padded so; the J = 2..4 buckets have no TLS 1.3 form)
-    const bool buckets = sg::wpr_enabled() && max_n > 4096u && !t13;
+    // (TLS 1.3: the routes go by the inner length -- a seal padded to a multiple of 64, a peer's
+    // fragments padded so; the packed kernel always, the J = 2..4 buckets under sg_set_tls13_buckets)
+    const bool buckets = sg::wpr_enabled() && max_n > 4096u && (!t13 || sg::tls13_buckets_enabled());
     if (!wpr && !uniform && p.tls && (buckets || (sg::pack_enabled() && max_n >= 64u))) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         SG_HIP(hipStreamIsCapturing(s, &cap));
@@ -625,6 +625,7 @@ int sg_compare_records(const uint8_t* a, uint64_t sa, const uint8_t* b, uint64_t
 
 int sg_set_lockstep(int enable) { return sg::set_wpr(enable); }
 int sg_set_packed(int enable) { return sg::set_pack(enable); }
+int sg_set_tls13_buckets(int enable) { return sg::set_tls13_buckets(enable); }
 
 int sg_last_batch_routes(sg_batch_routes* out) {
     if (!out) return fail(SG_E_ARG, "sg_batch_routes is NULL%s");

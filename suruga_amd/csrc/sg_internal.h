@@ -51,8 +51,9 @@ constexpr uint32_t kWHi = 120;
 constexpr uint32_t kWprRecWords = 160;
 // Record descriptor of a listed wave-per-record record (mixed batches), u32
 // words, indexed like the keying records by the record's slot in its bucket:
-//   in_off[2] out_off[2] n rec key_index n14 n15 n13 0 0
-// (n13: the nonce's first word, Construction::kRfc8439; 0 in the draft)
+//   in_off[2] out_off[2] n rec key_index n14 n15 n13 clen type
+// (n13: the nonce's first word, Construction::kRfc8439; 0 in the draft.  clen, type: the
+// content length and the inner type of a TLS 1.3 bucket seal, n its inner length; else 0)
 constexpr uint32_t kWprDescWords = 12;
 
 // Kernel parameters (passed by value as kernarg).
@@ -110,8 +111,8 @@ static_assert(sizeof(KParams) == 184, "KParams: the kernarg layout of every reco
 // The launchers' one selector: calls f(OPEN, C, T13) with the run-time triple
 // (open, p.rfc, p.tls13) as compile-time constants (OPEN.value and T13.value
 // bools, T13 only with C.value == Construction::kRfc8439), so a launcher names
-// its kernel once, as K<OPEN.value, ..., C.value, T13.value>; one without a TLS 1.3
-// form (the J = 2..4 buckets) refuses p.tls13 and ignores T13.  The message launchers: (rfc, open), f(OPEN, C).
+// its kernel once, as K<OPEN.value, ..., C.value, T13.value> (the J = 2..4 bucket record
+// kernel: T13 on seal only; its open is the RFC 8439 form).  The message launchers: (rfc, open), f(OPEN, C).
 template <class F>
 inline void with_form(bool rfc, bool open, F&& f) {
     constexpr std::integral_constant<Construction, Construction::kDraft> D{};
@@ -139,7 +140,8 @@ constexpr uint32_t kWprBuckets = 3;
 constexpr uint32_t kWprMinJ = 2;
 // ... and TLS records of 64 B <= n <= 4 KiB, n a multiple of 64, 16-byte
 // aligned, to the packed kernel (sg_pack.hip): list kPackList.  The TLS 1.3
-// form takes this route alone (n: the inner length); it has no buckets.
+// form takes this route (n: the inner length) and, under sg_set_tls13_buckets,
+// the buckets for padded records of 4 KiB < n <= 16 KiB (off by default).
 constexpr uint32_t kPackList = kNumClasses + kWprBuckets;
 constexpr uint32_t kNumLists = kPackList + 1u;
 constexpr uint32_t kListGridPerCU = 8;   // workgroups per CU for list-driven launches
@@ -228,6 +230,10 @@ inline hipError_t mark(hipEvent_t ev, hipStream_t s) { return ev ? hipEventRecor
 
 bool wpr_enabled();  // sg_set_lockstep / SG_LOCKSTEP environment switch
 int set_wpr(int enable);
+// sg_set_tls13_buckets / SG_TLS13_BUCKETS (off by default): padded TLS 1.3 records of
+// 4-16 KiB inner length take the J = 2..4 buckets.  A host decision only (launch_batch).
+bool tls13_buckets_enabled();
+int set_tls13_buckets(int enable);
 // keying pre-pass + record kernel; ev_mid (may be NULL) is recorded between them
 hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_mid);
 // wave-per-record buckets of a mixed batch (wl[b]: J = kWprMinJ + b chunks):

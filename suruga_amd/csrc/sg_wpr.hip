@@ -71,6 +71,18 @@
 // above (delta = 1: one block more follows them) and moves only the tag, to the
 // odd address n + 1; the keying kernel takes the tail byte, keystream block 257
 // and the tail block's term of ctot (tests/test_wpr_mac_model_tls13.py).
+//
+// TLS 1.3 buckets (LIST with T13 / TLS13; sg_set_tls13_buckets, off by default): a
+// padded record whose inner plaintext content || type || zeros is n = 64 k' bytes,
+// 4 KiB < n <= 16 KiB.  Its MAC stream AD(5) || 0^11 || ct || le64(5) || le64(n) is
+// the RFC bucket record's all-full-block stream behind a 5-byte AD, and
+// wpr_geom<kRfc8439>(5, n) is the 13-byte AD's, so the keying differs in the prefix
+// block 17 03 03 be16(n + 16) and the length block alone
+// (tests/test_wpr_bucket_model_tls13.py); the descriptor's words 10 and 11 carry the
+// content length and the inner type.  Open runs the RFC bucket kernel as it is on
+// those tables; seal is the record kernel's TLS13 bucket form, which loads the
+// units that hold content and patches each chunk that reaches the content's end in
+// LDS (see the kernel).
 #include "sg_internal.h"
 #include "sg_device.h"
 #include "sg_chacha_grp.inc"  // grouped ChaCha20 double round (tools/gen_chacha_grp.py --product)
@@ -200,12 +212,17 @@ struct WprKeyJobs {
 // block 257 beside block 0, the tail byte (seal: type ^ ks into out[2^14]; open:
 // in[2^14] ^ ks into out[2^14]) and its block (byte + 2^128) r^2 in ctot
 // (tests/test_wpr_mac_model_tls13.py).
+// T13 with LIST (bucket records, n the inner length, a multiple of 64): no tail; the
+// RFC bucket keying with adlen = 5, the header 17 03 03 be16(n + 16) as the prefix
+// block and le64(5) || le64(n) as the length block; seal: n = tls13_inner_len(len,
+// pad_to), and the descriptor carries the content length and the inner type.
 // (compiled for two waves per SIMD: four and more spill to scratch)
 template <bool OPEN, bool LIST, Construction C, bool T13>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg_wpr_keying_kernel(
     const KParams p, const WprKeyJobs jobs) {
     constexpr bool RFC = C == Construction::kRfc8439;
-    static_assert(!T13 || (RFC && !LIST), "TLS 1.3: uniform RFC 8439 launches");
+    static_assert(!T13 || RFC, "TLS 1.3 records are RFC 8439");
+    constexpr bool TAIL13 = T13 && !LIST;  // the uniform launch: this kernel takes the tail byte and its block
     const uint32_t lane = threadIdx.x;
     WprList wl = jobs.b[0];
     uint32_t b0 = 0;
@@ -227,9 +244,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
     const bool act = slot < wl.count;
     const uint32_t rec = LIST ? (act ? wl.list[slot] : 0u) : slot;
     uint32_t n = kWprN;
-    if constexpr (LIST) n = act ? p.len[rec] - (OPEN ? 16u : 0u) : kWprN;
+    // (T13 buckets: the inner length, content || type || zeros on seal, as classified)
+    if constexpr (LIST && T13 && !OPEN) n = act ? tls13_inner_len(p.len[rec], p.pad_to) : kWprN;
+    else if constexpr (LIST) n = act ? p.len[rec] - (OPEN ? 16u : 0u) : kWprN;
     WprGeom G = wpr_geom<C>(adlen, n);
-    if constexpr (T13) {  // the tail block behind the 1024 of the record kernel
+    if constexpr (TAIL13) {  // the tail block behind the 1024 of the record kernel
         G.B += 1u;
         G.delta = 1u;
     }
@@ -245,7 +264,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
         const PolyKey pk = poly_key(ks);
         r = words_to_f26(pk.r0, pk.r1, pk.r2, pk.r3, 0u);
         s[0] = pk.s[0]; s[1] = pk.s[1]; s[2] = pk.s[2]; s[3] = pk.s[3];
-        if constexpr (T13) {
+        if constexpr (TAIL13) {
             chacha_block(ks, rk.k, kWprTailBlock, rk.n13, rk.n14, rk.n15);  // byte 2^14 is its first
             uint8_t* ob = p.out + p.out_stride * rec + kWprN;
             if constexpr (OPEN) {
@@ -263,7 +282,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
             uint32_t* d = wl.desc + (uint64_t)slot * kWprDescWords;
             st16(d, u32x4{(uint32_t)io, (uint32_t)(io >> 32), (uint32_t)oo, (uint32_t)(oo >> 32)});
             st16(d + 4, u32x4{n, rec, ki, rk.n14});
-            st16(d + 8, u32x4{rk.n15, RFC ? rk.n13 : 0u, 0u, 0u});
+            // (T13 seal: the content length and the inner type, for the record kernel's loads and patch)
+            uint32_t clen = 0u, type = 0u;
+            if constexpr (T13 && !OPEN) {
+                clen = p.len[rec];
+                type = tls13_inner_type(p, rec);
+            }
+            st16(d + 8, u32x4{rk.n15, RFC ? rk.n13 : 0u, clen, type});
         }
     }
 
@@ -379,8 +404,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
             for (uint32_t i = 0; i < 16u; ++i) {
                 const uint32_t pos = 16u * b + i;
                 // (RFC 8439: ad and its zero padding; block beta is empty, sigma = 0)
-                if constexpr (T13) {  // the record header; L = n + 1 + 16
-                    if (pos < adlen) w[i >> 2] |= (uint32_t)tls13_ad_byte(kWprN + 17u, pos) << (8u * (i & 3u));
+                if constexpr (T13) {  // the record header; L = n + 1 + 16 (buckets: n the inner length, L = n + 16)
+                    if (pos < adlen) w[i >> 2] |= (uint32_t)tls13_ad_byte(LIST ? n + 16u : kWprN + 17u, pos) << (8u * (i & 3u));
                 } else if (pos < G.o)
                     w[i >> 2] |= (uint32_t)prefix_byte<C>(p, rec, rk.seq, n, adlen, pos) << (8u * (i & 3u));
             }
@@ -391,7 +416,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
     // suffix le64(n) at stream offset o + n = 16 (beta + m) + sigma: n 2^(8 sigma) split at 2^128
     // (RFC 8439: the single full block le64(adlen) || le64(n), the stream's last, at weight r)
     F26 suffix;
-    if constexpr (T13) {  // the tail block at r^2 (its 2^128 is in pads), then the length block
+    if constexpr (TAIL13) {  // the tail block at r^2 (its 2^128 is in pads), then the length block
         suffix = fmul_add(F26{tail, 0u, 0u, 0u, 0u}, r2, fmul(words_to_f26(adlen, 0u, n + 1u, 0u, 0u), r));
     } else if constexpr (RFC) {
         suffix = fmul(words_to_f26(adlen, 0u, n, 0u, 0u), r);
@@ -548,16 +573,30 @@ struct RecDesc {
     uint32_t rec;       // record index (status, key index, sequence number)
     uint32_t ki, n14, n15;
     uint32_t n13;       // RFC 8439 only (the draft's word 13 is 0)
+    uint32_t clen, type;  // TLS 1.3 bucket seal only: the content length and the inner type
 };
 
-// TLS13 (TLS 1.3 uniform launch, see the keying kernel): the record's 2^14 bytes as
+// TLS13, uniform launch (TLS 1.3, see the keying kernel): the record's 2^14 bytes as
 // ever; only the tag moves behind the tail byte, to the odd address n + 1.
+// TLS13, bucket launch (LIST; seal only): a padded TLS 1.3 record of n inner bytes,
+// content || type || zeros, built here from the record's clen content bytes.  With
+// e = vs + clen the frame offset of the content's end, a lane loads a 16-byte unit
+// only if it starts below e (the unit with the last content byte whole: at most 15
+// bytes behind the content in an aligned unit, hence on the content's page; none at
+// all with clen = 0), and every chunk that reaches e is patched in LDS once it has
+// landed: the unit that holds e keeps its content bytes and takes the type, the
+// units behind it are zeroed, so that stale LDS bytes never reach the XOR.  The
+// patch sits under a wave-uniform branch at the chunk's wait, outside the round
+// loop; the tag stays at the aligned address n.  The open of such a record needs no
+// form of its own: sigma = 0 never reads the AD length, the tag lies at in + n.
 template <bool OPEN, bool TLS, uint32_t J, bool LIST, Construction C, bool TLS13>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void sg_wpr_kernel(const KParams p,
                                                                                                const WprList wl) {
     static_assert(J >= 1u && J <= 4u && (LIST || J == 4u), "uniform launches are full 16 KiB records");
     constexpr bool RFC = C == Construction::kRfc8439;
-    static_assert(!TLS13 || (RFC && TLS && !LIST), "TLS 1.3: uniform RFC 8439 launches");
+    static_assert(!TLS13 || (RFC && TLS && (!LIST || !OPEN)), "TLS 1.3: uniform RFC 8439 launches and the bucket seal");
+    constexpr bool TAIL13 = TLS13 && !LIST;  // the tag behind the tail byte
+    constexpr bool PAD13 = TLS13 && LIST;    // content || type || zeros built in LDS
     constexpr uint32_t j0 = 4u - J;  // the first chunk of the right-aligned record in the 16 KiB frame
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const uint32_t wave = uniform(threadIdx.x >> 6), lane = threadIdx.x & 63u;
@@ -605,7 +644,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     // bucket launches from the descriptor the keying kernel wrote.
     auto desc_of_slot = [&](uint32_t slot) {
         RecDesc d;
-        d.n13 = 0u;
+        d.n13 = d.clen = d.type = 0u;
         if constexpr (LIST) {
             const uint32_t* dw = wl.desc + (uint64_t)slot * kWprDescWords;
             d.io = (uint64_t)cload(dw, 0) | ((uint64_t)cload(dw, 1) << 32);
@@ -616,6 +655,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             d.n14 = cload(dw, 7);
             d.n15 = cload(dw, 8);
             if constexpr (RFC) d.n13 = cload(dw, 9);
+            if constexpr (PAD13) {
+                d.clen = cload(dw, 10);
+                d.type = cload(dw, 11);
+            }
         } else {
             d.rec = slot;
             d.io = p.in_stride * slot;
@@ -649,7 +692,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     auto desc_from_lds = [&]() {
         const uint32_t* dl = reinterpret_cast<const uint32_t*>(lines + kWprDescOff);
         RecDesc d;
-        d.n13 = 0u;
+        d.n13 = d.clen = d.type = 0u;
         d.io = (uint64_t)uniform(dl[0]) | ((uint64_t)uniform(dl[1]) << 32);
         d.oo = (uint64_t)uniform(dl[2]) | ((uint64_t)uniform(dl[3]) << 32);
         d.n = uniform(dl[4]);
@@ -658,6 +701,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         d.n14 = uniform(dl[7]);
         d.n15 = uniform(dl[8]);
         if constexpr (RFC) d.n13 = uniform(dl[9]);
+        if constexpr (PAD13) {
+            d.clen = uniform(dl[10]);
+            d.type = uniform(dl[11]);
+        }
         return d;
     };
 
@@ -672,9 +719,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     // table (640 B) is fetched into the line area the same way.  The only
     // vector-memory operations of the kernel are these DMAs, the descriptor
     // DMA and the output stores, so the waits below count exactly.
-    auto dma_piece_of = [&](uint32_t ldsb, const uint8_t* chunk_base, uint32_t k, uint32_t lo) {
+    // (PAD13: hi = the chunk's content bytes, counted from the chunk's start; units at or behind hi are not read)
+    auto dma_piece_of = [&](uint32_t ldsb, const uint8_t* chunk_base, uint32_t k, uint32_t lo, uint32_t hi = 0u) {
         // chunk_base: the record's frame chunk start in real addresses (may lie before the record)
-        if (!LIST || 1024u * k + 16u * wunit >= lo) dma_sv(uniform(ldsb + 1024u * k), chunk_base + 1024u * k, 16u * wunit);
+        if constexpr (PAD13) {
+            const uint32_t off = 1024u * k + 16u * wunit;
+            if (off >= lo && off < hi) dma_sv(uniform(ldsb + 1024u * k), chunk_base + 1024u * k, 16u * wunit);
+        } else if (!LIST || 1024u * k + 16u * wunit >= lo) dma_sv(uniform(ldsb + 1024u * k), chunk_base + 1024u * k, 16u * wunit);
     };
     auto dma_table_of = [&](uint32_t slot) {  // into the line area, lane u: unit u
         if (lane < kWprRecWords / 4u) {
@@ -706,7 +757,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         const uint32_t vs = kWprN - cd.n, lo = kWprChunk * J - cd.n;
         const uint8_t* cb0 = p.in + cd.io + kWprChunk * j0 - vs;
 #pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k) dma_piece_of(lds_wave, cb0, k, lo);
+        for (uint32_t k = 0; k < 4u; ++k) dma_piece_of(lds_wave, cb0, k, lo, lo + cd.clen);
         dma_table_of(slot);
     }
     bool first = true;
@@ -778,7 +829,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         // hold up the table reads below until it returned)
         // (TLS13: the tag lies at in + n + 1; the two aligned 16-byte units that hold it
         // land in the idle descriptor slot's end and the tag slot, still one DMA)
-        if constexpr (TLS13) {
+        if constexpr (TAIL13) {
             if (OPEN && lane < 2u) dma_one(lds_rxs - 16u, inb + n + 16u * lane);
         } else if (OPEN && lane == 0u) dma_one(lds_rxs, inb + n);
         SG_TICK(t_tw);
@@ -980,6 +1031,30 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             uint8_t* cb = buf + kWprChunk * bj;
             uint8_t* pb = buf + kWprChunk * (bj ^ 1u);
             const uint32_t plo = pend_lo;
+            uint32_t chi = 0u;  // PAD13: the content bytes of chunk j + 1, from its start
+            if constexpr (PAD13) {
+                const uint32_t e = vs + cd.clen;  // frame offset of the content's end, below 2^14
+                chi = e > kWprChunk * (j + 1u) ? e - kWprChunk * (j + 1u) : 0u;
+                if (e < kWprChunk * (j + 1u)) {  // (wave-uniform) the chunk reaches the content's end
+                    // el: the content bytes of the lane's 64-byte block (<= 0: none).  A lane of chunk j0
+                    // in front of the record has el >= 64 (e >= vs) and sits this out.
+                    const int32_t el = (int32_t)e - (int32_t)(kWprChunk * j + 64u * lane);
+                    if (el < 64) {
+#pragma unroll
+                        for (uint32_t i = 0; i < 4u; ++i) {
+                            uint8_t* up = cb + 16u * (4u * lane + (i ^ xq));
+                            u32x4 v = ld16(up);  // (a unit that was not loaded: stale bytes, all masked)
+#pragma unroll
+                            for (uint32_t w = 0; w < 4u; ++w) {
+                                const int32_t kk = el - (int32_t)(16u * i + 4u * w);  // content bytes of the word
+                                const uint32_t keep = kk >= 4 ? 0xffffffffu : kk <= 0 ? 0u : (1u << (8 * kk)) - 1u;
+                                v[w] = (v[w] & keep) | (kk >= 0 && kk < 4 ? cd.type << (8 * kk) : 0u);
+                            }
+                            st16(up, v);
+                        }
+                    }
+                }
+            }
 
             // keystream block 64 j + lane + 1 of the frame = block 64 j + lane + 1 - vs / 64 of the
             // record (chacha20_poly1305.rs:52), lock-step rounds
@@ -1029,10 +1104,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             auto dma_piece = [&](uint32_t k) {
                 const uint32_t ldsb = lds_wave + kWprChunk * (bj ^ 1u);
                 if (j < 3u) {
-                    if (active) dma_piece_of(ldsb, inb + kWprChunk * (j + 1u) - vs, k, 0u);
+                    if (active) dma_piece_of(ldsb, inb + kWprChunk * (j + 1u) - vs, k, 0u, chi);
                 } else if (next) {
                     const uint32_t nvs = kWprN - (LIST ? nd.n : kWprN);
-                    dma_piece_of(ldsb, p.in + nd.io + kWprChunk * j0 - nvs, k, LIST ? kWprChunk * J - nd.n : 0u);
+                    const uint32_t nlo = LIST ? kWprChunk * J - nd.n : 0u;
+                    dma_piece_of(ldsb, p.in + nd.io + kWprChunk * j0 - nvs, k, nlo, nlo + nd.clen);
                 }
             };
             u32x4 oa = {}, ob = {};
@@ -1188,7 +1264,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                         lane63(f.v3) + ctot.v3, lane63(f.v4) + ctot.v4};
         uint32_t tw[4];
         tag_words(fs, sk, tw);
-        if constexpr (TLS13) {
+        if constexpr (TAIL13) {
             if constexpr (!OPEN) {  // one byte per lane: exactly [n + 1, n + 17) is written
                 const uint32_t wi = lane >> 2;
                 const uint32_t w = wi == 0u ? tw[0] : wi == 1u ? tw[1] : wi == 2u ? tw[2] : tw[3];
@@ -1306,7 +1382,7 @@ hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_
 }
 
 hipError_t launch_wpr_keying_lists(const KParams& p, bool open, const WprList* wl, hipStream_t s) {
-    if (!p.tls || p.tls13) return hipErrorInvalidValue;  // buckets are TLS 1.2 records (of either construction)
+    if (!p.tls) return hipErrorInvalidValue;  // buckets are TLS records: 1.2 of either construction, padded 1.3
     WprKeyJobs jobs = {};
     uint32_t grid = 0;
     for (uint32_t b = 0; b < kWprBuckets; ++b) {
@@ -1317,27 +1393,30 @@ hipError_t launch_wpr_keying_lists(const KParams& p, bool open, const WprList* w
         ++jobs.njobs;
     }
     if (grid == 0) return hipSuccess;
-    with_form(p, open, [&](auto OPEN, auto C, auto) {
+    with_form(p, open, [&](auto OPEN, auto C, auto T13) {
         const dim3 g(grid), b(kWprKeyThreads);
-        hipLaunchKernelGGL((sg_wpr_keying_kernel<OPEN.value, true, C.value, false>), g, b, 0, s, p, jobs);
+        hipLaunchKernelGGL((sg_wpr_keying_kernel<OPEN.value, true, C.value, T13.value>), g, b, 0, s, p, jobs);
     });
     return hipGetLastError();
 }
 
 hipError_t launch_wpr_list(const KParams& p, bool open, uint32_t J, const WprList& wl, hipStream_t s) {
     if (wl.count == 0) return hipSuccess;
-    if (!p.tls || p.tls13 || J < kWprMinJ || J > 4u) return hipErrorInvalidValue;  // TLS 1.2 records of 2..4 chunks
+    if (!p.tls || J < kWprMinJ || J > 4u) return hipErrorInvalidValue;  // TLS records of 2..4 chunks
     hipError_t e;
     int cus = 0;
     if ((e = device_cus(&cus)) != hipSuccess) return e;
     const uint32_t grid = wpr_grid(cus, wl.count);
-    with_form(p, open, [&](auto OPEN, auto C, auto) {
+    with_form(p, open, [&](auto OPEN, auto C, auto T13) {
         const dim3 g(grid), b(512);
         constexpr bool O = OPEN.value;
+        // TLS 1.3: the seal builds content || type || zeros (the record kernel's bucket form); the
+        // open is the RFC 8439 kernel on the tables of the TLS 1.3 keying
+        constexpr bool P = T13.value && !O;
         switch (J) {
-            case 2: hipLaunchKernelGGL((sg_wpr_kernel<O, true, 2, true, C.value, false>), g, b, kWprWgLds, s, p, wl); break;
-            case 3: hipLaunchKernelGGL((sg_wpr_kernel<O, true, 3, true, C.value, false>), g, b, kWprWgLds, s, p, wl); break;
-            default: hipLaunchKernelGGL((sg_wpr_kernel<O, true, 4, true, C.value, false>), g, b, kWprWgLds, s, p, wl); break;
+            case 2: hipLaunchKernelGGL((sg_wpr_kernel<O, true, 2, true, C.value, P>), g, b, kWprWgLds, s, p, wl); break;
+            case 3: hipLaunchKernelGGL((sg_wpr_kernel<O, true, 3, true, C.value, P>), g, b, kWprWgLds, s, p, wl); break;
+            default: hipLaunchKernelGGL((sg_wpr_kernel<O, true, 4, true, C.value, P>), g, b, kWprWgLds, s, p, wl); break;
         }
     });
     return hipGetLastError();
@@ -1346,6 +1425,9 @@ hipError_t launch_wpr_list(const KParams& p, bool open, uint32_t J, const WprLis
 static EnvSwitch g_wpr{"SG_LOCKSTEP"};
 bool wpr_enabled() { return g_wpr.on(); }
 int set_wpr(int enable) { return g_wpr.set(enable); }
+static EnvSwitch g_tls13_buckets{"SG_TLS13_BUCKETS", -1, false};  // off unless set
+bool tls13_buckets_enabled() { return g_tls13_buckets.on(); }
+int set_tls13_buckets(int enable) { return g_tls13_buckets.set(enable); }
 
 const char* wpr_kernel_config() {
     return "sg_wpr_kernel v17: full 16 KiB records, one wave per record (8 per 512-thread workgroup, persistent "
@@ -1357,7 +1439,9 @@ const char* wpr_kernel_config() {
            "lines of r^(128k+d) in LDS, read as aligned dwords + v_alignbyte), exact per-lane assembly, "
            "W = r^(4(31-q)) scaling, DPP sum; keying pre-pass with the constant term; bucket records: the idle lanes "
            "of the first chunk sit out its rounds (EXEC); every form also as Construction::kRfc8439 (RFC 8439 / RFC "
-           "7905: word-13 nonce, block-aligned MAC stream; uniform 16 KiB launch and the J = 2..4 buckets)";
+           "7905: word-13 nonce, block-aligned MAC stream; uniform 16 KiB launch and the J = 2..4 buckets); TLS 1.3: "
+           "the uniform launch, and under sg_set_tls13_buckets the J = 2..4 buckets for padded records (5-byte AD "
+           "keying; seal loads the content's units and patches type and zeros into the LDS chunk)";
 }
 
 }  // namespace sg

@@ -2,12 +2,13 @@
 """Rate of the padded TLS 1.3 seal (sg_seal_batch_tls13_ex, pad_to = 64) and of the open of
 its fragments on a mixed batch, routed to the packed kernel and on the size classes alone,
 beside the RFC 7905 batch over the same lengths.  Prints one JSON line and writes it to
-``--out`` (profiles/tls13_pad_bench.json is the committed run).
+``--out`` (profiles/tls13_bucket_bench.json is the committed four-leg run;
+profiles/tls13_pad_bench.json the three-leg run of before the bucket route).
 
 One batch: ``--records`` (default 2^18) device-resident records, 256 connection keys.  The
 inner lengths are tools/rfc_batch_bench.py's Zipf leg (suruga_amd.workloads.zipf_lengths:
 64 B-16 KiB, multiples of 64); record i has inner_i - 1 - (i * 37 mod 64) content bytes, so
-that pad_to = 64 pads it to inner_i and the content ends anywhere in the last block.  Three
+that pad_to = 64 pads it to inner_i and the content ends anywhere in the last block.  Four
 legs:
 
 * ``rfc7905``: sg_*_batch_rfc8439 in TLS mode over records of inner_i bytes, as routed
@@ -15,10 +16,12 @@ legs:
   before this one;
 * ``tls13``: sg_seal_batch_tls13_ex with pad_to = 64 and sg_open_batch_tls13 of its
   fragments, as routed: inner lengths up to 4 KiB on the packed kernel in its TLS 1.3 form,
-  the longer ones on the size classes (the buckets have no TLS 1.3 form);
-* ``tls13_classes``: the same calls under ``sg_set_packed(0)``: the size classes alone.
+  the longer ones on the size classes (sg_set_tls13_buckets is off by default);
+* ``tls13_classes``: the same calls under ``sg_set_packed(0)``: the size classes alone;
+* ``tls13_buckets``: the calls of ``tls13`` under ``sg_set_tls13_buckets(1)``: inner lengths
+  above 4 KiB on the J = 2..4 wave-per-record buckets in their TLS 1.3 form.
 
-The legs alternate launch by launch in one process (the three seals and the three opens
+The legs alternate launch by launch in one process (the four seals and the four opens
 once per round), every round in another order (a seeded shuffle, tools/ab_legs.py).  Each
 leg reports the median of ``--reps`` launches after ``--warmup`` from HIP events, GiB/s of
 inner plaintext, and ``spread`` = (max - min) / median; ``routes`` holds every leg's
@@ -26,7 +29,11 @@ inner plaintext, and ``spread`` = (max - min) / median; ``routes`` holds every l
 ratios; ``packed_kept_*`` says, for seal and for open separately, whether the routed leg
 beats the class-only leg by more than the larger of the two legs' spreads -- DESIGN.md
 section 4.12's rule for keeping the packed route the default of the TLS 1.3 form.  The
-second ratio is reported, not gated.  The two TLS 1.3 images must be equal, every open must
+second ratio is reported, not gated.  ``buckets_vs_tls13_*`` (the baseline: the default route
+of the same call in the same process) and ``buckets_vs_rfc7905_*`` are the bucket leg's time
+ratios, and ``buckets_recommended_*`` applies the same rule to the first: the switch is
+recommended in a direction only if the bucket leg beats the default leg by more than the
+larger of the two legs' spreads.  The three TLS 1.3 images must be equal, every open must
 return type and content length, and a sample of fragments is compared with
 tests/tls13_ref.py, every byte and the tag.
 
@@ -50,7 +57,7 @@ SEED = 0x746C7364
 SAMPLE = 24
 CTYPE = 23
 PAD_TO = 64
-NAMES = ("rfc7905", "tls13", "tls13_classes")
+NAMES = ("rfc7905", "tls13", "tls13_classes", "tls13_buckets")
 
 
 def make(count: int):
@@ -118,16 +125,17 @@ def run(w: dict, reps: int, warmup: int) -> dict:
     from suruga_amd import batch as B
 
     from gpu_support import kernel_forms  # sets the switch and puts it back after the launch
+    from tls13_bucket_support import tls13_buckets  # likewise, sg_set_tls13_buckets
 
     lib = _native.load()
-    forms = {"tls13_classes": dict(packed=0)}
+    forms = {"tls13_classes": lambda: kernel_forms(lib, packed=0), "tls13_buckets": lambda: tls13_buckets(lib, 1)}
     routes = {}
 
     def leg(name, d):
         t13 = name != "rfc7905"
 
         def fn():
-            with kernel_forms(lib, **forms.get(name, {})):
+            with forms.get(name, lambda: kernel_forms(lib))():
                 if not t13:
                     (B.open_ if d else B.seal)(w["legs"][name][d])
                 elif d:
@@ -145,6 +153,8 @@ def run(w: dict, reps: int, warmup: int) -> dict:
             assert bool((ty == CTYPE).all()) and torch.equal(cl, w["d_lens"]), f"{name}: inner type / content length"
     assert torch.equal(w["cts"]["tls13"], w["cts"]["tls13_classes"]), "the routed and the class-only images differ"
     assert torch.equal(w["backs"]["tls13"], w["backs"]["tls13_classes"]), "the routed and the class-only opens differ"
+    assert torch.equal(w["cts"]["tls13_buckets"], w["cts"]["tls13"]), "the bucket leg's and the default route's images differ"
+    assert torch.equal(w["backs"]["tls13_buckets"], w["backs"]["tls13"]), "the bucket leg's and the default route's opens differ"
     out = {"batch": w["desc"], "payload_bytes": w["payload"], "content_bytes": w["content"], "pad_to": PAD_TO}
     for name, ms in times.items():
         out[name] = ab_legs.summary(ms, w["payload"])
@@ -153,6 +163,10 @@ def run(w: dict, reps: int, warmup: int) -> dict:
         out[f"tls13_vs_rfc7905_{d}"] = round(out[f"tls13_{d}"]["ms"] / out[f"rfc7905_{d}"]["ms"], 4)
         spread = max(out[f"tls13_{d}"]["spread"], out[f"tls13_classes_{d}"]["spread"])
         out[f"packed_kept_{d}"] = out[f"packed_vs_classes_{d}"] < 1.0 - spread
+        out[f"buckets_vs_tls13_{d}"] = round(out[f"tls13_buckets_{d}"]["ms"] / out[f"tls13_{d}"]["ms"], 4)
+        out[f"buckets_vs_rfc7905_{d}"] = round(out[f"tls13_buckets_{d}"]["ms"] / out[f"rfc7905_{d}"]["ms"], 4)
+        spread = max(out[f"tls13_buckets_{d}"]["spread"], out[f"tls13_{d}"]["spread"])
+        out[f"buckets_recommended_{d}"] = out[f"buckets_vs_tls13_{d}"] < 1.0 - spread
     out["routes"] = routes
     return out
 
@@ -174,7 +188,7 @@ def main() -> None:
     ap.add_argument("--records", type=int, default=1 << 18)
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "tls13_pad_bench.json", help="where the JSON is written")
+    ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "tls13_bucket_bench.json", help="where the JSON is written")
     args = ap.parse_args()
 
     res, bus = ab_legs.prelude("tls13_pad_bench", args.reps, args.warmup)
