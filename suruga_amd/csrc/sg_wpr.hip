@@ -160,7 +160,7 @@ __device__ __forceinline__ uint32_t bytes_from(uint32_t w, uint32_t lo) {
 }
 
 // p - (2^24 * sum_{c<32} 2^(8c) mod p) in radix 2^26: the seed of the 32 x 32
-// accumulator, negated (tests/test_wpr_mac_model.py: CJ)
+// accumulator, negated (tests/wpr_model.py keying: cj)
 constexpr uint32_t kCJ0 = 0x1bd2d2bu, kCJ1 = 0x36f6f6fu, kCJ2 = 0x3dbdbdbu, kCJ3 = 0x2f6f6f6u, kCJ4 = 0x1bdbdbdu;
 
 // ---------------------------------------------------------------------------

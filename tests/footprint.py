@@ -17,7 +17,8 @@ The route predicates restate, in Python, which kernel a record of a batch goes
 to (wpr_eligible / launch_batch in sg_capi.cpp, wpr_bucket_of / pack_ok /
 size_class in sg_internal.h, the comments of sg_set_lockstep / sg_set_packed in
 include/suruga_gpu.h).  Every GPU case asserts with them that its records are
-eligible for the route it means to exercise.
+eligible for the route it means to exercise.  They are stated here once: the TLS
+1.3 tests apply them to inner lengths (tls13_pad_support.routes_of).
 """
 from __future__ import annotations
 

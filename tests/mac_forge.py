@@ -30,6 +30,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+import wpr_model
+
 P = (1 << 130) - 5
 CLAMP = 0x0FFFFFFC0FFFFFFC0FFFFFFC0FFFFFFF
 M128 = (1 << 128) - 1
@@ -304,29 +306,13 @@ def wpr_sign_ct(ad: bytes, r: int, row: int, negate: bool) -> bytes:
     """16 KiB of ciphertext whose every byte is 0xff where the signed digit it
     multiplies in accumulator row `row` is >= 0 and 0x00 where it is negative
     (negate: the other way round): |D[row][q]| as large as ciphertext can make
-    it.  The T operand is built as tests/test_wpr_mac_model.py wpr_tag builds it."""
-    from test_wpr_mac_model import P as PM
-    from test_wpr_mac_model import keying, signed_digits
-
-    kt = keying(ad, r)
-    sig = kt["sig"]
-    lines = np.zeros(40 * 48 + 16, dtype=np.int64)
-    for line in range(40):
-        k, u = divmod(line, 5)
-        d = signed_digits(kt["rd"][u] * kt["tk"][k] % PM)
-        for i in range(17):
-            lines[48 * line + 47 - sig - i] = d[i]
+    it.  The T operand is the one tests/wpr_model.py's wpr_tag multiplies by."""
+    kt = wpr_model.keying(wpr_model.DRAFT, ad, r)
+    lines = wpr_model.digit_lines(kt)
     ct = np.zeros((1024, 16), dtype=np.uint8)
-    for j in range(4):
-        for i in range(4):
-            for h in range(2):
-                k = (1 - h) + 2 * (3 - j)
-                iv = 5 * k + 4 - i
-                vw = lines[48 * iv + 47 - row:48 * iv + 47 - row + 16]
-                pw = lines[48 * iv - 17 - row:48 * iv - 17 - row + 16]
-                t = np.concatenate([vw[:16 - sig], pw[16 - sig:]])
-                m = 256 * j + 128 * h + 4 * np.arange(32) + i
-                ct[m] = np.where((t >= 0) != negate, 0xFF, 0x00).astype(np.uint8)
+    for j, i, h in wpr_model.STEPS:
+        t, m = wpr_model.t_operand(lines, kt["sig"], j, i, h, rows=(row,))
+        ct[m] = np.where((t[0] >= 0) != negate, 0xFF, 0x00).astype(np.uint8)
     return ct.tobytes()
 
 

@@ -54,6 +54,50 @@ def tiles_of(adlen: int, n: int) -> int:
     return max(1, -(-(adlen + 16 + n) // TB))
 
 
+def rnd(tag: str, n: int) -> bytes:
+    """n bytes from SHA-256 of the tag: the streams and Poly1305 keys of the CPU models."""
+    out = b""
+    i = 0
+    while len(out) < n:
+        out += hashlib.sha256(f"{tag}:{i}".encode()).digest()
+        i += 1
+    return out[:n]
+
+
+# ---------------------------------------------------------------------------
+# the C batch on the host (the argument checks never dereference a device pointer)
+# ---------------------------------------------------------------------------
+def batch(count=2, n=100, adlen=13):
+    """A well-formed seal batch on made-up device addresses, its items and a fitting workspace size."""
+    from suruga_amd import _native as N
+
+    items = (N.SgMsgItem * max(count, 1))()
+    for i in range(count):
+        it = items[i]
+        it.key_index = i % 2
+        it.ad, it.ad_len = 0x100000 + 0x1000 * i, adlen
+        it.in_, it.in_len = 0x200000 + 0x10000 * i, n
+        it.out = 0x400000 + 0x10000 * i
+    b = N.SgMsgBatch()
+    b.count, b.flags, b.keys, b.num_keys, b.items = count, 0, 0x1000, 2, items
+    b.status = 0x2000
+    b.stream = None
+    b.workspace, b.workspace_size = 0x800000, N.load().sg_msg_batch_workspace_size(count)
+    return b, items
+
+
+def rejected(lib, b, open_=False, text=None):
+    """The call answers SG_E_ARG, with `text` in sg_last_error where one is given."""
+    import ctypes as C
+
+    from suruga_amd._native import SG_E_ARG
+
+    rc = (lib.sg_open_msg_batch if open_ else lib.sg_seal_msg_batch)(C.byref(b))
+    assert rc == SG_E_ARG, rc
+    if text:
+        assert text.encode() in lib.sg_last_error(), lib.sg_last_error()
+
+
 # ---------------------------------------------------------------------------
 # the decomposition in Python integers
 # ---------------------------------------------------------------------------

@@ -101,6 +101,21 @@ def rnd(n: int, what: str) -> bytes:
     return R.data(n, what.encode())
 
 
+def poly_rs(key: bytes, nonce12: bytes):
+    """The Poly1305 key of a record as integers: r clamped, and s."""
+    r16, s16 = R.poly_key(key, nonce12)
+    return int.from_bytes(r16, "little") & R.CLAMP, int.from_bytes(s16, "little")
+
+
+def model_record(kslot: int, seq: int, iv12: bytes | None = None):
+    """(key, nonce, r, s) of a TLS record under key slot kslot, for the CPU models of the
+    kernels' MACs: the slot's key and write IV (or iv12), the nonce rule above, which is
+    TLS 1.3's too."""
+    key = KEYS3[32 * kslot:32 * kslot + 32]
+    nonce = tls_nonce(IVS3[12 * kslot:12 * kslot + 12] if iv12 is None else iv12, seq)
+    return (key, nonce) + poly_rs(key, nonce)
+
+
 def listed_case(lens, *, mode, skew=(0, 0), align=16, kidx=None, keys=KEYS3, tag="", **kw) -> RfcCase:
     """A listed batch of `lens` (mode "tls" or an explicit AD length): records in slots
     of `align` plus skew bytes, plaintext and, in explicit mode, nonces and ADs from SHAKE."""

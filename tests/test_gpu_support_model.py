@@ -224,8 +224,10 @@ def test_slots_are_the_formulas_the_tests_wrote_out(align, skew):
 
 
 class FakeLib:
+    START = {"sg_set_lockstep": 1, "sg_set_packed": 1, "sg_set_msg_groups": 0, "sg_set_tls13_buckets": 0}
+
     def __init__(self):
-        self.v = {"sg_set_lockstep": 1, "sg_set_packed": 1, "sg_set_msg_groups": 0}
+        self.v = dict(self.START)
         self.stuck = None
 
     def __getattr__(self, name):
@@ -239,21 +241,23 @@ class FakeLib:
 
 def test_kernel_forms_set_check_and_restore():
     lib = FakeLib()
-    with G.kernel_forms(lib, lockstep=0, groups=3):
-        assert lib.v == {"sg_set_lockstep": 0, "sg_set_packed": 1, "sg_set_msg_groups": 3}
-        with G.kernel_forms(lib, lockstep=1):
-            assert lib.v["sg_set_lockstep"] == 1
-        assert lib.v["sg_set_lockstep"] == 0
-    assert lib.v == {"sg_set_lockstep": 1, "sg_set_packed": 1, "sg_set_msg_groups": 0}
+    assert set(G.SWITCHES.values()) == set(lib.START)
+    with G.kernel_forms(lib, lockstep=0, groups=3, tls13_buckets=1):
+        assert lib.v == {"sg_set_lockstep": 0, "sg_set_packed": 1, "sg_set_msg_groups": 3, "sg_set_tls13_buckets": 1}
+        with G.kernel_forms(lib, lockstep=1, tls13_buckets=0):
+            assert lib.v["sg_set_lockstep"] == 1 and lib.v["sg_set_tls13_buckets"] == 0
+        assert lib.v["sg_set_lockstep"] == 0 and lib.v["sg_set_tls13_buckets"] == 1
+    assert lib.v == lib.START
     with pytest.raises(RuntimeError):  # restored when the body raises
-        with G.kernel_forms(lib, packed=0):
+        with G.kernel_forms(lib, packed=0, tls13_buckets=1):
             raise RuntimeError
-    assert lib.v["sg_set_packed"] == 1
-    lib.stuck = "sg_set_packed"  # a switch that does not take: the readback fails, the others are put back
-    with pytest.raises(AssertionError):
-        with G.kernel_forms(lib, lockstep=0, packed=0):
-            pass
-    assert lib.v == {"sg_set_lockstep": 1, "sg_set_packed": 1, "sg_set_msg_groups": 0}
+    assert lib.v["sg_set_packed"] == 1 and lib.v["sg_set_tls13_buckets"] == 0
+    for stuck in ("sg_set_packed", "sg_set_tls13_buckets"):
+        lib.stuck = stuck  # a switch that does not take: the readback fails, the others are put back
+        with pytest.raises(AssertionError):
+            with G.kernel_forms(lib, lockstep=0, packed=0, tls13_buckets=1):
+                pass
+        assert lib.v == lib.START, stuck
 
 
 def test_support_module_needs_no_torch():

@@ -4,8 +4,9 @@ open, on the GPU.
 The reference for every byte is tests/tls13_ref.py; every buffer is compared whole
 (tests/tls13_pad_support.py, tests/tls13_batch_support.py), so a record writes exactly its
 inner + 16 bytes and its input stays as it was.  The routes must be those of
-tests/tls13_bucket_support.py's restatement of wpr_bucket_of and pack_ok.  The switch is
-on unless a test says otherwise, and every switch a test sets is put back."""
+tests/footprint.py's route model on the inner lengths (tls13_pad_support.routes_of).  The switch
+is on unless a test says otherwise, and every switch a test sets is put back by
+gpu_support.kernel_forms."""
 from __future__ import annotations
 
 import functools
@@ -17,7 +18,6 @@ import footprint as fp
 import rfc8439_ref as R
 import rfc_batch_support as S
 import tls13_batch_support as X
-import tls13_bucket_support as K
 import tls13_pad_support as Q
 import tls13_ref as T
 from gpu_support import kernel_forms
@@ -48,7 +48,7 @@ def types_of(count):
 # ---------------------------------------------------------------------------
 # the bucket edges; then packed sizes (inner 64, 64, 1024, 4096), a bucket record with the most
 # padding a pad_to of 64 gives (16320 -> 16384), a full record (inner 2^14 + 1: the classes) and 5000
-EDGE_LENS = tuple(K.bucket_edge_lens()) + (0, 63, 1000, 4095, 16320, 16384, 5000)
+EDGE_LENS = tuple(Q.bucket_edge_lens()) + (0, 63, 1000, 4095, 16320, 16384, 5000)
 
 
 @functools.lru_cache(maxsize=None)
@@ -61,16 +61,16 @@ def edge_batch():
 
 def test_edges_seal_then_open(gpu):
     contents, kidx, seqs, types, want = edge_batch()
-    assert [len(w) - 16 for w in want[:len(K.BUCKET_NS)]] == list(K.BUCKET_NS)
+    assert [len(w) - 16 for w in want[:len(Q.BUCKET_NS)]] == list(Q.BUCKET_NS)
     opened = [(T.OK, t, n) for t, n in zip(types, EDGE_LENS)]
     for on in (1, 0):
-        with K.tls13_buckets(gpu, on):
+        with kernel_forms(gpu, tls13_buckets=on):
             frags, routes, eligible = Q.seal_padded(contents, kidx, seqs, pad_to=64, types=types, ctype=0, want=want,
                                                     where=("edges", on))
-            model = K.seal_routes(EDGE_LENS, 64, buckets=bool(on))
+            model = Q.seal_routes(EDGE_LENS, 64, buckets=bool(on))
             assert frags == want and routes == model and eligible == model["packed"], (on, routes, model)
             got, routes = Q.open_routes(frags, kidx, seqs, where=("edges", on))
-            assert got == opened and routes == K.open_routes_of(frags, buckets=bool(on)), (on, routes)
+            assert got == opened and routes == Q.open_routes_of(frags, buckets=bool(on)), (on, routes)
             if on:
                 assert model["bucket"] == [2 * 19 + 1, 2 * 19, 3 * 19 + 1] and routes["bucket"] == model["bucket"]
                 assert model["packed"] == 4 and model["classes"] == 1
@@ -97,9 +97,9 @@ def test_whole_chunks_of_padding(gpu, pad_to):
     contents = [rnd(n, f"tls13 chunks {pad_to} {i}") for i, n in enumerate(lens)]
     kidx, seqs = ids(len(lens), 2**32 - 5)
     types = types_of(len(lens))
-    with K.tls13_buckets(gpu, 1):
+    with kernel_forms(gpu, tls13_buckets=1):
         frags, routes, _ = Q.seal_padded(contents, kidx, seqs, pad_to=pad_to, types=types, ctype=0, where=("chunks",))
-        model = K.seal_routes(lens, pad_to, buckets=True)
+        model = Q.seal_routes(lens, pad_to, buckets=True)
         assert routes == model and model["classes"] == model["packed"] == 0, (routes, model)
         assert model["bucket"] == ([8, 0, 8] if pad_to == 8192 else [0, 0, 16])
         got, routes = Q.open_routes(frags, kidx, seqs, where=("chunks",))
@@ -111,21 +111,21 @@ def test_whole_chunks_of_padding(gpu, pad_to):
 # ---------------------------------------------------------------------------
 def test_eligibility_on_seal(gpu):
     # records 0 and 16, which a layout skewed by (1, 3) still leaves 16-byte aligned, are full records
-    lens = [N if i in (0, 16) else n for i, n in enumerate(K.bucket_edge_lens()[:21])]
+    lens = [N if i in (0, 16) else n for i, n in enumerate(Q.bucket_edge_lens()[:21])]
     contents = [rnd(n, f"tls13 eligible {i}") for i, n in enumerate(lens)]
     kidx, seqs = ids(len(lens))
-    with K.tls13_buckets(gpu, 1):
+    with kernel_forms(gpu, tls13_buckets=1):
         _, routes, _ = Q.seal_padded(contents, kidx, seqs, pad_to=64, where=("aligned",))
-        assert routes == K.seal_routes(lens, 64, buckets=True) and sum(routes["bucket"]) == 19
+        assert routes == Q.seal_routes(lens, 64, buckets=True) and sum(routes["bucket"]) == 19
         _, routes, _ = Q.seal_padded(contents, kidx, seqs, pad_to=64, skew=(1, 3), where=("skewed",))
-        assert routes == K.seal_routes(lens, 64, (1, 3), buckets=True) and routes["bucket"] == NO_BUCKETS, routes
+        assert routes == Q.seal_routes(lens, 64, (1, 3), buckets=True) and routes["bucket"] == NO_BUCKETS, routes
         with kernel_forms(gpu, lockstep=0):
             _, routes, _ = Q.seal_padded(contents, kidx, seqs, pad_to=64, where=("lockstep off",))
-            assert routes == K.seal_routes(lens, 64, buckets=False) and routes["bucket"] == NO_BUCKETS, routes
+            assert routes == Q.seal_routes(lens, 64, buckets=False) and routes["bucket"] == NO_BUCKETS, routes
         # multiples of 100 that are no multiples of 64
         assert all(Q.inner_len(n, 100) % 64 for n in lens)
         _, routes, _ = Q.seal_padded(contents, kidx, seqs, pad_to=100, where=("pad 100",))
-        assert routes == K.seal_routes(lens, 100, buckets=True) and routes["bucket"] == NO_BUCKETS, routes
+        assert routes == Q.seal_routes(lens, 100, buckets=True) and routes["bucket"] == NO_BUCKETS, routes
 
 
 def test_eligibility_on_open(gpu):
@@ -135,12 +135,12 @@ def test_eligibility_on_open(gpu):
     frags = [want[i] for i in pick]
     assert len(frags[7]) == N + 17
     opened = [(T.OK, types[i], EDGE_LENS[i]) for i in pick]
-    with K.tls13_buckets(gpu, 1):
+    with kernel_forms(gpu, tls13_buckets=1):
         got, routes = Q.open_routes(frags, kidx[pick], seqs[pick], where=("full",))
-        assert got == opened and routes == K.open_routes_of(frags, buckets=True)
+        assert got == opened and routes == Q.open_routes_of(frags, buckets=True)
         assert routes["classes"] == 1 and sum(routes["bucket"]) == 9, routes
         got, routes = Q.open_routes(frags, kidx[pick], seqs[pick], skew=(1, 3), where=("skewed",))
-        assert got == opened and routes == K.open_routes_of(frags, (1, 3), buckets=True)
+        assert got == opened and routes == Q.open_routes_of(frags, (1, 3), buckets=True)
         assert routes["bucket"] == [1, 0, 0], routes  # record 0 alone is still aligned
         with kernel_forms(gpu, lockstep=0):
             got, routes = Q.open_routes(frags, kidx[pick], seqs[pick], where=("lockstep off",))
@@ -163,7 +163,7 @@ def test_a_wave_runs_more_than_one_record(gpu):
     cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
     count = 8 * (2 * 2 * cus + 1) + 3
     inner = 4160
-    lens = [inner - 64 + K.ENDS[i % len(K.ENDS)] for i in range(count)]
+    lens = [inner - 64 + Q.ENDS[i % len(Q.ENDS)] for i in range(count)]
     kidx, seqs = ids(count, 2**32 - 1000)
     types = types_of(count)
     in_off, out_off, in_size, out_size = Q.layout(lens, [inner] * count)
@@ -184,7 +184,7 @@ def test_a_wave_runs_more_than_one_record(gpu):
 
     sealed = {}
     for on in (0, 1):
-        with K.tls13_buckets(gpu, on):
+        with kernel_forms(gpu, tls13_buckets=on):
             o = fp.run_whole(seal, in_img, fp.sentinel(size, 0x5A), sealed.get(0), rs)
         assert o.ret["known"] and o.ret["bucket"] == ([count, 0, 0] if on else NO_BUCKETS), o.ret
         sealed[on] = o.out
@@ -214,7 +214,7 @@ def test_a_wave_runs_more_than_one_record(gpu):
 
     opened = {}
     for on in (0, 1):
-        with K.tls13_buckets(gpu, on):
+        with kernel_forms(gpu, tls13_buckets=on):
             o = fp.run_whole(open_, sealed[1], fp.sentinel(osize, 0xA5), opened.get(0), ors,
                              arrays={"status": fp.array_start(count, 0x51), "inner_type": fp.array_start(count, 0x52),
                                      "content_len": fp.array_start(count, 0x53, np.uint32)})
@@ -253,10 +253,10 @@ def test_tamper(gpu, keep):
         flips[i] = [(0, 0x01), (lens[i] + 1 + 5, 0x40), (n - 1, 0x80), (n, 0x01), (n + 15, 0x80)][kind]
         frags[i][flips[i][0]] ^= flips[i][1]
     assert len(flips) == 15
-    with K.tls13_buckets(gpu, 1):
+    with kernel_forms(gpu, tls13_buckets=1):
         got, routes = Q.open_routes([bytes(f) for f in frags], kidx, seqs, keep=keep, where=("tamper", keep))
     assert got == [(T.BAD_MAC, 0, 0) if i in flips else (T.OK, 23, n) for i, n in enumerate(lens)]
-    assert routes == K.open_routes_of(frags, buckets=True) and sum(routes["bucket"]) == count, routes
+    assert routes == Q.open_routes_of(frags, buckets=True) and sum(routes["bucket"]) == count, routes
 
 
 # ---------------------------------------------------------------------------
@@ -279,7 +279,7 @@ def test_mac_finish(gpu):
         frags.append(ct + R.tag_of(key, nonce, ad, ct))
     bad = [f[:-1] + bytes([f[-1] ^ 1]) for f in frags]
     for on in (1, 0):
-        with K.tls13_buckets(gpu, on):
+        with kernel_forms(gpu, tls13_buckets=on):
             got, routes = Q.open_routes(frags, kidx, seqs, where=("finish", on))
             assert [g[0] for g in got] == [T.OK] * len(shapes)
             assert routes["bucket"] == ([6, 6, 6] if on else NO_BUCKETS), routes
@@ -302,7 +302,7 @@ def test_open_of_content_that_ends_in_zero_bytes(gpu):
              for i, (c, t) in enumerate(recs)]
     frags.append(T.seal_inner(*X.key_iv(int(kidx[-1])), int(seqs[-1]), bytes(8192)))
     want = [(T.OK, t, len(c)) for c, t in recs] + [(T.NO_TYPE, 0, 0)]
-    with K.tls13_buckets(gpu, 1):
+    with kernel_forms(gpu, tls13_buckets=1):
         got, routes = Q.open_routes(frags, kidx, seqs, where=("zeros",))
     assert got == want
-    assert routes == K.open_routes_of(frags, buckets=True) and routes["bucket"] == [5, 0, 1], routes
+    assert routes == Q.open_routes_of(frags, buckets=True) and routes["bucket"] == [5, 0, 1], routes

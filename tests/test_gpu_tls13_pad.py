@@ -12,6 +12,7 @@ import functools
 import numpy as np
 import pytest
 
+import footprint as fp
 import rfc8439_ref as R
 import rfc_batch_support as S
 import tls13_batch_support as X
@@ -57,7 +58,7 @@ def edge_sealed(pad_to, lens=LENS):
 
 def packable(frags) -> int:
     """Fragments the packed kernel takes when every record is 16-byte aligned."""
-    return sum(Q.eligible(len(f) - 16, 0, 0) for f in frags)
+    return sum(fp.pack_ok(len(f) - 16, 0, 0) for f in frags)
 
 
 # ---------------------------------------------------------------------------
@@ -196,7 +197,6 @@ def test_per_record_types(gpu, pad_to):
 def test_per_record_types_of_uniform_full_records(gpu):
     """Full records in the wave-per-record kernel's shape: with inner_types the call stays
     off that route, whose pre-pass appends the call's one type."""
-    import footprint as fp
     from gpu_support import dev_u8
     from suruga_amd import batch as B
 

@@ -19,7 +19,7 @@ import functools
 import pytest
 
 import mac_forge as F
-
+import wpr_model as W
 
 
 @functools.lru_cache(maxsize=None)
@@ -72,11 +72,9 @@ def test_forged_records_against_the_oracle(oracle, group):
 def test_wpr_extreme_ciphertext_in_the_model(oracle):
     """Tier C: the fills and the sign-aligned patterns keep the model's seeded
     accumulator in (0, 2^25) (asserted inside wpr_tag) and give the oracle's tag."""
-    from test_wpr_mac_model import wpr_tag
-
     for case in groups()["wpr_c"]:
         f = check_record(oracle, case)
-        assert wpr_tag(f.ad, f.ct, f.r, f.s) == f.tag, case
+        assert W.wpr_tag(f.ad, f.ct, f.r, f.s, W.keying(W.DRAFT, f.ad, f.r)) == f.tag, case
 
 
 def test_sign_patterns_follow_the_digit_signs(oracle):

@@ -16,7 +16,7 @@ import ctypes as C
 
 import pytest
 
-from test_msg_batch_abi import batch
+from msg_batch_support import batch
 
 NULLS = "in/out/ad must be non-NULL"
 TOO_LONG = "message longer than SG_MSG_MAX_LEN"

@@ -8,6 +8,8 @@ import ctypes as C
 
 import pytest
 
+from msg_batch_support import batch, rejected
+
 
 @pytest.fixture(scope="module")
 def lib():
@@ -15,34 +17,6 @@ def lib():
 
     _build.build_library()
     return _native.load()
-
-
-def batch(count=2, n=100, adlen=13):
-    """A well-formed seal batch on made-up device addresses, its items and a fitting workspace size."""
-    from suruga_amd import _native as N
-
-    items = (N.SgMsgItem * max(count, 1))()
-    for i in range(count):
-        it = items[i]
-        it.key_index = i % 2
-        it.ad, it.ad_len = 0x100000 + 0x1000 * i, adlen
-        it.in_, it.in_len = 0x200000 + 0x10000 * i, n
-        it.out = 0x400000 + 0x10000 * i
-    b = N.SgMsgBatch()
-    b.count, b.flags, b.keys, b.num_keys, b.items = count, 0, 0x1000, 2, items
-    b.status = 0x2000
-    b.stream = None
-    b.workspace, b.workspace_size = 0x800000, N.load().sg_msg_batch_workspace_size(count)
-    return b, items
-
-
-def rejected(lib, b, open_=False, text=None):
-    from suruga_amd._native import SG_E_ARG
-
-    rc = (lib.sg_open_msg_batch if open_ else lib.sg_seal_msg_batch)(C.byref(b))
-    assert rc == SG_E_ARG, rc
-    if text:
-        assert text.encode() in lib.sg_last_error(), lib.sg_last_error()
 
 
 def test_null_batch_and_empty_batch(lib):

@@ -8,7 +8,7 @@ import pytest
 
 import msg_batch_support as mb
 from mac_forge import mac_stream
-from test_msg_model import rnd
+from msg_batch_support import rnd
 
 
 @pytest.fixture(scope="module", autouse=True)

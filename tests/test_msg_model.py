@@ -10,11 +10,10 @@ bit at its own length.  The geometry comes from sg_msg_plan_for, as it does on
 the device.  CPU only."""
 from __future__ import annotations
 
-import hashlib
-
 import pytest
 
 from mac_forge import mac_stream
+from msg_batch_support import rnd
 
 P1305 = (1 << 130) - 5
 CLAMP = 0x0FFFFFFC0FFFFFFC0FFFFFFC0FFFFFFF
@@ -44,15 +43,6 @@ def tiled_tag(stream: bytes, r16: bytes, s16: bytes, plan: dict) -> bytes:
             H = (H * R + h) % P1305
         total = (total + H * pow(R, T - hi, P1305)) % P1305
     return ((total + int.from_bytes(s16, "little")) % (1 << 128)).to_bytes(16, "little")
-
-
-def rnd(tag: str, n: int) -> bytes:
-    out = b""
-    i = 0
-    while len(out) < n:
-        out += hashlib.sha256(f"{tag}:{i}".encode()).digest()
-        i += 1
-    return out[:n]
 
 
 def cases():

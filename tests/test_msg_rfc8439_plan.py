@@ -183,7 +183,7 @@ def test_device_form_flags_without_gpu(lib):
 
 
 def test_batch_flags_without_gpu(lib):
-    from test_msg_batch_abi import batch, rejected
+    from msg_batch_support import batch, rejected
 
     from suruga_amd._native import SG_MSG_KEEP_FAILED, SG_MSG_RFC8439
 

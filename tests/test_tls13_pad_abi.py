@@ -9,6 +9,8 @@ from pathlib import Path
 
 import pytest
 
+from tls13_pad_support import inner_len  # RFC 8446 section 5.4, restated in Python once
+
 N = 1 << 14
 LENS = (0, 1, 62, 63, 64, 127, 4095, 4096, 16383, 16384)
 PADS = (0, 1, 2, 64, 100, 256, 16384)
@@ -52,10 +54,6 @@ def opts(inner_types=None, pad_to=64, flags=0):
 
 def err(lib) -> bytes:
     return lib.sg_last_error()
-
-
-def inner_len(n: int, pad_to: int) -> int:
-    return n + 1 if pad_to <= 1 else min(-(-(n + 1) // pad_to) * pad_to, N + 1)
 
 
 def test_options_struct_layout():

@@ -8,6 +8,11 @@ inner + 16 bytes per record may change and the input none.  The reference is
 tests/tls13_ref.py's seal with pad = inner - len - 1.  Opening goes through
 tls13_batch_support.open_whole as it is.
 
+The second half is what the TLS 1.3 bucket tests (sg_set_tls13_buckets) add: the routes a
+mixed batch must take, tests/footprint.py's route model on the inner lengths in the shape
+of sg_last_batch_routes.  Every buffer of these harnesses starts 16-byte aligned, so a
+record's offset stands for its address.
+
 Imports without torch and without a GPU."""
 from __future__ import annotations
 
@@ -16,6 +21,7 @@ import numpy as np
 import footprint as fp
 import tls13_batch_support as X
 import tls13_ref as T
+from gpu_support import slots
 
 M = fp.MARGIN
 N = 1 << 14
@@ -29,11 +35,6 @@ def inner_len(n: int, pad_to: int) -> int:
 def expected_padded(contents, kidx, seqs, pad_to, types, ivs=X.IVS3, keys=X.KEYS3):
     return [T.seal(*X.key_iv(int(k), ivs, keys), int(q), c, int(t), inner_len(len(c), pad_to) - len(c) - 1)
             for c, k, q, t in zip(contents, kidx, seqs, types)]
-
-
-def eligible(inner: int, in_addr: int, out_addr: int) -> bool:
-    """pack_ok on the inner length: the packed kernel's records."""
-    return inner % 64 == 0 and 64 <= inner <= 4096 and (in_addr | out_addr) % 16 == 0
 
 
 def layout(lens, inners, skew=(0, 0)):
@@ -81,7 +82,7 @@ def seal_padded(contents, kidx, seqs, *, pad_to, types=None, ctype=23, skew=(0, 
                 _seal_ex(batch)
             got["types"] = it  # (alive until the run is downloaded)
         got["routes"] = B.last_routes()
-        got["eligible"] = sum(eligible(n, d["inp"][M:].data_ptr() + int(i), d["out"][M:].data_ptr() + int(o))
+        got["eligible"] = sum(fp.pack_ok(n, d["inp"][M:].data_ptr() + int(i), d["out"][M:].data_ptr() + int(o))
                               for n, i, o in zip(inners, in_off, out_off))
 
     o = fp.run_whole(call, in_img, fp.sentinel(size, 0x5A), fp.image(size, 0x5A, [(lo, w) for (lo, _), w in zip(rs, want)]), rs)
@@ -105,3 +106,39 @@ def open_routes(frags, kidx, seqs, **kw):
 
     got = X.open_whole(frags, kidx, seqs, **kw)
     return got, B.last_routes()
+
+
+# ---------------------------------------------------------------------------
+# the routes of a mixed batch, buckets included
+# ---------------------------------------------------------------------------
+BUCKET_NS = (4160, 8192, 8256, 12288, 12352, 16320, 16384)
+# where a content may end in its last 64-byte block: bytes 0, 1 and 15 of 16-byte units, and the block's last two
+ENDS = (0, 1, 15, 16, 17, 31, 47, 62, 63)
+
+
+def routes_of(inners, in_off, out_off, *, buckets: bool, packed: bool = True) -> dict:
+    """What sg_last_batch_routes must say of records of these inner lengths at these offsets."""
+    c = fp.route_counts(inners, in_off, out_off, buckets, packed)
+    return {"known": True, "classes": sum(v for k, v in c.items() if k[0] == "class"),
+            "bucket": [c.get(("bucket", J), 0) for J in (2, 3, 4)], "packed": c.get(("packed",), 0), "skipped": 0}
+
+
+def seal_routes(lens, pad_to, skew=(0, 0), **kw) -> dict:
+    """... of a seal_padded of contents of these lengths."""
+    inners = [inner_len(n, pad_to) for n in lens]
+    in_off, out_off, _, _ = layout(lens, inners, skew)
+    return routes_of(inners, in_off, out_off, **kw)
+
+
+def open_routes_of(frags, skew=(0, 0), **kw) -> dict:
+    """... of a tls13_batch_support.open_whole of these fragments (its layout is a seal's, run backwards)."""
+    inners = [max(len(f) - 16, 0) for f in frags]
+    out_off, in_off, _, _ = slots(inners, 16, skew, 16)
+    return routes_of(inners, in_off, out_off, **kw)
+
+
+def bucket_edge_lens():
+    """19 content lengths per inner length of BUCKET_NS under pad_to = 64, interleaved over the
+    inner lengths: two full groups of eight and a partial one per bucket, the content ending at
+    every place of ENDS."""
+    return [n - 64 + ENDS[(i + j) % len(ENDS)] for i in range(19) for j, n in enumerate(BUCKET_NS)]

@@ -125,17 +125,16 @@ def run(w: dict, reps: int, warmup: int) -> dict:
     from suruga_amd import batch as B
 
     from gpu_support import kernel_forms  # sets the switch and puts it back after the launch
-    from tls13_bucket_support import tls13_buckets  # likewise, sg_set_tls13_buckets
 
     lib = _native.load()
-    forms = {"tls13_classes": lambda: kernel_forms(lib, packed=0), "tls13_buckets": lambda: tls13_buckets(lib, 1)}
+    forms = {"tls13_classes": dict(packed=0), "tls13_buckets": dict(tls13_buckets=1)}
     routes = {}
 
     def leg(name, d):
         t13 = name != "rfc7905"
 
         def fn():
-            with forms.get(name, lambda: kernel_forms(lib))():
+            with kernel_forms(lib, **forms.get(name, {})):
                 if not t13:
                     (B.open_ if d else B.seal)(w["legs"][name][d])
                 elif d:
