@@ -643,6 +643,17 @@ int sg_record_timing(double* h2d_ms, double* kernel_ms, double* d2h_ms, double* 
  * sg_ctx_new and every draft call behave as before, with or without an IV. */
 int sg_ctx_set_iv(sg_ctx* ctx, const uint8_t iv[12]);
 
+/* Derives key and IV from a TLS 1.3 traffic secret (RFC 8446 section 7.3) and
+ * installs them: the 32 key bytes replace the context's key on the device, the
+ * IV as sg_ctx_set_iv does.  The context keeps the secret for sg_ctx_key_update.
+ * Not while another call uses the context, as sg_ctx_set_iv. */
+int sg_ctx_set_traffic_secret(sg_ctx* ctx, const uint8_t secret[32]);
+/* KeyUpdate (RFC 8446 section 4.6.3, 7.2): secret <- Expand-Label(secret,
+ * "traffic upd", "", 32), then as above; the old secret's host copy is
+ * overwritten.  SG_E_ARG on a context that never had a secret.  The caller
+ * restarts its sequence numbers at 0 (section 5.3). */
+int sg_ctx_key_update(sg_ctx* ctx);
+
 /* RFC 7905 (TLS 1.2 suites 0xCCA8 / 0xCCA9): the signatures, wire format,
  * header checks, 13-byte AD, error order and sg_read_result of
  * sg_write_records / sg_read_records; the sealing is the RFC 8439 record batch
@@ -762,6 +773,56 @@ int  sg_derive_keys_ivs(uint32_t count, const uint8_t* pre_master, size_t pm_len
  * "server finished"): PRF(master_secret, label || handshake_hash)[0..12]. */
 int  sg_finished_verify_data(const uint8_t master_secret[48], int server,
                              const uint8_t handshake_hash[32], uint8_t out[12]);
+
+/* ---- TLS 1.3 traffic keys and KeyUpdate (RFC 8446 section 7.1 - 7.3) -------
+ * TLS_CHACHA20_POLY1305_SHA256 is the one TLS 1.3 suite the library speaks, so
+ * the hash is SHA-256 throughout.  The first three calls are CPU only, as the
+ * TLS 1.2 schedule above; the early and handshake secrets' Derive-Secret chains
+ * are the caller's to compose from the first two. */
+
+/* RFC 5869 section 2.2 with SHA-256.  salt NULL / 0 bytes = 32 zero bytes; salt_len <= 64
+ * (the HMAC key bound of sg_hmac_sha256), else SG_E_ARG. */
+int sg_hkdf_extract(const uint8_t* salt, size_t salt_len, const uint8_t* ikm, size_t ikm_len, uint8_t prk[32]);
+
+/* RFC 8446 section 7.1: HKDF-Expand(secret, HkdfLabel, out_len) with
+ * HkdfLabel = be16(out_len) || u8(6 + label_len) || "tls13 " || label || u8(context_len) || context.
+ * label_len <= 249, context_len <= 255, out_len <= 255 * 32; out_len 0 writes nothing. */
+int sg_hkdf_expand_label(const uint8_t secret[32], const char* label, size_t label_len,
+                         const uint8_t* context, size_t context_len, uint8_t* out, size_t out_len);
+
+/* RFC 8446 section 7.3 / 7.2 for `count` connections, host memory, threads >= 1:
+ *   update != 0:  secrets[i] <- Expand-Label(secrets[i], "traffic upd", "", 32)   (in place, first)
+ *   keys[i]  = Expand-Label(secrets[i], "key", "", 32)      [count][32], may be NULL
+ *   ivs[i]   = Expand-Label(secrets[i], "iv",  "", 12)      [count][12], may be NULL
+ * count == 0 is SG_OK; a call that would do nothing (no keys, no ivs, no update) is SG_E_ARG. */
+int sg_tls13_traffic_keys(uint32_t count, uint8_t* secrets, uint8_t* keys, uint8_t* ivs, int update, int threads);
+
+/* The same on the device: one launch turns a device table of traffic secrets
+ * into the keys / ivs tables of the batch calls, in place in HBM (sg_hkdf.hip:
+ * one lane per row).  Per row exactly the host call.  The selected rows of keys
+ * and ivs are written, 32 and 12 bytes each, and under UPDATE the same rows of
+ * secrets; no other byte of any table is.  Ordered on its stream like a batch
+ * call -- a sg_seal_batch_tls13 enqueued on the same stream right after it sees
+ * the new rows -- and capturable: no workspace, no host read-back.
+ * SG_E_ARG before any GPU work: NULL k, unknown flags, NULL secrets, a
+ * misaligned pointer, keys == ivs == NULL without UPDATE, index == NULL with
+ * count > rows.  count == 0 returns SG_OK and launches nothing. */
+#define SG_TLS13_KEYS_UPDATE 0x1u   /* ratchet the secret first (KeyUpdate), in place */
+typedef struct sg_tls13_keys {
+    uint32_t        count;    /* rows to derive                                                       */
+    uint32_t        flags;    /* 0 or SG_TLS13_KEYS_UPDATE; anything else SG_E_ARG                    */
+    uint32_t        rows;     /* rows of every table                                                  */
+    uint32_t        _pad;
+    const uint32_t* index;    /* device, count row numbers, 4-byte aligned; NULL: rows 0..count-1
+                                 (then count <= rows).  An entry >= rows is skipped: nothing is read
+                                 or written for it.  A row named twice in an UPDATE call holds an
+                                 unspecified generation afterwards (no fault; the caller's to avoid) */
+    uint8_t*        secrets;  /* device [rows][32], 4-byte aligned; read, and written under UPDATE    */
+    uint8_t*        keys;     /* device [rows][32], 4-byte aligned, or NULL  -> sg_batch.keys         */
+    uint8_t*        ivs;      /* device [rows][12], 4-byte aligned, or NULL  -> sg_batch_tls13.ivs    */
+    void*           stream;   /* as sg_batch.stream: non-NULL asynchronous, NULL waits                */
+} sg_tls13_keys;              /* 56 bytes */
+int sg_tls13_traffic_keys_dev(const sg_tls13_keys* k);
 
 /* ---- synthetic workload helpers (bench / tests) ------------------------ */
 /* Fills records on the device: byte i of record j =

@@ -50,6 +50,8 @@ EXPORTS = [
     "sg_set_record13_gather",
     "sg_sha256", "sg_hmac_sha256", "sg_prf_new", "sg_prf_get_bytes", "sg_prf_free",
     "sg_derive_keys", "sg_derive_keys_ivs", "sg_finished_verify_data",
+    "sg_hkdf_extract", "sg_hkdf_expand_label", "sg_tls13_traffic_keys", "sg_tls13_traffic_keys_dev",
+    "sg_ctx_set_traffic_secret", "sg_ctx_key_update",
     "sg_msg_workspace_size", "sg_seal_msg_dev", "sg_open_msg_dev", "sg_seal_msg", "sg_open_msg",
     "sg_seal_msg_rfc8439", "sg_open_msg_rfc8439",
     "sg_msg_plan_for", "sg_msg_plan_for_flags", "sg_set_msg_groups",
@@ -115,6 +117,15 @@ class SgTls13SealOpts(C.Structure):
 
 
 SG_TLS13_MAX_INNER = (1 << 14) + 1
+SG_TLS13_KEYS_UPDATE = 0x1
+
+
+class SgTls13Keys(C.Structure):
+    """Mirror of ``struct sg_tls13_keys``."""
+
+    _fields_ = [("count", C.c_uint32), ("flags", C.c_uint32), ("rows", C.c_uint32), ("_pad", C.c_uint32),
+                ("index", C.c_void_p), ("secrets", C.c_void_p), ("keys", C.c_void_p), ("ivs", C.c_void_p),
+                ("stream", C.c_void_p)]
 
 
 class SgBatchRoutes(C.Structure):
@@ -368,6 +379,18 @@ def _declare(lib: C.CDLL) -> None:
     lib.sg_derive_keys_ivs.argtypes = [C.c_uint32, vp, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, C.c_int]
     lib.sg_finished_verify_data.restype = C.c_int
     lib.sg_finished_verify_data.argtypes = [vp, C.c_int, vp, vp]
+    lib.sg_hkdf_extract.restype = C.c_int
+    lib.sg_hkdf_extract.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp]
+    lib.sg_hkdf_expand_label.restype = C.c_int
+    lib.sg_hkdf_expand_label.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
+    lib.sg_tls13_traffic_keys.restype = C.c_int
+    lib.sg_tls13_traffic_keys.argtypes = [C.c_uint32, vp, vp, vp, C.c_int, C.c_int]
+    lib.sg_tls13_traffic_keys_dev.restype = C.c_int
+    lib.sg_tls13_traffic_keys_dev.argtypes = [C.POINTER(SgTls13Keys)]
+    lib.sg_ctx_set_traffic_secret.restype = C.c_int
+    lib.sg_ctx_set_traffic_secret.argtypes = [C.c_void_p, C.c_char_p]
+    lib.sg_ctx_key_update.restype = C.c_int
+    lib.sg_ctx_key_update.argtypes = [C.c_void_p]
     lib.sg_msg_workspace_size.restype = C.c_size_t
     lib.sg_msg_workspace_size.argtypes = []
     for f in (lib.sg_seal_msg_dev, lib.sg_open_msg_dev):

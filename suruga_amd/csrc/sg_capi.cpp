@@ -492,6 +492,52 @@ int sg_ctx_set_iv(sg_ctx* c, const uint8_t iv[12]) {
     return SG_OK;
 }
 
+// key and IV of c->secret (after one ratchet step with update) onto the device; c->mu held
+static int install_traffic_keys(sg_ctx* c, int update) {
+    uint8_t key[32], iv[12];
+    int rc = sg_tls13_traffic_keys(1, c->secret, key, iv, update, 1);
+    if (rc != SG_OK) return rc;
+    sg::DeviceGuard dg(c->device);
+    if (!dg.ok) return fail(SG_E_HIP, "hipSetDevice failed%s");
+    SG_HIP(hipMemcpy(c->d_key, key, 32, hipMemcpyHostToDevice));
+    SG_HIP(hipMemcpy(c->d_key + sg::kIvOff, iv, 12, hipMemcpyHostToDevice));
+    std::memcpy(c->iv, iv, 12);
+    c->has_iv = true;
+    return SG_OK;
+}
+
+int sg_ctx_set_traffic_secret(sg_ctx* c, const uint8_t secret[32]) {
+    if (!c || !secret) return fail(SG_E_ARG, "NULL argument%s");
+    std::lock_guard<std::mutex> lk(c->mu);
+    std::memcpy(c->secret, secret, 32);
+    c->has_secret = true;
+    return install_traffic_keys(c, 0);
+}
+
+int sg_ctx_key_update(sg_ctx* c) {
+    if (!c) return fail(SG_E_ARG, "NULL argument%s");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->has_secret) return fail(SG_E_ARG, "the context has no traffic secret (sg_ctx_set_traffic_secret)%s");
+    return install_traffic_keys(c, 1);
+}
+
+int sg_tls13_traffic_keys_dev(const sg_tls13_keys* k) {
+    if (!k) return fail(SG_E_ARG, "sg_tls13_keys is NULL%s");
+    static_assert(sizeof(sg_tls13_keys) == 56, "sg_tls13_keys layout");
+    if (k->flags & ~SG_TLS13_KEYS_UPDATE) return fail(SG_E_ARG, "unknown flags in sg_tls13_keys%s");
+    const bool update = (k->flags & SG_TLS13_KEYS_UPDATE) != 0u;
+    if (!k->secrets) return fail(SG_E_ARG, "secrets is NULL%s");
+    if (((uintptr_t)k->secrets | (uintptr_t)k->keys | (uintptr_t)k->ivs | (uintptr_t)k->index) & 3u)
+        return fail(SG_E_ARG, "secrets, keys, ivs and index must be 4-byte aligned%s");
+    if (!k->keys && !k->ivs && !update) return fail(SG_E_ARG, "nothing to do: no keys, no ivs and no update%s");
+    if (!k->index && k->count > k->rows) return fail(SG_E_ARG, "count exceeds rows without an index%s");
+    if (k->count == 0) return SG_OK;
+    SG_HIP(sg::launch_tls13_keys(k->count, k->rows, update, k->index, k->secrets, k->keys, k->ivs,
+                                 (hipStream_t)k->stream));
+    if (!k->stream) SG_HIP(hipStreamSynchronize(nullptr));
+    return SG_OK;
+}
+
 int sg_gather_records(const uint8_t* src, uint32_t stride, const uint8_t* status, const uint32_t* content_len,
                       uint32_t count, uint8_t* dst, int use_base, const sg_gather_cursor* in, sg_gather_cursor* out,
                       uint32_t* result, void* stream) {

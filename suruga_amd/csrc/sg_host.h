@@ -81,5 +81,9 @@ struct sg_ctx {
     // host copy (explicit-mode nonces); the device copy is d_key + kIvOff
     uint8_t iv[12] = {0};
     bool has_iv = false;
+    // the TLS 1.3 traffic secret that key and IV were derived from
+    // (sg_ctx_set_traffic_secret), kept for sg_ctx_key_update's ratchet
+    uint8_t secret[32] = {0};
+    bool has_secret = false;
     std::mutex mu;
 };

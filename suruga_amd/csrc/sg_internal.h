@@ -306,5 +306,11 @@ hipError_t launch_fill(uint8_t* buf, uint64_t stride, uint32_t len, uint32_t cou
                        uint64_t j0, hipStream_t s);
 hipError_t launch_compare(const uint8_t* a, uint64_t sa, const uint8_t* b, uint64_t sb, uint32_t len,
                           uint32_t count, unsigned long long* mism, hipStream_t s);
+// ---- sg_hkdf.hip ----
+// TLS 1.3 traffic keys of `count` rows of device tables of `rows` rows (sg_tls13_traffic_keys_dev,
+// suruga_gpu.h): row = index ? index[i] : i, skipped where >= rows; every pointer 4-byte aligned,
+// keys / ivs may be NULL
+hipError_t launch_tls13_keys(uint32_t count, uint32_t rows, bool update, const uint32_t* index, uint8_t* secrets,
+                             uint8_t* keys, uint8_t* ivs, hipStream_t s);
 
 }  // namespace sg

@@ -13,23 +13,13 @@
 
 #include "../../include/suruga_gpu.h"
 #include "sg_err.h"  // host only: no HIP (tests/cpp/test_host_san.cpp builds it with g++ under sanitizers)
+#include "sg_hkdf.h"
 
 namespace sg {
 namespace {
 
 // ---- SHA-256 (FIPS 180-4; the algorithm of crypto/sha2.rs:18-116) ----------
-constexpr uint32_t kK[64] = {
-    0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u,
-    0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u,
-    0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau,
-    0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u,
-    0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
-    0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u,
-    0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u,
-    0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
-
-inline uint32_t rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
-
+// The compression function is sg_hkdf.h's, which the device key table kernel shares.
 struct Sha256 {
     uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
                      0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
@@ -38,21 +28,10 @@ struct Sha256 {
     uint64_t total = 0;
 
     void compress(const uint8_t* p) {
-        uint32_t w[64];
+        uint32_t w[16];
         for (int i = 0; i < 16; ++i)
             w[i] = (uint32_t)p[4 * i] << 24 | (uint32_t)p[4 * i + 1] << 16 | (uint32_t)p[4 * i + 2] << 8 | p[4 * i + 3];
-        for (int i = 16; i < 64; ++i) {
-            const uint32_t s0 = rotr(w[i - 15], 7) ^ rotr(w[i - 15], 18) ^ (w[i - 15] >> 3);
-            const uint32_t s1 = rotr(w[i - 2], 17) ^ rotr(w[i - 2], 19) ^ (w[i - 2] >> 10);
-            w[i] = w[i - 16] + s0 + w[i - 7] + s1;
-        }
-        uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
-        for (int i = 0; i < 64; ++i) {
-            const uint32_t t1 = hh + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + ((e & f) ^ (~e & g)) + kK[i] + w[i];
-            const uint32_t t2 = (rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
-            hh = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
-        }
-        h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
+        hkdf::compress(h, w);
     }
     void update(const uint8_t* p, size_t n) {
         total += n;
@@ -260,6 +239,112 @@ int sg_finished_verify_data(const uint8_t master_secret[48], int server, const u
     std::memcpy(seed, server ? "server finished" : "client finished", 15);
     std::memcpy(seed + 15, handshake_hash, 32);
     sg::Prf(master_secret, 48, seed, sizeof seed).get_bytes(out, 12);
+    return SG_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// TLS 1.3: HKDF (RFC 5869) with SHA-256, HKDF-Expand-Label (RFC 8446 section
+// 7.1) and the traffic keys of section 7.3 with the KeyUpdate ratchet of 7.2.
+// The label bytes and the per-connection derivation are sg_hkdf.h's, shared
+// with the device form (sg_hkdf.hip).
+// ---------------------------------------------------------------------------
+namespace sg {
+namespace {
+
+// HKDF-Expand, the general one: T(i) = HMAC(prk, T(i - 1) || info || i), i = 1 .. ceil(n / 32)
+void hkdf_expand(const uint8_t prk[32], const uint8_t* info, size_t info_len, uint8_t* out, size_t n) {
+    uint8_t pad[64];
+    std::memset(pad, 0x36, 64);
+    for (int i = 0; i < 32; ++i) pad[i] ^= prk[i];
+    Sha256 inner0;
+    inner0.update(pad, 64);
+    std::memset(pad, 0x5c, 64);
+    for (int i = 0; i < 32; ++i) pad[i] ^= prk[i];
+    Sha256 outer0;
+    outer0.update(pad, 64);
+    uint8_t t[32];
+    for (size_t done = 0, i = 1; done < n; done += 32, ++i) {
+        Sha256 hi = inner0;
+        if (i > 1) hi.update(t, 32);
+        if (info_len) hi.update(info, info_len);
+        const uint8_t ctr = (uint8_t)i;
+        hi.update(&ctr, 1);
+        hi.finish(t);
+        Sha256 ho = outer0;
+        ho.update(t, 32);
+        ho.finish(t);
+        std::memcpy(out + done, t, std::min<size_t>(32, n - done));
+    }
+}
+
+inline void load_be(const uint8_t* p, uint32_t* w, int words) {
+    for (int i = 0; i < words; ++i)
+        w[i] = (uint32_t)p[4 * i] << 24 | (uint32_t)p[4 * i + 1] << 16 | (uint32_t)p[4 * i + 2] << 8 | p[4 * i + 3];
+}
+inline void store_be(const uint32_t* w, uint8_t* p, int words) {
+    for (int i = 0; i < words; ++i) {
+        p[4 * i] = (uint8_t)(w[i] >> 24);
+        p[4 * i + 1] = (uint8_t)(w[i] >> 16);
+        p[4 * i + 2] = (uint8_t)(w[i] >> 8);
+        p[4 * i + 3] = (uint8_t)w[i];
+    }
+}
+
+void traffic_one(uint8_t* secret, uint8_t* key, uint8_t* iv, bool update) {
+    uint32_t s[8], k[8], v[8];
+    load_be(secret, s, 8);
+    hkdf::traffic_row(s, update, key != nullptr, iv != nullptr, k, v);
+    if (update) store_be(s, secret, 8);
+    if (key) store_be(k, key, 8);
+    if (iv) store_be(v, iv, 3);
+}
+
+}  // namespace
+}  // namespace sg
+
+extern "C" {
+
+int sg_hkdf_extract(const uint8_t* salt, size_t salt_len, const uint8_t* ikm, size_t ikm_len, uint8_t prk[32]) {
+    if (salt_len > sg::kMaxHmacKey) return fail(SG_E_ARG, "HKDF salt longer than 64 bytes (the HMAC key bound)%s");
+    if ((salt_len && !salt) || (ikm_len && !ikm) || !prk) return fail(SG_E_ARG, "NULL argument%s");
+    const uint8_t zeros[32] = {0};  // RFC 5869 section 2.2: no salt = HashLen zeros
+    sg::hmac(salt_len ? salt : zeros, salt_len ? salt_len : 32, ikm, ikm_len, nullptr, 0, prk);
+    return SG_OK;
+}
+
+int sg_hkdf_expand_label(const uint8_t secret[32], const char* label, size_t label_len, const uint8_t* context,
+                         size_t context_len, uint8_t* out, size_t out_len) {
+    if (label_len > sg::hkdf::kMaxLabel) return fail(SG_E_ARG, "HKDF label longer than 249 bytes%s");
+    if (context_len > sg::hkdf::kMaxContext) return fail(SG_E_ARG, "HKDF context longer than 255 bytes%s");
+    if (out_len > sg::hkdf::kMaxOut) return fail(SG_E_ARG, "HKDF output longer than 255 * 32 bytes%s");
+    if (!secret || (label_len && !label) || (context_len && !context) || (out_len && !out))
+        return fail(SG_E_ARG, "NULL argument%s");
+    if (!out_len) return SG_OK;
+    uint8_t info[sg::hkdf::kMaxInfo];
+    const size_t n = sg::hkdf::hkdf_label(info, out_len, label, label_len, context, context_len);
+    sg::hkdf_expand(secret, info, n, out, out_len);
+    return SG_OK;
+}
+
+int sg_tls13_traffic_keys(uint32_t count, uint8_t* secrets, uint8_t* keys, uint8_t* ivs, int update, int threads) {
+    if (!count) return SG_OK;
+    if (!secrets) return fail(SG_E_ARG, "NULL argument%s");
+    if (!keys && !ivs && !update) return fail(SG_E_ARG, "nothing to do: no keys, no ivs and no update%s");
+    const uint32_t nt = (uint32_t)std::max(1, std::min<int>(threads, (int)std::min<uint32_t>(count, 1u << 16)));
+    auto work = [&](uint32_t t) {
+        for (uint32_t i = t; i < count; i += nt)
+            sg::traffic_one(secrets + 32ull * i, keys ? keys + 32ull * i : nullptr, ivs ? ivs + 12ull * i : nullptr,
+                            update != 0);
+    };
+    if (nt == 1) {
+        work(0);
+    } else {
+        std::vector<std::thread> pool;
+        for (uint32_t t = 0; t < nt; ++t) pool.emplace_back(work, t);
+        for (auto& th : pool) th.join();
+    }
     return SG_OK;
 }
 

@@ -1,7 +1,12 @@
 """TLS 1.2 key schedule (suruga src/cipher/prf.rs, src/client.rs:130-225) over
 the C ABI: ``hmac_sha256``, ``Prf`` and the per-connection key derivation that
 fills the key tables of the batch calls.  Host code (sg_keysched.cpp); no GPU
-needed, no Python fallback."""
+needed, no Python fallback.
+
+TLS 1.3 (RFC 8446 section 7.1 - 7.3) further below: ``hkdf_extract``,
+``hkdf_expand_label`` and ``tls13_traffic_keys`` on the host, and
+``tls13_traffic_keys_dev``, which derives (and with ``update`` ratchets) the rows
+of device tables in one launch (sg_hkdf.hip)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -91,3 +96,59 @@ def verify_data(master_secret: bytes, server: bool, handshake_hash: bytes) -> by
     out = (C.c_uint8 * 12)()
     N.check(N.load().sg_finished_verify_data(master_secret, int(server), handshake_hash, out))
     return bytes(out)
+
+
+# ---- TLS 1.3 (RFC 8446 section 7.1 - 7.3): HKDF with SHA-256, traffic keys, KeyUpdate ----
+def hkdf_extract(salt: bytes, ikm: bytes) -> bytes:
+    """RFC 5869 section 2.2 (``sg_hkdf_extract``); an empty or None salt is 32 zero bytes."""
+    salt = bytes(salt or b"")
+    out = (C.c_uint8 * 32)()
+    N.check(N.load().sg_hkdf_extract(salt or None, len(salt), bytes(ikm) or None, len(ikm), out))
+    return bytes(out)
+
+
+def hkdf_expand_label(secret: bytes, label: bytes, context: bytes, length: int) -> bytes:
+    """RFC 8446 section 7.1 (``sg_hkdf_expand_label``): ``label`` without the "tls13 " prefix."""
+    secret, label, context = bytes(secret), bytes(label), bytes(context)
+    if len(secret) != 32:
+        raise ValueError("the secret must be 32 bytes (SHA-256)")
+    out = (C.c_uint8 * max(length, 1))()
+    N.check(N.load().sg_hkdf_expand_label(secret, label or None, len(label), context or None, len(context), out,
+                                          length))
+    return bytes(out)[:length]
+
+
+def tls13_traffic_keys(secrets, update: bool = False, threads: int = 8):
+    """RFC 8446 section 7.3 for many connections (``sg_tls13_traffic_keys``).
+
+    secrets: uint8 [count, 32], the traffic secrets.  Returns (keys, ivs) as uint8
+    arrays [count, 32] and [count, 12], the tables of the TLS 1.3 batch calls.
+    With ``update`` every secret takes one KeyUpdate step first (section 7.2) and
+    the call returns (keys, ivs, next_secrets); the argument is left as it was."""
+    sec = np.array(secrets, dtype=np.uint8, order="C")  # a copy: the C call ratchets in place
+    if sec.ndim != 2 or sec.shape[1] != 32:
+        raise ValueError("secrets must be [count, 32]")
+    count = sec.shape[0]
+    keys = np.empty((count, 32), dtype=np.uint8)
+    ivs = np.empty((count, 12), dtype=np.uint8)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    N.check(N.load().sg_tls13_traffic_keys(count, p(sec), p(keys), p(ivs), int(bool(update)), threads))
+    return (keys, ivs, sec) if update else (keys, ivs)
+
+
+def tls13_traffic_keys_dev(secrets, keys=None, ivs=None, index=None, update: bool = False, stream=None) -> None:
+    """The same over device tensors in one launch (``sg_tls13_traffic_keys_dev``).
+
+    secrets: uint8 [rows, 32] on the device; keys [rows, 32] and ivs [rows, 12] (either may
+    be None) receive the rows' keys and write IVs; index: uint32 [count] row numbers, or
+    None for every row.  With ``update`` the selected secrets are ratcheted in place first.
+    Ordered on ``stream`` (None: torch's current stream) like a batch call."""
+    from .batch import _ptr, _stream_handle
+
+    k = N.SgTls13Keys()
+    k.rows = int(secrets.numel()) // 32
+    k.count = int(index.numel()) if index is not None else k.rows
+    k.flags = N.SG_TLS13_KEYS_UPDATE if update else 0
+    k.index, k.secrets, k.keys, k.ivs = _ptr(index), _ptr(secrets), _ptr(keys), _ptr(ivs)
+    k.stream = _stream_handle(stream)
+    N.check(N.load().sg_tls13_traffic_keys_dev(C.byref(k)))

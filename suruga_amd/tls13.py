@@ -10,9 +10,14 @@ The protected stream of a TLS 1.3 connection with TLS_CHACHA20_POLY1305_SHA256:
   complete record is opened and stripped of its inner type and padding;
   ``drain`` returns ``[(inner_type, content)]``.
 
-Key and write IV come from the caller's key schedule; a KeyUpdate is a new
-writer / reader.  The plaintext records of the handshake (outer types 20 - 22)
-are not part of the protected stream: the caller removes them first.
+Key and write IV come from the caller's key schedule, or the library derives
+them from the direction's traffic secret (``from_secret``, RFC 8446 section 7.3).
+A writer or reader made from a secret follows a KeyUpdate (section 4.6.3, 7.2):
+``Tls13Writer.send_key_update`` writes the message and ratchets, and
+``Tls13StreamReader.drain`` ratchets where it delivers one, inside one buffer
+too.  One made from key and IV cannot, and for it a KeyUpdate is a new writer /
+reader.  The plaintext records of the handshake (outer types 20 - 22) are not
+part of the protected stream: the caller removes them first.
 """
 from __future__ import annotations
 
@@ -24,6 +29,17 @@ from .tls import _ERR_KIND, _sink
 
 APPLICATION_DATA, ALERT, HANDSHAKE = 23, 21, 22
 RECORD_MAX_LEN = 1 << 14
+KEY_UPDATE = 24  # HandshakeType key_update (RFC 8446 section 4)
+
+
+def key_update_message(request_update: bool) -> bytes:
+    """The KeyUpdate handshake message: 18 00 00 01 || update_not_requested(0) / update_requested(1)."""
+    return bytes([KEY_UPDATE, 0, 0, 1, 1 if request_update else 0])
+
+
+def _is_key_update(inner_type: int, content: bytes) -> bool:
+    return inner_type == HANDSHAKE and len(content) == 5 and content[:4] == key_update_message(False)[:4] \
+        and content[4] in (0, 1)
 
 
 class _Tls13Ctx(_GpuCtx):
@@ -33,6 +49,20 @@ class _Tls13Ctx(_GpuCtx):
         super().__init__(key, device)
         _set_iv(self, iv)
 
+    @classmethod
+    def from_secret(cls, secret: bytes, device: int = 0) -> "_Tls13Ctx":
+        """Key and IV derived from the traffic secret, which the context keeps (``sg_ctx_set_traffic_secret``)."""
+        secret = bytes(secret)
+        if len(secret) != 32:
+            raise ValueError(f"the traffic secret must be 32 bytes, got {len(secret)}")
+        self = cls.__new__(cls)
+        _GpuCtx.__init__(self, bytes(N.SG_KEY_LEN), device)  # the derived key replaces this placeholder
+        N.check(self._lib.sg_ctx_set_traffic_secret(self._ptr, secret))
+        return self
+
+    def key_update(self) -> None:
+        N.check(self._lib.sg_ctx_key_update(self._ptr))
+
 
 class Tls13Writer:
     def __init__(self, sink, key: bytes, iv: bytes, device: int = 0):
@@ -40,6 +70,28 @@ class Tls13Writer:
         self._write = _sink(sink)
         self.ctx = _Tls13Ctx(key, iv, device)
         self.write_count = 0
+
+    @classmethod
+    def from_secret(cls, sink, secret: bytes, device: int = 0) -> "Tls13Writer":
+        """A writer under the keys of a traffic secret; it can ``key_update``."""
+        self = cls.__new__(cls)
+        self.writer = sink
+        self._write = _sink(sink)
+        self.ctx = _Tls13Ctx.from_secret(secret, device)
+        self.write_count = 0
+        return self
+
+    def key_update(self) -> None:
+        """The next generation's keys (``sg_ctx_key_update``); sequence numbers restart at 0
+        (RFC 8446 section 5.3).  Needs a writer made ``from_secret``."""
+        self.ctx.key_update()
+        self.write_count = 0
+
+    def send_key_update(self, request_update: bool = False) -> None:
+        """Writes the KeyUpdate message as a handshake record under the current keys, then
+        switches to the next generation (RFC 8446 section 4.6.3)."""
+        self.write_data(HANDSHAKE, key_update_message(request_update))
+        self.key_update()
 
     def write_data(self, inner_type: int, data: bytes) -> None:
         if not 0 < int(inner_type) < 256:
@@ -77,6 +129,30 @@ class Tls13StreamReader:
         self.max_records = max_records
         self.types = (C.c_uint8 * max_records)()
         self.lens = (C.c_uint32 * max_records)()
+        self._follows_key_updates = False
+        self.key_update_requested = False
+
+    @classmethod
+    def from_secret(cls, secret: bytes, device: int = 0, max_records: int = 1 << 16) -> "Tls13StreamReader":
+        """A reader under the keys of a traffic secret.  ``drain`` follows the peer's KeyUpdate
+        messages: where it delivers one it ratchets, restarts ``read_count`` at 0 and reads on.
+        ``key_update_requested`` turns True when one asked for an update in return (the
+        caller answers with ``Tls13Writer.send_key_update`` and resets it)."""
+        self = cls.__new__(cls)
+        self.ctx = _Tls13Ctx.from_secret(secret, device)
+        self.read_count = 0
+        self.buf = bytearray()
+        self.max_records = max_records
+        self.types = (C.c_uint8 * max_records)()
+        self.lens = (C.c_uint32 * max_records)()
+        self._follows_key_updates = True
+        self.key_update_requested = False
+        return self
+
+    def key_update(self) -> None:
+        """The reader's counterpart of ``Tls13Writer.key_update``."""
+        self.ctx.key_update()
+        self.read_count = 0
 
     def feed(self, data: bytes) -> None:
         self.buf += data
@@ -84,9 +160,28 @@ class Tls13StreamReader:
     def drain(self):
         """-> list of (inner_type, content).  Raises TlsError at the first failing
         record, after consuming the records before it (they are lost to the caller,
-        as a connection that saw a fatal alert condition is)."""
-        if not self.buf:
-            return []
+        as a connection that saw a fatal alert condition is).
+
+        A reader made ``from_secret`` changes keys where the last record a read
+        delivered is a KeyUpdate message: the records behind it, which that read
+        stopped at because they fail under the old key, are read again under the
+        next generation and appended."""
+        msgs = []
+        while self.buf:
+            got, error = self._read()
+            msgs += got
+            if self._follows_key_updates and got and _is_key_update(*got[-1]):
+                self.key_update()
+                self.key_update_requested |= got[-1][1][4] == 1
+                continue
+            if error != N.SG_OK:
+                kind, desc = _ERR_KIND.get(error, (TlsErrorKind.InternalError, f"status {error}"))
+                raise TlsError(kind, desc)
+            break  # what is left is an incomplete record
+        return msgs
+
+    def _read(self):
+        """One ``sg_read_records_tls13`` over the buffer: (delivered records, error)."""
         lib = N.load()
         src = (C.c_uint8 * len(self.buf)).from_buffer(self.buf)
         out = (C.c_uint8 * max(len(self.buf), 1))()
@@ -101,10 +196,7 @@ class Tls13StreamReader:
             pos += n
         del self.buf[:res.consumed]
         self.read_count += res.records
-        if res.error != N.SG_OK:
-            kind, desc = _ERR_KIND.get(res.error, (TlsErrorKind.InternalError, f"status {res.error}"))
-            raise TlsError(kind, desc)
-        return msgs
+        return msgs, res.error
 
     def close(self) -> None:
         self.ctx.close()
