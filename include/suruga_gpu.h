@@ -333,6 +333,96 @@ typedef struct sg_tls13_seal_opts {
 } sg_tls13_seal_opts;           /* 16 bytes */
 int sg_seal_batch_tls13_ex(const sg_batch* b, const sg_batch_tls13* x, const sg_tls13_seal_opts* o);
 
+/* ---- QUIC packet protection batch (RFC 9001 section 5.3 - 5.4) ----------------
+ * AEAD_CHACHA20_POLY1305 packet protection and ChaCha20 header protection of many
+ * packets in one launch (sg_quic.hip).  A packet differs from a record: its
+ * additional data is its own header, in front of the payload and of its own length;
+ * the nonce is iv XOR the packet number, which on receive has to be recovered from 1
+ * to 4 truncated bytes (RFC 9000 appendix A.3); and the first byte and the packet
+ * number bytes are masked with a ChaCha20 block under a third key (section 5.4.4).
+ *
+ * Packet i lies at in + in_off_i (off_i = off ? off[i] : stride * i) and has len_i =
+ * len ? len[i] : uniform_len bytes; pn_off_i = pn_off ? pn_off[i] : uniform_pn_off is
+ * the offset of its packet number field, 1..SG_QUIC_MAX_PN_OFF.  Parsing a datagram
+ * (coalesced packets, the long header's variable-length fields) is the caller's.
+ * Any alignment of `in`, `out` and the offsets; `in` and `out` of a call must not
+ * overlap (not checked; the result is undefined where they do).
+ *
+ * Rows.  k = min(key_index ? key_index[i] : 0, rows - 1).  Without
+ * SG_QUIC_KEY_PHASE rows = num_keys and key, IV and header protection key are row k
+ * of their tables.  With it rows = num_keys / 2: hp_keys has one row per connection
+ * (the HP key does not change at a key update, RFC 9001 section 6), row k, and key
+ * and IV are row 2 k + phase, phase = bit 2 (0x04) of the unprotected first byte of
+ * a short-header packet (bit 7 clear) and 0 for a long-header packet.
+ *
+ * Seal.  The input is header || payload, len_i bytes.  pn_len = (first byte & 3) + 1,
+ * hdr_len = pn_off_i + pn_len; the packet number field is written by the call, the low
+ * pn_len bytes of pn[i], big-endian, whatever the input holds there.  AD = that header,
+ * nonce = iv XOR (00 00 00 00 || be64(pn[i])).  The output is len_i + 16 bytes:
+ * protected header || ciphertext || tag.  Header protection: sample = the 16 output
+ * bytes at pn_off_i + 4; mask = the first 5 bytes of the ChaCha20 block under the HP
+ * key with counter le32(sample[0..4)) and nonce sample[4..16); first byte ^= mask[0] &
+ * 0x1f (short header) or & 0x0f (long header), packet number bytes ^= mask[1..].
+ * Status SG_OK; SG_E_SHORT, nothing written, where len_i < hdr_len or pn_len + payload
+ * length < 4 (no full sample: the sender has to pad, section 5.4.2).  max_len is at
+ * most SG_QUIC_MAX_PACKET_LEN - 16.
+ *
+ * Open.  The input is a protected packet of len_i bytes; SG_E_SHORT, nothing written,
+ * where len_i < pn_off_i + 20.  The mask comes off the first byte (bit 7, not masked,
+ * tells the form), pn_len is read, the packet number bytes are unmasked and the full
+ * number is decoded against pn[i] as expected_pn (largest received + 1).  `out`
+ * receives len_i - 16 bytes, unprotected header || plaintext, pn_out[i] the number, and
+ * status[i] SG_OK or SG_E_BAD_MAC.  The decryption always runs; on SG_E_BAD_MAC all
+ * len_i - 16 output bytes are zero and pn_out[i] is 0, unless SG_QUIC_KEEP_FAILED is
+ * set: nothing derived from an unauthenticated packet leaves the call.
+ *
+ * Both.  A packet with len_i > max_len (len != NULL; with len == NULL the bound is
+ * uniform_len itself) gets SG_STATUS_SKIPPED and is untouched; the call still returns
+ * SG_OK and reads nothing back.  A per-packet pn_off outside 1..251 gives SG_E_SHORT.
+ * One launch, no workspace, no host read-back: the call is capturable.
+ * count == 0 returns SG_OK and launches nothing.
+ * SG_E_ARG before any GPU work: NULL b, unknown flags, NULL keys / ivs / hp_keys /
+ * status / in / out / pn, pn_out NULL on open, ivs or a per-packet array misaligned
+ * (4 bytes; 8 for pn, pn_out, in_off, out_off), uniform_pn_off (pn_off == NULL) outside
+ * 1..251, the length bound above SG_QUIC_MAX_PACKET_LEN (seal: - 16), num_keys zero, or
+ * odd under SG_QUIC_KEY_PHASE. */
+#define SG_QUIC_MAX_PACKET_LEN 16384u  /* protected packet, tag included */
+#define SG_QUIC_MAX_PN_OFF       251u  /* so that the header (AD) is <= 255 = SG_MAX_AD_LEN */
+#define SG_QUIC_KEY_PHASE        0x1u
+#define SG_QUIC_KEEP_FAILED      0x2u
+
+typedef struct sg_quic_batch {
+    uint32_t        count, flags;
+    const uint8_t*  keys;       /* device [num_keys][32]                                       */
+    const uint8_t*  ivs;        /* device [num_keys][12], 4-byte aligned                       */
+    const uint8_t*  hp_keys;    /* device [rows][32] (above)                                   */
+    const uint32_t* key_index;  /* device, or NULL: 0                                          */
+    const uint64_t* pn;         /* device. seal: the packet number; open: the expected number  */
+    uint64_t*       pn_out;     /* open: device, the decoded packet number; seal: not read     */
+    const uint32_t* pn_off;     /* device, or NULL: uniform_pn_off                             */
+    uint32_t        num_keys;
+    uint32_t        uniform_pn_off;
+    const uint8_t*  in;
+    const uint64_t* in_off;
+    uint64_t        in_stride;
+    uint8_t*        out;
+    const uint64_t* out_off;
+    uint64_t        out_stride;
+    const uint32_t* len;
+    uint32_t        uniform_len;
+    uint32_t        max_len;
+    uint8_t*        status;     /* device, count bytes, required for seal and open             */
+    void*           stream;     /* as sg_batch.stream: non-NULL asynchronous, NULL waits       */
+} sg_quic_batch;                /* 152 bytes */
+int sg_seal_batch_quic(const sg_quic_batch* b);
+int sg_open_batch_quic(const sg_quic_batch* b);
+
+/* RFC 9000 appendix A.3 on the host (no GPU), what the open kernel runs per packet:
+ * the full packet number of `truncated` (pn_len bytes, 1..4) given expected_pn =
+ * largest received + 1.  pn_len outside 1..4 is taken into that range and truncated is
+ * cut to 8 * pn_len bits. */
+uint64_t sg_quic_decode_pn(uint64_t expected_pn, uint32_t truncated, uint32_t pn_len);
+
 /* ---- long messages: any data and AD length, one message over the whole chip
  * Encryptor::encrypt / Decryptor::decrypt take data and additional data of any
  * length (cipher/mod.rs:22-32, chacha20_poly1305.rs:19-94).  sg_seal, sg_open
@@ -796,6 +886,18 @@ int sg_hkdf_expand_label(const uint8_t secret[32], const char* label, size_t lab
  *   ivs[i]   = Expand-Label(secrets[i], "iv",  "", 12)      [count][12], may be NULL
  * count == 0 is SG_OK; a call that would do nothing (no keys, no ivs, no update) is SG_E_ARG. */
 int sg_tls13_traffic_keys(uint32_t count, uint8_t* secrets, uint8_t* keys, uint8_t* ivs, int update, int threads);
+
+/* QUIC packet protection keys (RFC 9001 section 5.1, 6.1) for `count` connections, with
+ * the shape and rules of the call above:
+ *   update != 0:  secrets[i] <- Expand-Label(secrets[i], "quic ku", "", 32)   (in place, first)
+ *   keys[i] = Expand-Label(secrets[i], "quic key", "", 32)   [count][32], may be NULL
+ *   ivs[i]  = Expand-Label(secrets[i], "quic iv",  "", 12)   [count][12], may be NULL
+ *   hps[i]  = Expand-Label(secrets[i], "quic hp",  "", 32)   [count][32], may be NULL
+ * The header protection key does not change at a key update (section 6): a caller that
+ * updates passes hps == NULL.  count == 0 is SG_OK; a call that would do nothing is
+ * SG_E_ARG.  Host memory; the tables feed sg_quic_batch. */
+int sg_quic_packet_keys(uint32_t count, uint8_t* secrets, uint8_t* keys, uint8_t* ivs, uint8_t* hps, int update,
+                        int threads);
 
 /* The same on the device: one launch turns a device table of traffic secrets
  * into the keys / ivs tables of the batch calls, in place in HBM (sg_hkdf.hip:

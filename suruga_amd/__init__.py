@@ -10,6 +10,8 @@ Layout:
                              in the draft construction or (rfc8439=True) RFC 8439
   suruga_amd/tls13.py        TLS 1.3 protected stream (Tls13Writer / Tls13StreamReader) over
                              sg_write_records_tls13 / sg_read_records_tls13
+  suruga_amd/quic.py         QUIC packet protection of a device-resident batch (RFC 9001):
+                             AEAD and header protection, seal_quic / open_quic
   suruga_amd/_native.py      ctypes binding of libsuruga_gpu.so
 
 The HIP library is the only compute path; importing the cipher classes works
@@ -18,10 +20,13 @@ without a GPU, calling them needs one (and fails loudly otherwise).
 from . import _native
 from .cipher import (Aead, ChaCha20Poly1305, ChaCha20Poly1305Decryptor, ChaCha20Poly1305Encryptor,
                      ChaCha20Poly1305Rfc8439, CipherSuite, Decryptor, Encryptor, TlsError, TlsErrorKind)
+from .keysched import quic_packet_keys
+from .quic import QuicBatch, decode_pn, open_quic, seal_quic
 
 __all__ = [
     "Aead", "ChaCha20Poly1305", "ChaCha20Poly1305Decryptor", "ChaCha20Poly1305Encryptor", "ChaCha20Poly1305Rfc8439",
     "CipherSuite", "Decryptor", "Encryptor", "TlsError", "TlsErrorKind", "load_native",
+    "QuicBatch", "seal_quic", "open_quic", "decode_pn", "quic_packet_keys",
 ]
 
 

@@ -57,6 +57,7 @@ EXPORTS = [
     "sg_msg_plan_for", "sg_msg_plan_for_flags", "sg_set_msg_groups",
     "sg_msg_batch_workspace_size", "sg_seal_msg_batch", "sg_open_msg_batch", "sg_msg_batch_plan_for",
     "sg_msg_batch_plan_for_flags",
+    "sg_seal_batch_quic", "sg_open_batch_quic", "sg_quic_decode_pn", "sg_quic_packet_keys",
 ]
 SG_MSG_BATCH_MAX_COUNT = 1 << 20
 SG_MSG_MAX_GROUPS = 1024
@@ -126,6 +127,41 @@ class SgTls13Keys(C.Structure):
     _fields_ = [("count", C.c_uint32), ("flags", C.c_uint32), ("rows", C.c_uint32), ("_pad", C.c_uint32),
                 ("index", C.c_void_p), ("secrets", C.c_void_p), ("keys", C.c_void_p), ("ivs", C.c_void_p),
                 ("stream", C.c_void_p)]
+
+
+SG_QUIC_MAX_PACKET_LEN = 16384
+SG_QUIC_MAX_PN_OFF = 251
+SG_QUIC_KEY_PHASE = 0x1
+SG_QUIC_KEEP_FAILED = 0x2
+
+
+class SgQuicBatch(C.Structure):
+    """Mirror of ``struct sg_quic_batch``."""
+
+    _fields_ = [
+        ("count", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("keys", C.c_void_p),
+        ("ivs", C.c_void_p),
+        ("hp_keys", C.c_void_p),
+        ("key_index", C.c_void_p),
+        ("pn", C.c_void_p),
+        ("pn_out", C.c_void_p),
+        ("pn_off", C.c_void_p),
+        ("num_keys", C.c_uint32),
+        ("uniform_pn_off", C.c_uint32),
+        ("in_", C.c_void_p),
+        ("in_off", C.c_void_p),
+        ("in_stride", C.c_uint64),
+        ("out", C.c_void_p),
+        ("out_off", C.c_void_p),
+        ("out_stride", C.c_uint64),
+        ("len", C.c_void_p),
+        ("uniform_len", C.c_uint32),
+        ("max_len", C.c_uint32),
+        ("status", C.c_void_p),
+        ("stream", C.c_void_p),
+    ]
 
 
 class SgBatchRoutes(C.Structure):
@@ -387,6 +423,13 @@ def _declare(lib: C.CDLL) -> None:
     lib.sg_tls13_traffic_keys.argtypes = [C.c_uint32, vp, vp, vp, C.c_int, C.c_int]
     lib.sg_tls13_traffic_keys_dev.restype = C.c_int
     lib.sg_tls13_traffic_keys_dev.argtypes = [C.POINTER(SgTls13Keys)]
+    for f in (lib.sg_seal_batch_quic, lib.sg_open_batch_quic):
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(SgQuicBatch)]
+    lib.sg_quic_decode_pn.restype = C.c_uint64
+    lib.sg_quic_decode_pn.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
+    lib.sg_quic_packet_keys.restype = C.c_int
+    lib.sg_quic_packet_keys.argtypes = [C.c_uint32, vp, vp, vp, vp, C.c_int, C.c_int]
     lib.sg_ctx_set_traffic_secret.restype = C.c_int
     lib.sg_ctx_set_traffic_secret.argtypes = [C.c_void_p, C.c_char_p]
     lib.sg_ctx_key_update.restype = C.c_int

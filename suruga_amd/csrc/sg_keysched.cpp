@@ -348,4 +348,33 @@ int sg_tls13_traffic_keys(uint32_t count, uint8_t* secrets, uint8_t* keys, uint8
     return SG_OK;
 }
 
+int sg_quic_packet_keys(uint32_t count, uint8_t* secrets, uint8_t* keys, uint8_t* ivs, uint8_t* hps, int update,
+                        int threads) {
+    if (!count) return SG_OK;
+    if (!secrets) return fail(SG_E_ARG, "NULL argument%s");
+    if (!keys && !ivs && !hps && !update) return fail(SG_E_ARG, "nothing to do: no keys, no ivs, no hps and no update%s");
+    const uint32_t nt = (uint32_t)std::max(1, std::min<int>(threads, (int)std::min<uint32_t>(count, 1u << 16)));
+    auto work = [&](uint32_t t) {
+        for (uint32_t i = t; i < count; i += nt) {
+            uint8_t* s = secrets + 32ull * i;
+            if (update) {  // RFC 9001 section 6.1: the next generation's secret
+                uint8_t next[32];
+                (void)sg_hkdf_expand_label(s, "quic ku", 7, nullptr, 0, next, 32);
+                std::memcpy(s, next, 32);
+            }
+            if (keys) (void)sg_hkdf_expand_label(s, "quic key", 8, nullptr, 0, keys + 32ull * i, 32);
+            if (ivs) (void)sg_hkdf_expand_label(s, "quic iv", 7, nullptr, 0, ivs + 12ull * i, 12);
+            if (hps) (void)sg_hkdf_expand_label(s, "quic hp", 7, nullptr, 0, hps + 32ull * i, 32);
+        }
+    };
+    if (nt == 1) {
+        work(0);
+    } else {
+        std::vector<std::thread> pool;
+        for (uint32_t t = 0; t < nt; ++t) pool.emplace_back(work, t);
+        for (auto& th : pool) th.join();
+    }
+    return SG_OK;
+}
+
 }  // extern "C"

@@ -6,7 +6,8 @@ needed, no Python fallback.
 TLS 1.3 (RFC 8446 section 7.1 - 7.3) further below: ``hkdf_extract``,
 ``hkdf_expand_label`` and ``tls13_traffic_keys`` on the host, and
 ``tls13_traffic_keys_dev``, which derives (and with ``update`` ratchets) the rows
-of device tables in one launch (sg_hkdf.hip)."""
+of device tables in one launch (sg_hkdf.hip).  ``quic_packet_keys`` at the end:
+the packet protection keys of RFC 9001 section 5.1 and 6.1, on the host."""
 from __future__ import annotations
 
 import ctypes as C
@@ -152,3 +153,23 @@ def tls13_traffic_keys_dev(secrets, keys=None, ivs=None, index=None, update: boo
     k.index, k.secrets, k.keys, k.ivs = _ptr(index), _ptr(secrets), _ptr(keys), _ptr(ivs)
     k.stream = _stream_handle(stream)
     N.check(N.load().sg_tls13_traffic_keys_dev(C.byref(k)))
+
+
+def quic_packet_keys(secrets, update: bool = False, threads: int = 8):
+    """RFC 9001 section 5.1 for many connections (``sg_quic_packet_keys``).
+
+    secrets: uint8 [count, 32], the packet protection secrets.  Returns (keys, ivs, hps) as
+    uint8 arrays [count, 32], [count, 12] and [count, 32], the tables of ``quic.QuicBatch``.
+    With ``update`` every secret takes one key update step first ("quic ku", section 6.1) and
+    the call returns (keys, ivs, next_secrets): the header protection keys do not change at
+    a key update.  The argument is left as it was."""
+    sec = np.array(secrets, dtype=np.uint8, order="C")  # a copy: the C call ratchets in place
+    if sec.ndim != 2 or sec.shape[1] != 32:
+        raise ValueError("secrets must be [count, 32]")
+    count = sec.shape[0]
+    keys = np.empty((count, 32), dtype=np.uint8)
+    ivs = np.empty((count, 12), dtype=np.uint8)
+    hps = None if update else np.empty((count, 32), dtype=np.uint8)
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    N.check(N.load().sg_quic_packet_keys(count, p(sec), p(keys), p(ivs), p(hps), int(bool(update)), threads))
+    return (keys, ivs, sec) if update else (keys, ivs, hps)
