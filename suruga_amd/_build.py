@@ -23,8 +23,8 @@ LIB = PKG / "libsuruga_gpu.so"
 ORACLE_DIR = ROOT / "oracle"
 ORACLE_LIB = ORACLE_DIR / "liboracle.so"
 
-HIP_SOURCES = [CSRC / "sg_kernels.hip", CSRC / "sg_wpr.hip", CSRC / "sg_pack.hip", CSRC / "sg_plumb.hip",
-               CSRC / "sg_dispatch.cpp", CSRC / "sg_capi.cpp", CSRC / "sg_record.cpp",
+HIP_SOURCES = [CSRC / "sg_kernels.hip", CSRC / "sg_wpr.hip", CSRC / "sg_wpr_keying.hip", CSRC / "sg_pack.hip",
+               CSRC / "sg_plumb.hip", CSRC / "sg_dispatch.cpp", CSRC / "sg_capi.cpp", CSRC / "sg_record.cpp",
                CSRC / "sg_keysched.cpp", CSRC / "sg_wire.cpp", CSRC / "sg_copy_pool.cpp",
                CSRC / "sg_msg.hip", CSRC / "sg_msg_capi.cpp", CSRC / "sg_msg_plan.cpp",
                CSRC / "sg_msg_batch.hip", CSRC / "sg_msg_batch_capi.cpp", CSRC / "sg_hkdf.hip",
@@ -32,7 +32,7 @@ HIP_SOURCES = [CSRC / "sg_kernels.hip", CSRC / "sg_wpr.hip", CSRC / "sg_pack.hip
 HIP_DEPS = HIP_SOURCES + [CSRC / "sg_internal.h", CSRC / "sg_device.h", CSRC / "sg_host.h", CSRC / "sg_err.h",
                           CSRC / "sg_wire.h", CSRC / "sg_copy_pool.h", CSRC / "sg_env.h", CSRC / "sg_chacha_grp.inc",
                           CSRC / "sg_msg_plan.h", CSRC / "sg_msg_device.h", CSRC / "sg_layout.h",
-                          CSRC / "sg_hkdf.h", CSRC / "sg_quic.h",
+                          CSRC / "sg_wpr_layout.h", CSRC / "sg_hkdf.h", CSRC / "sg_quic.h",
                           ROOT / "include" / "suruga_gpu.h"]
 ORACLE_SOURCES = [ORACLE_DIR / "suruga_oracle.c"]
 ORACLE_DEPS = ORACLE_SOURCES + [ORACLE_DIR / "suruga_oracle.h", ORACLE_DIR / "so_pool.h"]

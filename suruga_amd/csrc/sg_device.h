@@ -1,6 +1,6 @@
 // sg_device.h -- device-side building blocks shared by the gfx950 kernels
-// (sg_kernels.hip: size-class kernels, keying, bucketing; sg_wpr.hip: the
-// wave-per-record kernel for 4-16 KiB records; sg_pack.hip: the packed small
+// (sg_kernels.hip: size-class kernels, keying, bucketing; sg_wpr.hip and
+// sg_wpr_keying.hip: the wave-per-record kernel for 4-16 KiB records and its keying; sg_pack.hip: the packed small
 // records of mixed batches; sg_msg.hip: long messages; sg_plumb.hip: scrub).
 // Not part of the public ABI.
 //

@@ -2,9 +2,12 @@
 // 16 KiB one (launch_aead, sg_internal.h): a uniform batch is keyed and
 // launched directly; a mixed one is bucketed on the device, its populations
 // are read back into a pooled pinned buffer, and its lists run on up to three
-// streams.  No device code: every kernel is reached through a launch_*
-// function of sg_kernels.hip, sg_wpr.hip or sg_pack.hip.
+// streams.  Also the host's other decisions about the record kernels: the CU
+// count that sizes the persistent grids and the two environment switches of the
+// wave-per-record route.  No device code: every kernel is reached through a
+// launch_* function of sg_kernels.hip, sg_wpr.hip, sg_wpr_keying.hip or sg_pack.hip.
 #include "sg_internal.h"
+#include "sg_env.h"
 
 #include <mutex>
 #include <utility>
@@ -12,6 +15,8 @@
 
 namespace sg {
 namespace {
+
+int g_cus[64];  // CUs per device ordinal (0: not read yet)
 
 // Pinned host buffers for the population readback of mixed batches, shared by
 // every calling thread (a thread_local buffer per caller leaked one pinned
@@ -163,6 +168,25 @@ void routes_reset() {
 void routes_get(uint32_t out[kRouteWords]) {
     for (uint32_t i = 0; i < kRouteWords; ++i) out[i] = t_routes[i];
 }
+
+hipError_t device_cus(int* cus) {
+    int dev = 0;
+    hipError_t e;
+    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
+    *cus = dev >= 0 && dev < 64 ? __atomic_load_n(&g_cus[dev], __ATOMIC_RELAXED) : 0;
+    if (*cus <= 0) {
+        if ((e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) __atomic_store_n(&g_cus[dev], *cus, __ATOMIC_RELAXED);
+    }
+    return hipSuccess;
+}
+
+static EnvSwitch g_wpr{"SG_LOCKSTEP"};
+bool wpr_enabled() { return g_wpr.on(); }
+int set_wpr(int enable) { return g_wpr.set(enable); }
+static EnvSwitch g_tls13_buckets{"SG_TLS13_BUCKETS", -1, false};  // off unless set
+bool tls13_buckets_enabled() { return g_tls13_buckets.on(); }
+int set_tls13_buckets(int enable) { return g_tls13_buckets.set(enable); }
 
 hipError_t launch_aead(const KParams& p, bool open, uint32_t max_n, bool uniform, hipStream_t s, uint32_t* over,
                        hipEvent_t ev_mid) {

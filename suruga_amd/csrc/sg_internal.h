@@ -1,5 +1,5 @@
 // sg_internal.h -- shared between the HIP kernel files (sg_kernels.hip,
-// sg_wpr.hip, sg_pack.hip, sg_plumb.hip), the mixed-batch dispatcher
+// sg_wpr.hip, sg_wpr_keying.hip, sg_pack.hip, sg_plumb.hip), the mixed-batch dispatcher
 // (sg_dispatch.cpp) and the C-ABI host layer (sg_capi.cpp): the workspace and
 // keying-record layouts, the kernel parameters and every launch_* function.
 // Not part of the public ABI.
@@ -33,7 +33,7 @@ __host__ __device__ constexpr uint32_t key_used_words(uint32_t PL) {
 }
 static_assert(key_used_words(64) == kKeyRecWords, "keying record layout");
 
-// Keying record of the wave-per-record kernel (sg_wpr.hip), u32 words; F26
+// Keying record of the wave-per-record kernel (sg_wpr_keying.hip writes it, sg_wpr.hip reads it), u32 words; F26
 // entries are 5 radix-2^26 limbs.  With delta = 0/1 from the geometry
 // (wpr_geom), R = r^4 and T = r^128:
 //   s[4]                                    second half of keystream block 0
@@ -77,7 +77,7 @@ struct KParams {
     uint64_t out_stride;
     const uint32_t* len;
     uint8_t* status;
-    uint32_t* ws;            // count * kKeyRecWords (kWprRecWords for sg_wpr.hip) keying records
+    uint32_t* ws;            // count * kKeyRecWords (kWprRecWords for sg_wpr_keying.hip) keying records
     uint32_t uniform_len;
     uint32_t count;
     uint32_t ad_len;         // explicit mode
@@ -191,7 +191,7 @@ __host__ __device__ inline uint32_t* ws_tail(uint32_t* ws, uint32_t count) { ret
 constexpr uint32_t kTailOver = kNumLists;           // records longer than max_n
 constexpr uint32_t kTailCtr = kNumLists + 1u;       // + b: group counter of wpr bucket b, + kWprBuckets: uniform C1 launch
 constexpr uint32_t kTailPackCtr = kTailCtr + kWprBuckets + 1u;  // run counter of the packed launch
-hipError_t device_cus(int* cus);  // CUs of the current device (cached)
+hipError_t device_cus(int* cus);  // CUs of the current device (cached; sg_dispatch.cpp)
 
 // A wave-per-record bucket launch (mixed batch) or the uniform launch (list NULL).
 struct WprList {
@@ -228,7 +228,7 @@ hipError_t launch_class(uint32_t c, const KParams& q, bool open, const uint32_t*
 
 inline hipError_t mark(hipEvent_t ev, hipStream_t s) { return ev ? hipEventRecord(ev, s) : hipSuccess; }
 
-bool wpr_enabled();  // sg_set_lockstep / SG_LOCKSTEP environment switch
+bool wpr_enabled();  // sg_set_lockstep / SG_LOCKSTEP environment switch (sg_dispatch.cpp, like the next)
 int set_wpr(int enable);
 // sg_set_tls13_buckets / SG_TLS13_BUCKETS (off by default): padded TLS 1.3 records of
 // 4-16 KiB inner length take the J = 2..4 buckets.  A host decision only (launch_batch).
@@ -236,8 +236,10 @@ bool tls13_buckets_enabled();
 int set_tls13_buckets(int enable);
 // keying pre-pass + record kernel; ev_mid (may be NULL) is recorded between them
 hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_mid);
+// the keying pre-pass of a uniform launch alone (sg_wpr_keying.hip)
+hipError_t launch_wpr_keying(const KParams& p, bool open, const WprList& wl, hipStream_t s);
 // wave-per-record buckets of a mixed batch (wl[b]: J = kWprMinJ + b chunks):
-// one keying launch for every bucket, then the record kernel of one bucket
+// one keying launch for every bucket (sg_wpr_keying.hip), then the record kernel of one bucket
 hipError_t launch_wpr_keying_lists(const KParams& p, bool open, const WprList* wl, hipStream_t s);
 hipError_t launch_wpr_list(const KParams& p, bool open, uint32_t J, const WprList& wl, hipStream_t s);
 const char* wpr_kernel_config();

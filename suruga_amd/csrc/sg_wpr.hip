@@ -23,48 +23,18 @@
 //     operands of four v_mfma_i32_32x32x32_i8 per iteration, issued during the
 //     next iteration's rounds (see "MAC" below).
 //
-// MAC.  The reference evaluates h = sum_b v_b r^(B - b) over the 16-byte
-// blocks of ad || le64(|ad|) || ct || le64(|ct|) (chacha20_poly1305.rs:19-42,
-// poly1305.rs:207-228).  Ciphertext chunk m (bytes 16 m .. 16 m + 15) starts
-// at stream offset o + 16 m, o = |ad| + 8 = 16 beta + sigma, so its byte a' has
-// weight 2^(8 (sigma + a')) r^(E(m) + 1) when sigma + a' < 16 and
-// 2^(8 (sigma + a' - 16)) r^E(m) otherwise, with E(m) = B - beta - 1 - m.
-// Chunk m = 256 j + 128 h + 4 q + i (iteration j, lane 32 h + q, chunk i of
-// the lane's block) factors as E(m) = 4 (31 - q) + e(j, h, i),
-// e = 128 (1 - h) + 256 (3 - j) + (4 - i) + delta.  Each MFMA step (j, i) then
-// computes D[c][q] += sum_{h, a'} T[c][(h, a')] (byte - 128), where column q
-// is the lane's chunk and row c a base-256 digit position: T holds the signed
-// digits of r^(e + 1) and r^e, shifted by sigma + a' (a Toeplitz band).  The
-// eight powers per step, r^(128 k + 1 + delta + u) (k = 0..7, u = 0..4), are
-// built once per record as 48-byte digit lines in LDS; a lane reads its
-// 16-byte T fragment as two windows of two adjacent lines (aligned dwords
-// shifted with v_alignbyte).  |D| <
-// 2^23; the record's first MFMA starts from a zero accumulator and the
-// assembly adds a seed of 2^24 per entry (v_mad_i64_i32 on the signed
-// entries), so every 64-bit word is positive.  At the end each lane assembles
-// its 16 entries exactly, X = sum_r (D[c_r][q] + 2^24) 2^(8 c_r), reduces it
-// mod 2^130 - 5, multiplies by
-// W = r^(4 (31 - q)) (times 2^32 for the upper half-wave) and a DPP sum adds
-// the 64 terms.  The keying kernel supplies the per-record constant ctot:
-// the AD / length blocks, the pad bits, the i8 bias and the seed.  Every step
-// is exact arithmetic mod p, so tags equal the reference's bit for bit
-// (tests/test_wpr_mac_model.py pins this decomposition against the CPU
-// restatement of poly1305.rs).
+// MAC: the decomposition of the tag into the MFMA steps, the per-lane assembly,
+// the W scaling and the keying kernel's constant term ctot is written out in
+// sg_wpr_keying.hip; the steps of it that run here are named where they stand
+// (digit lines, mac_load / mac_frag / mac_mfma, lane term, wave sum).
 //
-// Construction::kRfc8439 (the uniform launch and the J = 2..4 buckets; sg_*_batch_rfc8439): in the RFC
-// 8439 stream ad || 0.. || ct || 0.. || le64(|ad|) || le64(n) the ciphertext
-// starts on a block boundary, which is the sigma = 0 case above for every AD
-// length, so the MFMA body is the draft's.  The keying kernel's constant term
-// changes (wpr_geom: o = 16 ceil(|ad| / 16), B = beta + m + 1, rem = 16,
-// delta = 0; the prefix is ad and its zero padding, the suffix the one full
-// length block at weight r), block 0 and the rounds take the nonce's first word
+// Construction::kRfc8439 (the uniform launch and the J = 2..4 buckets): the
+// ciphertext starts a MAC block (sigma = 0), so the MFMA body is the draft's;
+// block 0 and the rounds take the nonce's first word
 // in state word 13 (u[13] on the SALU, x[13] + n13 in the feed-forward), and
 // the TLS nonce is the key's write IV XOR the byte-swapped sequence number (RFC
-// 7905), on the SALU.  tests/test_wpr_mac_model_rfc8439.py pins the constant term.
-// Bucket records (LIST) carry the nonce's first word in descriptor word 9; their
-// constant term is wpr_geom<kRfc8439>(13, n) of the right-aligned record, with
-// the S(c) pieces of the draft's bucket keying (they depend on n / 64 alone) and
-// the same single length block (tests/test_wpr_bucket_model_rfc8439.py).
+// 7905), on the SALU.
+// Bucket records (LIST) carry the nonce's first word in descriptor word 9.
 //
 // TLS 1.3 (T13 / TLS13, sg_*_batch_tls13, uniform launches): a full record is 2^14
 // content bytes and the inner type byte.  The record kernel runs the 2^14 bytes as
@@ -74,19 +44,13 @@
 //
 // TLS 1.3 buckets (LIST with T13 / TLS13; sg_set_tls13_buckets, off by default): a
 // padded record whose inner plaintext content || type || zeros is n = 64 k' bytes,
-// 4 KiB < n <= 16 KiB.  Its MAC stream AD(5) || 0^11 || ct || le64(5) || le64(n) is
-// the RFC bucket record's all-full-block stream behind a 5-byte AD, and
-// wpr_geom<kRfc8439>(5, n) is the 13-byte AD's, so the keying differs in the prefix
-// block 17 03 03 be16(n + 16) and the length block alone
-// (tests/test_wpr_bucket_model_tls13.py); the descriptor's words 10 and 11 carry the
-// content length and the inner type.  Open runs the RFC bucket kernel as it is on
-// those tables; seal is the record kernel's TLS13 bucket form, which loads the
+// 4 KiB < n <= 16 KiB.  Open runs the RFC bucket kernel as it is on
+// the TLS 1.3 keying's tables; seal is the record kernel's TLS13 bucket form, which loads the
 // units that hold content and patches each chunk that reaches the content's end in
 // LDS (see the kernel).
-#include "sg_internal.h"
+#include "sg_wpr_layout.h"
 #include "sg_device.h"
 #include "sg_chacha_grp.inc"  // grouped ChaCha20 double round (tools/gen_chacha_grp.py --product)
-#include "sg_env.h"
 
 #include <stdint.h>
 
@@ -97,346 +61,6 @@ using namespace dev;
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
-
-constexpr uint32_t kWprWaves = 8;           // records per 512-thread workgroup
-constexpr uint32_t kWprChunk = 4096;        // bytes per wave iteration
-constexpr uint32_t kWprLines = 40;          // T digit lines per record
-constexpr uint32_t kWprLineBytes = 48;
-constexpr uint32_t kWprLinesOff = 2 * kWprChunk;  // two chunk buffers, then the T lines
-// after the lines (offsets from the line area): 16 zero bytes read past the
-// last line, the next record's descriptor (bucket launches), the received tag
-constexpr uint32_t kWprDescOff = kWprLines * kWprLineBytes + 16;
-constexpr uint32_t kWprRxOff = kWprDescOff + 48;
-constexpr uint32_t kWprWaveLds = 2 * kWprChunk + kWprRxOff + 16;  // 10192
-// eight waves and the workgroup's next-group slot: two workgroups per CU
-constexpr uint32_t kWprWgLds = kWprWaves * kWprWaveLds + 16;
-static_assert(2 * kWprWgLds <= 160 * 1024, "two workgroups per CU");
-static_assert(kWprDescWords * 4 <= 48, "descriptor slot");
-constexpr uint32_t kWprKeyThreads = 64;
-
-// Geometry of the MAC stream ad || le64(|ad|) || ct || le64(n), n a multiple
-// of 16 (C1: n = 2^14).  A record of n < 2^14 bytes runs right-aligned in the
-// 2^14-byte frame of the kernel (virtual offset 2^14 - n): shifting the
-// ciphertext by a multiple of 16 shifts its MAC block indices and the block
-// count B alike, so every ciphertext byte keeps its weight r^(B - b) 2^(8 k)
-// and the MFMA part of the MAC is the same for every n; only the constant term
-// (AD, length and pad blocks, bias) depends on n.
-struct WprGeom {
-    uint32_t o, sigma, beta, B, rem, delta, m;
-};
-// RFC 8439 (ad || 0.. || ct || 0.. || le64(|ad|) || le64(n)): the ciphertext
-// starts on a block boundary, o = 16 ceil(adlen / 16), sigma = 0, and one full
-// block closes the stream: B = beta + m + 1, rem = 16, delta = 0.
-// (o and the stream length: sg_layout.h)
-template <Construction C>
-__device__ __forceinline__ WprGeom wpr_geom(uint32_t adlen, uint32_t n) {
-    WprGeom g;
-    g.o = ct_offset<C>(adlen);
-    if constexpr (C == Construction::kRfc8439) {
-        g.sigma = 0u;
-        g.beta = g.o >> 4;
-        g.m = n >> 4;
-        g.B = g.beta + g.m + 1u;
-        g.rem = 16u;
-        g.delta = 0u;
-        return g;
-    }
-    g.sigma = g.o & 15u;
-    g.beta = g.o >> 4;
-    const uint32_t L = stream_bytes<C>(adlen, n);
-    g.B = (L + 15u) >> 4;
-    g.rem = L - 16u * (g.B - 1u);
-    g.m = n >> 4;                        // 16-byte ciphertext chunks
-    g.delta = g.B - g.beta - 1u - g.m;  // 0 or 1
-    return g;
-}
-
-// bytes >= lo of a little-endian word set: mask of the bytes whose index
-// (4 w + byte) is >= lo
-__device__ __forceinline__ uint32_t bytes_from(uint32_t w, uint32_t lo) {
-    if (lo <= 4u * w) return 0xffffffffu;
-    if (lo >= 4u * w + 4u) return 0u;
-    return 0xffffffffu << (8u * (lo - 4u * w));
-}
-
-// p - (2^24 * sum_{c<32} 2^(8c) mod p) in radix 2^26: the seed of the 32 x 32
-// accumulator, negated (tests/wpr_model.py keying: cj)
-constexpr uint32_t kCJ0 = 0x1bd2d2bu, kCJ1 = 0x36f6f6fu, kCJ2 = 0x3dbdbdbu, kCJ3 = 0x2f6f6f6u, kCJ4 = 0x1bdbdbdu;
-
-// ---------------------------------------------------------------------------
-// Keying pre-pass: one lane per record, 64 records per wave, the 160-word
-// record (sg_internal.h, kW*) stored unit by unit from registers (grouped layout below).
-// LIST: lane = slot of a bucket list (record wl.list[slot], any n of the
-// bucket), which also writes the slot's descriptor; otherwise slot = record
-// and n = 2^14.
-// ---------------------------------------------------------------------------
-// Table layout in HBM (round 3): the records of eight consecutive slots (a
-// record kernel's group) interleaved by 16-byte unit, unit u of slot 8 g + w
-// at tab + 1280 g + 4 (u rows + w) words (rows = 8, or count mod 8 in the last
-// group).  Each lane stores its own record unit by unit straight from
-// registers (non-temporal: the table does not sit dirty in the caches while
-// the record kernel streams) and every store instruction still writes whole
-// 128-byte lines (a group's row of one unit), so the keying kernel needs no
-// LDS staging and runs at the occupancy its registers allow; the record
-// kernel's 40 unit reads per record touch lines that the other seven waves of
-// its group read at the same time (the same 640 bytes per record from HBM).
-__device__ __forceinline__ uint32_t* wpr_tab_unit(const WprList& wl, uint32_t slot, uint32_t u) {
-    const uint32_t g = slot >> 3, w = slot & 7u;
-    const uint32_t rows = g < (wl.count >> 3) ? 8u : (wl.count & 7u);
-    return wl.tab + (uint64_t)g * (8u * kWprRecWords) + 4u * (u * rows + w);
-}
-// units [U0, U1) of a lane's record (rec: the record's 160 words, registers)
-template <uint32_t U0, uint32_t U1>
-__device__ __forceinline__ void wpr_store_units(const WprList& wl, uint32_t slot, bool act, const uint32_t* rec) {
-    if (!act) return;
-#pragma unroll
-    for (uint32_t u = U0; u < U1; ++u) {
-        const u32x4 val = {rec[4u * u], rec[4u * u + 1u], rec[4u * u + 2u], rec[4u * u + 3u]};
-        __builtin_nontemporal_store(val, reinterpret_cast<u32x4*>(wpr_tab_unit(wl, slot, u)));
-    }
-}
-
-// One launch keys every bucket: job b on blocks [blk0[b], blk0[b + 1]).
-struct WprKeyJobs {
-    WprList b[kWprBuckets];
-    uint32_t blk0[kWprBuckets];
-    uint32_t njobs;
-};
-
-// T13 (KParams.tls13; uniform launches of Construction::kRfc8439 only): a TLS 1.3
-// record of 2^14 content bytes and the inner type byte, n = 2^14 + 1 (RFC 8446
-// section 5.2).  The MAC stream is AD(5) || 11 zeros || 1024 ciphertext blocks ||
-// [ct byte 2^14 || 15 zeros] || le64(5) || le64(n): the record kernel's 1024 blocks
-// with one block more behind them, i.e. wpr_geom's B + 1 and delta = 1.  The
-// record kernel runs the 2^14 bytes; this kernel takes the tail over: keystream
-// block 257 beside block 0, the tail byte (seal: type ^ ks into out[2^14]; open:
-// in[2^14] ^ ks into out[2^14]) and its block (byte + 2^128) r^2 in ctot
-// (tests/test_wpr_mac_model_tls13.py).
-// T13 with LIST (bucket records, n the inner length, a multiple of 64): no tail; the
-// RFC bucket keying with adlen = 5, the header 17 03 03 be16(n + 16) as the prefix
-// block and le64(5) || le64(n) as the length block; seal: n = tls13_inner_len(len,
-// pad_to), and the descriptor carries the content length and the inner type.
-// (compiled for two waves per SIMD: four and more spill to scratch)
-template <bool OPEN, bool LIST, Construction C, bool T13>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg_wpr_keying_kernel(
-    const KParams p, const WprKeyJobs jobs) {
-    constexpr bool RFC = C == Construction::kRfc8439;
-    static_assert(!T13 || RFC, "TLS 1.3 records are RFC 8439");
-    constexpr bool TAIL13 = T13 && !LIST;  // the uniform launch: this kernel takes the tail byte and its block
-    const uint32_t lane = threadIdx.x;
-    WprList wl = jobs.b[0];
-    uint32_t b0 = 0;
-#pragma unroll
-    for (uint32_t i = 1; i < kWprBuckets; ++i)  // (constant indices: the kernarg table stays in SGPRs)
-        if (i < jobs.njobs && blockIdx.x >= jobs.blk0[i]) {
-            wl = jobs.b[i];
-            b0 = jobs.blk0[i];
-        }
-    const uint32_t slot0 = (blockIdx.x - b0) * kWprKeyThreads;
-    const uint32_t slot = slot0 + lane;
-    uint32_t rbuf[kWprRecWords];  // the lane's record (registers once unrolled)
-#pragma unroll
-    for (uint32_t i = 0; i < kWprRecWords; ++i) rbuf[i] = 0u;
-    uint32_t* st = rbuf + 80;  // the second half first (offsets below are half-relative)
-    const uint32_t adlen = T13 ? 5u : p.tls ? 13u : p.ad_len;
-    if (blockIdx.x == b0 && lane == 0u) *wl.ctr = 0u;  // the record kernel's group counter
-
-    const bool act = slot < wl.count;
-    const uint32_t rec = LIST ? (act ? wl.list[slot] : 0u) : slot;
-    uint32_t n = kWprN;
-    // (T13 buckets: the inner length, content || type || zeros on seal, as classified)
-    if constexpr (LIST && T13 && !OPEN) n = act ? tls13_inner_len(p.len[rec], p.pad_to) : kWprN;
-    else if constexpr (LIST) n = act ? p.len[rec] - (OPEN ? 16u : 0u) : kWprN;
-    WprGeom G = wpr_geom<C>(adlen, n);
-    if constexpr (TAIL13) {  // the tail block behind the 1024 of the record kernel
-        G.B += 1u;
-        G.delta = 1u;
-    }
-
-    F26 r = f26_zero();
-    uint32_t s[4] = {0u, 0u, 0u, 0u};
-    RecKey rk = {};
-    uint32_t tail = 0u;  // T13: ciphertext byte 2^14
-    if (act) {
-        rk = record_key<C>(p, rec);
-        uint32_t ks[16];
-        chacha_block(ks, rk.k, 0u, rk.n13, rk.n14, rk.n15);  // block 0 -> poly key (chacha20_poly1305.rs:50,75)
-        const PolyKey pk = poly_key(ks);
-        r = words_to_f26(pk.r0, pk.r1, pk.r2, pk.r3, 0u);
-        s[0] = pk.s[0]; s[1] = pk.s[1]; s[2] = pk.s[2]; s[3] = pk.s[3];
-        if constexpr (TAIL13) {
-            chacha_block(ks, rk.k, kWprTailBlock, rk.n13, rk.n14, rk.n15);  // byte 2^14 is its first
-            uint8_t* ob = p.out + p.out_stride * rec + kWprN;
-            if constexpr (OPEN) {
-                tail = p.in[p.in_stride * rec + kWprN];
-                *ob = (uint8_t)(tail ^ ks[0]);
-            } else {
-                tail = (p.tls_hdr ^ ks[0]) & 0xffu;  // the inner type (content_type)
-                *ob = (uint8_t)tail;
-            }
-        }
-        if constexpr (LIST) {  // the slot's descriptor: where the record lives, its length and nonce
-            const uint64_t io = rec_in_off(p, rec);
-            const uint64_t oo = rec_out_off(p, rec);
-            const uint32_t ki = key_slot(p, rec);
-            uint32_t* d = wl.desc + (uint64_t)slot * kWprDescWords;
-            st16(d, u32x4{(uint32_t)io, (uint32_t)(io >> 32), (uint32_t)oo, (uint32_t)(oo >> 32)});
-            st16(d + 4, u32x4{n, rec, ki, rk.n14});
-            // (T13 seal: the content length and the inner type, for the record kernel's loads and patch)
-            uint32_t clen = 0u, type = 0u;
-            if constexpr (T13 && !OPEN) {
-                clen = p.len[rec];
-                type = tls13_inner_type(p, rec);
-            }
-            st16(d + 8, u32x4{rk.n15, RFC ? rk.n13 : 0u, clen, type});
-        }
-    }
-
-    // ---- second half: lo[b] = R^b, hi[h][a] = 2^(32 h) R^(8 a) (R = r^4) ----
-    // (LIST: also the pieces of S(c) = sum_{u<c} R^u, c = (n / 64) & 31, see below)
-    const uint32_t kq = n >> 6, ca = kq >> 5, cl = kq & 7u, ch = (kq >> 3) & 3u;
-    auto sel = [](bool c, const F26& a, const F26& b) {
-        return F26{c ? a.v0 : b.v0, c ? a.v1 : b.v1, c ? a.v2 : b.v2, c ? a.v3 : b.v3, c ? a.v4 : b.v4};
-    };
-    const F26 r2 = fmul(r, r), R = fmul(r2, r2);
-    F26 x = f26_one(), sum_lo = f26_zero(), plo = f26_zero(), xlo = f26_one();
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        store_f26(st + (kWLo - 80u) + 5u * b, x);
-        sum_lo = f26_add(sum_lo, x);
-        if constexpr (LIST) {
-            plo = sel((uint32_t)b < cl, f26_add(plo, x), plo);  // sum_{b' < c & 7} R^b'
-            xlo = sel((uint32_t)b == cl, x, xlo);               // R^(c & 7)
-        }
-        x = fmul(x, R);
-    }
-    const F26 R8 = x;
-    F26 y = f26_one(), sum_hi = f26_zero(), phi = f26_zero(), yc = f26_one();
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        store_f26(st + (kWHi - 80u) + 5u * a, y);
-        store_f26(st + (kWHi - 80u) + 20u + 5u * a, mul_add(y, 0u, 64u, 0u, 0u, 0u, f26_zero()));  // * 2^32
-        sum_hi = f26_add(sum_hi, y);
-        if constexpr (LIST) {
-            phi = sel((uint32_t)a < ch, f26_add(phi, y), phi);  // sum_{a' < c >> 3} R^(8 a')
-            yc = sel((uint32_t)a == ch, y, yc);                 // R^(8 (c >> 3))
-        }
-        y = fmul(y, R8);
-    }
-    const F26 T = y;  // R^32 = r^128
-    wpr_store_units<20, 40>(wl, slot, act, rbuf);
-    st = rbuf;
-
-    // ---- first half: s, ctot, rd[u] = r^(1 + delta + u), tk[k] = T^k ----
-    st[kWS + 0] = s[0]; st[kWS + 1] = s[1]; st[kWS + 2] = s[2]; st[kWS + 3] = s[3];
-    const F26 r3 = fmul(r2, r), r5 = fmul(R, r), r6 = fmul(R, r2);
-    const bool d1 = G.delta != 0u;
-    const F26 pw[6] = {r, r2, r3, R, r5, r6};
-#pragma unroll
-    for (int u = 0; u < 5; ++u) store_f26(st + kWRd + 5u * u, d1 ? pw[u + 1] : pw[u]);
-    const F26 rd0 = d1 ? r2 : r;        // r^(1 + delta)
-    const F26 rdel = d1 ? r : f26_one();  // r^delta
-    F26 t = f26_one(), sum_t = f26_zero(), pta = f26_zero(), ta = f26_one();
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        store_f26(st + kWTk + 5u * k, t);
-        sum_t = f26_add(sum_t, t);
-        if constexpr (LIST) pta = sel((uint32_t)k < ca, f26_add(pta, t), pta);  // sum_{k' < a} T^k'
-        t = fmul(t, T);
-        if constexpr (LIST) ta = sel((uint32_t)k + 1u == ca, t, ta);            // T^a
-    }
-    wpr_store_units<3, 20>(wl, slot, act, rbuf);  // rd and tk now; s and ctot (units 0-2) at the end
-
-    // geometric sums: SW = sum_{u<32} R^u; g = G(m) = sum_{i=1..m} r^i and rm = r^m
-    // (m = n / 16: for n = 2^14, G(1024) = (r + r^2 + r^3 + r^4) SW sum_k T^k, r^1024 = T^8).
-    // Bucket records (LIST) have n = 64 k', k' = 32 a + c (a = 2..8, c < 32), so from the
-    // tables: G(4 k') = G4 S(k'), S(k') = sum_{u<k'} R^u = SW sum_{k<a} T^k + T^a S(c),
-    // S(c) = sum_{a'<c>>3} R^(8 a') sum_lo + R^(8 (c>>3)) sum_{b<c&7} R^b, r^m = T^a R^(8 (c>>3)) R^(c&7)
-    // (7 products instead of the ~25 of a square-and-multiply geometric sum)
-    const F26 SW = fmul(carry1(sum_hi), carry1(sum_lo));
-    const F26 G4 = carry1(f26_add(f26_add(r, r2), f26_add(r3, R)));
-    F26 g, rm;
-    if constexpr (LIST) {
-        const F26 Sc = fmul_add(yc, carry1(plo), fmul(carry1(phi), carry1(sum_lo)));
-        const F26 Sk = fmul_add(SW, carry1(pta), fmul(ta, Sc));
-        g = fmul(G4, Sk);
-        rm = fmul(ta, fmul(yc, xlo));
-    } else {
-        g = fmul(fmul(G4, SW), carry1(sum_t));
-        rm = t;
-    }
-    // pads (poly1305.rs:224-225): 2^128 sum_{b < B-1} r^(B-b) + 2^(8 rem) r
-    //   = 2^128 G(B) + (2^(8 rem) + p - 2^128) r,  G(B) = G(m) + r^m G(B - m)
-    const F26 GB = fmul_add(rm, geo_sum(r, G.B - G.m), g);
-    F26 pads = mul_add(GB, 0u, 0u, 0u, 0u, 1u << 24, f26_zero());
-    {
-        F26 cf = F26{0x3fffffbu, 0x3ffffffu, 0x3ffffffu, 0x3ffffffu, 0x2ffffffu};  // p - 2^128
-        const uint32_t bit = 8u * G.rem, li = bit / 26u, v = 1u << (bit - 26u * li);
-        cf.v0 += li == 0u ? v : 0u;
-        cf.v1 += li == 1u ? v : 0u;
-        cf.v2 += li == 2u ? v : 0u;
-        cf.v3 += li == 3u ? v : 0u;
-        cf.v4 += li == 4u ? v : 0u;
-        pads = fmul_add(cf, r, pads);
-    }
-    // i8 bias: 128 sum over the ciphertext bytes of their weights
-    //   = r^delta G(m) (A1 r + A2),  A1 = sum_{k=sigma}^{15} 128 2^(8k),  A2 = sum_{k<sigma} 128 2^(8k)
-    F26 bias;
-    {
-        uint32_t a1[4], a2[4];
-#pragma unroll
-        for (uint32_t w = 0; w < 4; ++w) {
-            const uint32_t mk = bytes_from(w, G.sigma);
-            a1[w] = 0x80808080u & mk;
-            a2[w] = 0x80808080u & ~mk;
-        }
-        const F26 A1 = words_to_f26(a1[0], a1[1], a1[2], a1[3], 0u);
-        const F26 A2 = words_to_f26(a2[0], a2[1], a2[2], a2[3], 0u);
-        bias = fmul(fmul(g, fmul_add(A1, r, A2)), rdel);
-    }
-    // accumulator seed: -(2^24 sum_c 2^(8c)) SW (every column, the idle lanes' too)
-    const F26 seed = mul_add(SW, kCJ0, kCJ1, kCJ2, kCJ3, kCJ4, f26_zero());
-    // prefix ad || le64(|ad|) (stream bytes < o) as blocks 0..beta: Horner, then r^(B - beta) = r^m r^(1 + delta)
-    F26 hp = f26_zero();
-    if (act) {
-        for (uint32_t b = 0; b <= G.beta; ++b) {
-            uint32_t w[4] = {0u, 0u, 0u, 0u};
-            for (uint32_t i = 0; i < 16u; ++i) {
-                const uint32_t pos = 16u * b + i;
-                // (RFC 8439: ad and its zero padding; block beta is empty, sigma = 0)
-                if constexpr (T13) {  // the record header; L = n + 1 + 16 (buckets: n the inner length, L = n + 16)
-                    if (pos < adlen) w[i >> 2] |= (uint32_t)tls13_ad_byte(LIST ? n + 16u : kWprN + 17u, pos) << (8u * (i & 3u));
-                } else if (pos < G.o)
-                    w[i >> 2] |= (uint32_t)prefix_byte<C>(p, rec, rk.seq, n, adlen, pos) << (8u * (i & 3u));
-            }
-            hp = fmul_add(hp, r, words_to_f26(w[0], w[1], w[2], w[3], 0u));
-        }
-    }
-    const F26 prefix = fmul(fmul(hp, rm), rd0);
-    // suffix le64(n) at stream offset o + n = 16 (beta + m) + sigma: n 2^(8 sigma) split at 2^128
-    // (RFC 8439: the single full block le64(adlen) || le64(n), the stream's last, at weight r)
-    F26 suffix;
-    if constexpr (TAIL13) {  // the tail block at r^2 (its 2^128 is in pads), then the length block
-        suffix = fmul_add(F26{tail, 0u, 0u, 0u, 0u}, r2, fmul(words_to_f26(adlen, 0u, n + 1u, 0u, 0u), r));
-    } else if constexpr (RFC) {
-        suffix = fmul(words_to_f26(adlen, 0u, n, 0u, 0u), r);
-    } else {
-        const uint32_t wi = G.sigma >> 2, bs = 8u * (G.sigma & 3u);
-        const uint64_t v = (uint64_t)n << bs;
-        uint32_t w[5] = {0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) {
-            if (i == wi) {
-                w[i] = (uint32_t)v;
-                w[i + 1] = (uint32_t)(v >> 32);
-            }
-        }
-        suffix = fmul_add(words_to_f26(w[0], w[1], w[2], w[3], 0u), rd0, fmul(F26{w[4], 0u, 0u, 0u, 0u}, rdel));
-    }
-    const F26 ctot = carry1(f26_add(f26_add(f26_add(pads, bias), f26_add(seed, prefix)), suffix));
-    store_f26(st + kWCtot, ctot);
-    wpr_store_units<0, 3>(wl, slot, act, rbuf);
-}
 
 // ---------------------------------------------------------------------------
 // The record kernel.
@@ -565,6 +189,142 @@ __device__ __forceinline__ void dma_one(uint32_t l0, const void* g) {
                  : "memory");
 }
 
+// One T digit line at ln (48 bytes of LDS): the 17 signed base-256 digits of lv, digit i at
+// byte 47 - sigma - i, zeros elsewhere (lv: the product of two table entries, unreduced)
+template <bool RFC, bool TLS>
+__device__ __forceinline__ void write_digit_line(uint8_t* ln, const F26& lv, uint32_t sigma) {
+    // any representative below 2^135 of r^e works (the MAC is exact mod p),
+    // so the product's limbs (v0, v2..v4 < 2^26, v1 < 2^26 + 2^9) are
+    // summed straight into 32-bit words, X = sum v_i 2^(26 i) < 2^131:
+    // four v_mad_u64_u32, no carry ripple, no reduction (round 4; the
+    // ripple_full form took ~35 more VALU per record)
+    uint32_t c;  // digits = the bytes of X + 0x80..80, each ^ 0x80
+    uint32_t d[5];
+    uint64_t t = mad_u64_u32(lv.v1, 1u << 26, (uint64_t)lv.v0);
+    const uint32_t x0 = (uint32_t)t;
+    t = mad_u64_u32(lv.v2, 1u << 20, t >> 32);
+    const uint32_t x1 = (uint32_t)t;
+    t = mad_u64_u32(lv.v3, 1u << 14, t >> 32);
+    const uint32_t x2 = (uint32_t)t;
+    t = mad_u64_u32(lv.v4, 1u << 8, t >> 32);
+    d[0] = addc(x0, 0x80808080u, 0u, &c) ^ 0x80808080u;
+    d[1] = addc(x1, 0x80808080u, c, &c) ^ 0x80808080u;
+    d[2] = addc(x2, 0x80808080u, c, &c) ^ 0x80808080u;
+    d[3] = addc((uint32_t)t, 0x80808080u, c, &c) ^ 0x80808080u;
+    d[4] = ((uint32_t)(t >> 32) + 0x80u + c) ^ 0x80u;
+    const u32x4 z = zero4();
+    if constexpr (RFC) {
+        // sigma = 0: line byte b = digit 47 - b (b = 31..47), the byte-reversed
+        // digit words R[k] = bswap(d[4 - k]) laid from byte 28 on
+        uint32_t R[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) R[k] = __builtin_bswap32(d[4 - k]);
+        st16(ln, z);
+        st16(ln + 16, u32x4{0u, 0u, 0u, R[0]});
+        st16(ln + 32, u32x4{R[1], R[2], R[3], R[4]});
+    } else if constexpr (TLS) {
+        // sigma = 5: line byte b = digit 42 - b (b = 26..42), i.e. the
+        // byte-reversed digit words R[k] = bswap(d[4 - k]) (digits 19 - 4k
+        // .. 16 - 4k, 17..19 zero) laid from byte 23 on: three 16-byte
+        // stores instead of 17 byte stores
+        uint32_t R[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) R[k] = __builtin_bswap32(d[4 - k]);
+        st16(ln, z);
+        st16(ln + 16, u32x4{0u, R[0] << 24, __builtin_amdgcn_alignbyte(R[1], R[0], 1),
+                            __builtin_amdgcn_alignbyte(R[2], R[1], 1)});
+        st16(ln + 32, u32x4{__builtin_amdgcn_alignbyte(R[3], R[2], 1), __builtin_amdgcn_alignbyte(R[4], R[3], 1),
+                            R[4] >> 8, 0u});
+    } else {
+        st16(ln, z);
+        st16(ln + 16, z);
+        st16(ln + 32, z);
+#pragma unroll
+        for (uint32_t i = 0; i < 17u; ++i) ln[47u - sigma - i] = (uint8_t)(d[i >> 2] >> (8u * (i & 3u)));
+    }
+}
+
+// TLS 1.3 bucket seal: the lane's 64-byte block blk of a landed chunk, el < 64 of its bytes content
+// (<= 0: none), becomes content || type || zeros: the unit that holds the content's end keeps its
+// content bytes and takes the type, the units behind it are zeroed.  LDS only.
+__device__ __forceinline__ void pad13_patch_block(uint8_t* blk, uint32_t xq, int32_t el, uint32_t type) {
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; ++i) {
+        uint8_t* up = blk + 16u * (i ^ xq);
+        u32x4 v = ld16(up);  // (a unit that was not loaded: stale bytes, all masked)
+#pragma unroll
+        for (uint32_t w = 0; w < 4u; ++w) {
+            const int32_t kk = el - (int32_t)(16u * i + 4u * w);  // content bytes of the word
+            const uint32_t keep = kk >= 4 ? 0xffffffffu : kk <= 0 ? 0u : (1u << (8 * kk)) - 1u;
+            v[w] = (v[w] & keep) | (kk >= 0 && kk < 4 ? type << (8 * kk) : 0u);
+        }
+        st16(up, v);
+    }
+}
+
+// The lane's term of the tag: X = sum_r (D[c_r][q] + 2^24) 2^(8 c_r - 32 hh) assembled exactly from
+// the lane's 16 accumulator entries, c_r = (r & 3) + 8 (r >> 2) + 4 hh (|D| < 2^23 signed; the seed
+// 2^24 per entry makes every 64-bit word positive), reduced and scaled by the row weight W.
+// The first read of an MFMA result: behind the fence.
+__device__ __forceinline__ F26 lane_term(const i32x16& acc, const F26& W) {
+    uint32_t xw[8];
+    constexpr uint64_t kSeed = (1ull << 24) + (1ull << 32) + (1ull << 40) + (1ull << 48);
+    mfma_result_fence();
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        uint64_t yv = mad_i64_i32_1(acc[4 * m], kSeed);  // exact mod 2^64: the sum is positive
+        yv = mad_i64_i32(acc[4 * m + 1], 256u, yv);
+        yv = mad_i64_i32(acc[4 * m + 2], 65536u, yv);
+        yv = mad_i64_i32(acc[4 * m + 3], 16777216u, yv);
+        xw[2 * m] = (uint32_t)yv;
+        xw[2 * m + 1] = (uint32_t)(yv >> 32);
+    }
+    return fmul(reduce_words8(xw), W);
+}
+
+// The sum of the 64 lane terms, wave-uniform (summed into lane 63: row_shr 1, 2, 4, 8,
+// row_bcast:15, carry, row_bcast:31; limbs unreduced)
+__device__ __forceinline__ F26 wave_sum(F26 f) {
+    dpp_add<kDppShr1>(f);
+    dpp_add<kDppShr2>(f);
+    dpp_add<kDppShr4>(f);
+    dpp_add<kDppShr8>(f);
+    dpp_add<kDppBcast15>(f);
+    f = carry1(f);
+    dpp_add<kDppBcast31>(f);
+    auto lane63 = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, 63); };
+    return F26{lane63(f.v0), lane63(f.v1), lane63(f.v2), lane63(f.v3), lane63(f.v4)};
+}
+
+// seal: the tag behind the ciphertext (tagp = out + n; TAIL13: behind the tail byte, at the odd address tagp + 1)
+// (tw by value as a vector: handed over as an array, the draft's uniform TLS seal kernel spills)
+template <bool TAIL13>
+__device__ __forceinline__ void store_tag(uint8_t* tagp, bool active, uint32_t lane, const u32x4 tw) {
+    if constexpr (TAIL13) {  // one byte per lane: exactly [n + 1, n + 17) is written
+        const uint32_t wi = lane >> 2;
+        const uint32_t w = wi == 0u ? tw[0] : wi == 1u ? tw[1] : wi == 2u ? tw[2] : tw[3];
+        if (active && lane < 16u) tagp[1u + lane] = (uint8_t)(w >> (8u * (lane & 3u)));
+    } else if (active && lane == 0u) {
+        st16(tagp, tw);  // ct || tag (chacha20_poly1305.rs:55)
+    }
+}
+// open: the record's status from the received tag in the wave's LDS tag slot rxs
+// (TAIL13: the two aligned units that hold it landed at rxs - 16; shifted by its one byte)
+template <bool TAIL13>
+__device__ __forceinline__ void check_tag(uint8_t* status, bool active, uint32_t lane, const uint8_t* rxs, const uint32_t tw[4]) {
+    if (active && lane == 0u) {
+        if constexpr (TAIL13) {
+            const uint32_t* rxl = reinterpret_cast<const uint32_t*>(rxs - 16u);
+            const uint32_t rx[4] = {__builtin_amdgcn_alignbyte(rxl[1], rxl[0], 1), __builtin_amdgcn_alignbyte(rxl[2], rxl[1], 1),
+                                    __builtin_amdgcn_alignbyte(rxl[3], rxl[2], 1), __builtin_amdgcn_alignbyte(rxl[4], rxl[3], 1)};
+            *status = tag_mismatch(rx, tw);
+        } else {
+            const uint32_t* rxl = reinterpret_cast<const uint32_t*>(rxs);
+            *status = tag_mismatch(rxl, tw);
+        }
+    }
+}
+
 // Where a record lives and what keys it (uniform per wave).  Uniform batches
 // derive it from the record index; bucket launches read the slot's descriptor.
 struct RecDesc {
@@ -575,6 +335,52 @@ struct RecDesc {
     uint32_t n13;       // RFC 8439 only (the draft's word 13 is 0)
     uint32_t clen, type;  // TLS 1.3 bucket seal only: the content length and the inner type
 };
+
+// The descriptor the keying kernel wrote for a bucket slot (kWprDescWords, sg_internal.h), word i
+// fetched by word(i): a scalar load from the table, or a read of the wave's LDS descriptor slot.
+template <bool RFC, bool PAD13, class Word>
+__device__ __forceinline__ RecDesc decode_desc(Word&& word) {
+    RecDesc d;
+    d.n13 = d.clen = d.type = 0u;
+    d.io = (uint64_t)word(0) | ((uint64_t)word(1) << 32);
+    d.oo = (uint64_t)word(2) | ((uint64_t)word(3) << 32);
+    d.n = word(4);
+    d.rec = word(5);
+    d.ki = word(6);
+    d.n14 = word(7);
+    d.n15 = word(8);
+    if constexpr (RFC) d.n13 = word(9);
+    if constexpr (PAD13) {
+        d.clen = word(10);
+        d.type = word(11);
+    }
+    return d;
+}
+
+// The nonce words of record `slot` of a uniform launch, key slot d.ki (chacha20.rs:25-51;
+// TLS: be64(seq), tls.rs:103), by scalar loads and on the SALU
+template <bool RFC, bool TLS>
+__device__ __forceinline__ void uniform_nonce(const KParams& p, uint32_t slot, RecDesc& d) {
+    if constexpr (RFC && TLS) {  // RFC 7905: the key's write IV XOR (0^32 || be64(seq)), on the SALU
+        uint64_t seq = p.seq0 + slot;
+        if (p.seq) seq = (uint64_t)cload(p.seq, 2ull * slot) | ((uint64_t)cload(p.seq, 2ull * slot + 1u) << 32);
+        d.n13 = cload(p.ivs, 3ull * d.ki);
+        d.n14 = cload(p.ivs, 3ull * d.ki + 1u) ^ sbswap32((uint32_t)(seq >> 32));
+        d.n15 = cload(p.ivs, 3ull * d.ki + 2u) ^ sbswap32((uint32_t)seq);
+    } else if constexpr (RFC) {  // explicit 12-byte nonces
+        d.n13 = cload(p.nonces, 3ull * slot);
+        d.n14 = cload(p.nonces, 3ull * slot + 1u);
+        d.n15 = cload(p.nonces, 3ull * slot + 2u);
+    } else if constexpr (TLS) {
+        uint64_t seq = p.seq0 + slot;
+        if (p.seq) seq = (uint64_t)cload(p.seq, 2ull * slot) | ((uint64_t)cload(p.seq, 2ull * slot + 1u) << 32);
+        d.n14 = sbswap32((uint32_t)(seq >> 32));  // (on the SALU: the chain below stays scalar)
+        d.n15 = sbswap32((uint32_t)seq);
+    } else {
+        d.n14 = cload(p.nonces, 2ull * slot);
+        d.n15 = cload(p.nonces, 2ull * slot + 1u);
+    }
+}
 
 // TLS13, uniform launch (TLS 1.3, see the keying kernel): the record's 2^14 bytes as
 // ever; only the tag moves behind the tail byte, to the odd address n + 1.
@@ -643,69 +449,25 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     // The record of slot `slot` (slot < cnt): uniform batches from the strides,
     // bucket launches from the descriptor the keying kernel wrote.
     auto desc_of_slot = [&](uint32_t slot) {
-        RecDesc d;
-        d.n13 = d.clen = d.type = 0u;
         if constexpr (LIST) {
             const uint32_t* dw = wl.desc + (uint64_t)slot * kWprDescWords;
-            d.io = (uint64_t)cload(dw, 0) | ((uint64_t)cload(dw, 1) << 32);
-            d.oo = (uint64_t)cload(dw, 2) | ((uint64_t)cload(dw, 3) << 32);
-            d.n = cload(dw, 4);
-            d.rec = cload(dw, 5);
-            d.ki = cload(dw, 6);
-            d.n14 = cload(dw, 7);
-            d.n15 = cload(dw, 8);
-            if constexpr (RFC) d.n13 = cload(dw, 9);
-            if constexpr (PAD13) {
-                d.clen = cload(dw, 10);
-                d.type = cload(dw, 11);
-            }
+            return decode_desc<RFC, PAD13>([&](uint32_t i) { return cload(dw, i); });
         } else {
+            RecDesc d;
+            d.n13 = d.clen = d.type = 0u;
             d.rec = slot;
             d.io = p.in_stride * slot;
             d.oo = p.out_stride * slot;
             d.n = kWprN;
             d.ki = key_slot_of(p, p.key_index ? cload(p.key_index, slot) : 0u);  // (key_slot, by a scalar load)
-            // nonce (chacha20.rs:25-51; TLS: be64(seq), tls.rs:103)
-            if constexpr (RFC && TLS) {  // RFC 7905: the key's write IV XOR (0^32 || be64(seq)), on the SALU
-                uint64_t seq = p.seq0 + slot;
-                if (p.seq) seq = (uint64_t)cload(p.seq, 2ull * slot) | ((uint64_t)cload(p.seq, 2ull * slot + 1u) << 32);
-                d.n13 = cload(p.ivs, 3ull * d.ki);
-                d.n14 = cload(p.ivs, 3ull * d.ki + 1u) ^ sbswap32((uint32_t)(seq >> 32));
-                d.n15 = cload(p.ivs, 3ull * d.ki + 2u) ^ sbswap32((uint32_t)seq);
-            } else if constexpr (RFC) {  // explicit 12-byte nonces
-                d.n13 = cload(p.nonces, 3ull * slot);
-                d.n14 = cload(p.nonces, 3ull * slot + 1u);
-                d.n15 = cload(p.nonces, 3ull * slot + 2u);
-            } else if constexpr (TLS) {
-                uint64_t seq = p.seq0 + slot;
-                if (p.seq) seq = (uint64_t)cload(p.seq, 2ull * slot) | ((uint64_t)cload(p.seq, 2ull * slot + 1u) << 32);
-                d.n14 = sbswap32((uint32_t)(seq >> 32));  // (on the SALU: the chain below stays scalar)
-                d.n15 = sbswap32((uint32_t)seq);
-            } else {
-                d.n14 = cload(p.nonces, 2ull * slot);
-                d.n15 = cload(p.nonces, 2ull * slot + 1u);
-            }
+            uniform_nonce<RFC, TLS>(p, slot, d);
+            return d;
         }
-        return d;
     };
     // the next record's descriptor, landed in the wave's LDS descriptor slot
     auto desc_from_lds = [&]() {
         const uint32_t* dl = reinterpret_cast<const uint32_t*>(lines + kWprDescOff);
-        RecDesc d;
-        d.n13 = d.clen = d.type = 0u;
-        d.io = (uint64_t)uniform(dl[0]) | ((uint64_t)uniform(dl[1]) << 32);
-        d.oo = (uint64_t)uniform(dl[2]) | ((uint64_t)uniform(dl[3]) << 32);
-        d.n = uniform(dl[4]);
-        d.rec = uniform(dl[5]);
-        d.ki = uniform(dl[6]);
-        d.n14 = uniform(dl[7]);
-        d.n15 = uniform(dl[8]);
-        if constexpr (RFC) d.n13 = uniform(dl[9]);
-        if constexpr (PAD13) {
-            d.clen = uniform(dl[10]);
-            d.type = uniform(dl[11]);
-        }
-        return d;
+        return decode_desc<RFC, PAD13>([&](uint32_t i) { return uniform(dl[i]); });
     };
 
     // Chunk c of a record is fetched by LDS-DMA into the wave buffer that the
@@ -851,56 +613,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         }
         wave_lds_sync();  // every table read is done before the lines overwrite it
         if (lane < kWprLines) {
-            // any representative below 2^135 of r^e works (the MAC is exact mod p),
-            // so the product's limbs (v0, v2..v4 < 2^26, v1 < 2^26 + 2^9) are
-            // summed straight into 32-bit words, X = sum v_i 2^(26 i) < 2^131:
-            // four v_mad_u64_u32, no carry ripple, no reduction (round 4; the
-            // ripple_full form took ~35 more VALU per record)
-            uint32_t c;  // digits = the bytes of X + 0x80..80, each ^ 0x80
-            uint32_t d[5];
-            uint64_t t = mad_u64_u32(lv.v1, 1u << 26, (uint64_t)lv.v0);
-            const uint32_t x0 = (uint32_t)t;
-            t = mad_u64_u32(lv.v2, 1u << 20, t >> 32);
-            const uint32_t x1 = (uint32_t)t;
-            t = mad_u64_u32(lv.v3, 1u << 14, t >> 32);
-            const uint32_t x2 = (uint32_t)t;
-            t = mad_u64_u32(lv.v4, 1u << 8, t >> 32);
-            d[0] = addc(x0, 0x80808080u, 0u, &c) ^ 0x80808080u;
-            d[1] = addc(x1, 0x80808080u, c, &c) ^ 0x80808080u;
-            d[2] = addc(x2, 0x80808080u, c, &c) ^ 0x80808080u;
-            d[3] = addc((uint32_t)t, 0x80808080u, c, &c) ^ 0x80808080u;
-            d[4] = ((uint32_t)(t >> 32) + 0x80u + c) ^ 0x80u;
-            uint8_t* ln = lines + kWprLineBytes * lane;
-            const u32x4 z = zero4();
-            if constexpr (RFC) {
-                // sigma = 0: line byte b = digit 47 - b (b = 31..47), the byte-reversed
-                // digit words R[k] = bswap(d[4 - k]) laid from byte 28 on
-                uint32_t R[5];
-#pragma unroll
-                for (int k = 0; k < 5; ++k) R[k] = __builtin_bswap32(d[4 - k]);
-                st16(ln, z);
-                st16(ln + 16, u32x4{0u, 0u, 0u, R[0]});
-                st16(ln + 32, u32x4{R[1], R[2], R[3], R[4]});
-            } else if constexpr (TLS) {
-                // sigma = 5: line byte b = digit 42 - b (b = 26..42), i.e. the
-                // byte-reversed digit words R[k] = bswap(d[4 - k]) (digits 19 - 4k
-                // .. 16 - 4k, 17..19 zero) laid from byte 23 on: three 16-byte
-                // stores instead of 17 byte stores
-                uint32_t R[5];
-#pragma unroll
-                for (int k = 0; k < 5; ++k) R[k] = __builtin_bswap32(d[4 - k]);
-                st16(ln, z);
-                st16(ln + 16, u32x4{0u, R[0] << 24, __builtin_amdgcn_alignbyte(R[1], R[0], 1),
-                                    __builtin_amdgcn_alignbyte(R[2], R[1], 1)});
-                st16(ln + 32, u32x4{__builtin_amdgcn_alignbyte(R[3], R[2], 1), __builtin_amdgcn_alignbyte(R[4], R[3], 1),
-                                    R[4] >> 8, 0u});
-            } else {
-                st16(ln, z);
-                st16(ln + 16, z);
-                st16(ln + 32, z);
-#pragma unroll
-                for (uint32_t i = 0; i < 17u; ++i) ln[47u - sigma - i] = (uint8_t)(d[i >> 2] >> (8u * (i & 3u)));
-            }
+            write_digit_line<RFC, TLS>(lines + kWprLineBytes * lane, lv, sigma);
         } else if (lane == kWprLines) {
             st16(lines + kWprLines * kWprLineBytes, zero4());
         }
@@ -1005,6 +718,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                      : "scc");                                                                                    \
     } while (0)
 
+    // double round of chunk j: at full EXEC, or limited to the live lanes in chunk j0 of a list record
+#define SG_ROUND(j)                          \
+    do {                                     \
+        if (LIST && (j) == j0) SG_DR_LIVE(); \
+        else SG_DR();                        \
+    } while (0)
+
 #pragma unroll
         for (uint32_t j = j0; j < 4u; ++j) {
             SG_TICK(t_js);
@@ -1039,20 +759,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                     // el: the content bytes of the lane's 64-byte block (<= 0: none).  A lane of chunk j0
                     // in front of the record has el >= 64 (e >= vs) and sits this out.
                     const int32_t el = (int32_t)e - (int32_t)(kWprChunk * j + 64u * lane);
-                    if (el < 64) {
-#pragma unroll
-                        for (uint32_t i = 0; i < 4u; ++i) {
-                            uint8_t* up = cb + 16u * (4u * lane + (i ^ xq));
-                            u32x4 v = ld16(up);  // (a unit that was not loaded: stale bytes, all masked)
-#pragma unroll
-                            for (uint32_t w = 0; w < 4u; ++w) {
-                                const int32_t kk = el - (int32_t)(16u * i + 4u * w);  // content bytes of the word
-                                const uint32_t keep = kk >= 4 ? 0xffffffffu : kk <= 0 ? 0u : (1u << (8 * kk)) - 1u;
-                                v[w] = (v[w] & keep) | (kk >= 0 && kk < 4 ? cd.type << (8 * kk) : 0u);
-                            }
-                            st16(up, v);
-                        }
-                    }
+                    if (el < 64) pad13_patch_block(cb + 64u * lane, xq, el, cd.type);
                 }
             }
 
@@ -1115,7 +822,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             if (j > j0) mac_load(j - 1u, 0u, R0);
             if (pend) oa = out_piece(0u);
             SG_PIN();
-            if (LIST && j == j0) SG_DR_LIVE(); else SG_DR();
+            SG_ROUND(j);
             SG_PIN();
             if (LIST && j == 3u) {  // wave 0 published it at the start of iteration j0 + 1 (LIST: J >= 2)
                 gnn = uniform(*gslot);
@@ -1129,7 +836,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 ob = out_piece(1u);
             }
             SG_PIN();
-            if (LIST && j == j0) SG_DR_LIVE(); else SG_DR();
+            SG_ROUND(j);
             SG_PIN();
             if (j > j0) {
                 mac_mfma(R1, A[1]);
@@ -1141,7 +848,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             }
             dma_piece(0u);
             SG_PIN();
-            if (LIST && j == j0) SG_DR_LIVE(); else SG_DR();
+            SG_ROUND(j);
             SG_PIN();
             if (j > j0) {
                 mac_mfma(R0, A[2]);
@@ -1153,13 +860,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             }
             dma_piece(1u);
             SG_PIN();
-            if (LIST && j == j0) SG_DR_LIVE(); else SG_DR();
+            SG_ROUND(j);
             SG_PIN();
             if (j > j0) mac_mfma(R1, A[3]);
             if (pend) store_piece(3u, ob);
             dma_piece(2u);
             SG_PIN();
-            if (LIST && j == j0) SG_DR_LIVE(); else SG_DR();
+            SG_ROUND(j);
             SG_PIN();
             dma_piece(3u);
             if (j == 3u) {
@@ -1167,7 +874,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 mac_load(3u, 1u, R1);
             }
             SG_PIN();
-            if (LIST && j == j0) SG_DR_LIVE(); else SG_DR();
+            SG_ROUND(j);
             SG_PIN();
             if (j == 3u) {
                 F3[0] = mac_frag(R0);
@@ -1176,19 +883,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 mac_load(3u, 3u, R1);
             }
             SG_PIN();
-            if (LIST && j == j0) SG_DR_LIVE(); else SG_DR();
+            SG_ROUND(j);
             SG_PIN();
             if (j == 3u) {
                 F3[2] = mac_frag(R0);
                 F3[3] = mac_frag(R1);
             }
             SG_PIN();
-            if (LIST && j == j0) SG_DR_LIVE(); else SG_DR();
+            SG_ROUND(j);
             SG_PIN();
 #pragma unroll
             for (uint32_t i = 0; i < 4u; ++i) D[i] = ld16(cb + 16u * (4u * lane + (i ^ xq)));
             SG_PIN();
-            if (LIST && j == j0) SG_DR_LIVE(); else SG_DR();
+            SG_ROUND(j);
             SG_PIN();
             SG_TICK(t_jr);
             SG_ACC(3, t_jw, t_jr);  // rounds (+ MAC of the previous chunk)
@@ -1232,57 +939,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             t_prev = t_je;
 #endif
         }
+#undef SG_ROUND
 #undef SG_DR
 #undef SG_PIN
 
-        // ---- assemble X = sum_r (D[c_r][q] + 2^24) 2^(8 c_r - 32 hh), c_r = (r & 3) + 8 (r >> 2) + 4 hh
-        // (|D| < 2^23 signed; the seed 2^24 per entry makes every 64-bit word positive)
-        uint32_t xw[8];
-        constexpr uint64_t kSeed = (1ull << 24) + (1ull << 32) + (1ull << 40) + (1ull << 48);
-        mfma_result_fence();
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            uint64_t yv = mad_i64_i32_1(acc[4 * m], kSeed);  // exact mod 2^64: the sum is positive
-            yv = mad_i64_i32(acc[4 * m + 1], 256u, yv);
-            yv = mad_i64_i32(acc[4 * m + 2], 65536u, yv);
-            yv = mad_i64_i32(acc[4 * m + 3], 16777216u, yv);
-            xw[2 * m] = (uint32_t)yv;
-            xw[2 * m + 1] = (uint32_t)(yv >> 32);
-        }
-        F26 f = fmul(reduce_words8(xw), W);
-        {  // sum the 64 lane terms into lane 63: row_shr 1, 2, 4, 8, row_bcast:15, carry, row_bcast:31
-            dpp_add<kDppShr1>(f);
-            dpp_add<kDppShr2>(f);
-            dpp_add<kDppShr4>(f);
-            dpp_add<kDppShr8>(f);
-            dpp_add<kDppBcast15>(f);
-            f = carry1(f);
-            dpp_add<kDppBcast31>(f);
-        }
-        auto lane63 = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, 63); };
-        const F26 fs = {lane63(f.v0) + ctot.v0, lane63(f.v1) + ctot.v1, lane63(f.v2) + ctot.v2,
-                        lane63(f.v3) + ctot.v3, lane63(f.v4) + ctot.v4};
+        // ---- the tag: lane terms, wave sum, constant term, s (poly1305.rs:229-253) ----
+        const F26 f = wave_sum(lane_term(acc, W));
+        const F26 fs = {f.v0 + ctot.v0, f.v1 + ctot.v1, f.v2 + ctot.v2, f.v3 + ctot.v3, f.v4 + ctot.v4};
         uint32_t tw[4];
         tag_words(fs, sk, tw);
-        if constexpr (TAIL13) {
-            if constexpr (!OPEN) {  // one byte per lane: exactly [n + 1, n + 17) is written
-                const uint32_t wi = lane >> 2;
-                const uint32_t w = wi == 0u ? tw[0] : wi == 1u ? tw[1] : wi == 2u ? tw[2] : tw[3];
-                if (active && lane < 16u) outb[n + 1u + lane] = (uint8_t)(w >> (8u * (lane & 3u)));
-            } else if (active && lane == 0u) {  // the tag from the aligned units, shifted by its one byte
-                const uint32_t* rxl = reinterpret_cast<const uint32_t*>(lines + kWprRxOff - 16u);
-                const uint32_t rx[4] = {__builtin_amdgcn_alignbyte(rxl[1], rxl[0], 1), __builtin_amdgcn_alignbyte(rxl[2], rxl[1], 1),
-                                        __builtin_amdgcn_alignbyte(rxl[3], rxl[2], 1), __builtin_amdgcn_alignbyte(rxl[4], rxl[3], 1)};
-                p.status[cd.rec] = tag_mismatch(rx, tw);
-            }
-        } else if (active && lane == 0u) {
-            if constexpr (!OPEN) {
-                st16(outb + n, u32x4{tw[0], tw[1], tw[2], tw[3]});  // ct || tag (chacha20_poly1305.rs:55)
-            } else {
-                const uint32_t* rxl = reinterpret_cast<const uint32_t*>(lines + kWprRxOff);
-                p.status[cd.rec] = tag_mismatch(rxl, tw);
-            }
-        }
+        if constexpr (OPEN) check_tag<TAIL13>(p.status + cd.rec, active, lane, lines + kWprRxOff, tw);
+        else store_tag<TAIL13>(outb + n, active, lane, u32x4{tw[0], tw[1], tw[2], tw[3]});
         g = gn;
         if constexpr (LIST) {
             gnx = gnn;
@@ -1316,8 +983,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #endif
 }
 
-int g_cus[64];  // CUs per device ordinal (0: not read yet)
-
 }  // namespace
 
 #if SG_WPR_PROFILE
@@ -1333,18 +998,6 @@ extern "C" int sg_wpr_profile_read(unsigned long long* host, size_t n) {
 namespace sg {
 #endif
 
-hipError_t device_cus(int* cus) {
-    int dev = 0;
-    hipError_t e;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-    *cus = dev >= 0 && dev < 64 ? __atomic_load_n(&g_cus[dev], __ATOMIC_RELAXED) : 0;
-    if (*cus <= 0) {
-        if ((e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) __atomic_store_n(&g_cus[dev], *cus, __ATOMIC_RELAXED);
-    }
-    return hipSuccess;
-}
-
 // persistent grid: two workgroups (16 waves) per CU, at most one per record group
 static uint32_t wpr_grid(int cus, uint32_t count) {
     const uint32_t ngroups = (count + kWprWaves - 1u) / kWprWaves;
@@ -1359,16 +1012,8 @@ hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_
     wl.tab = p.ws + (uint64_t)p.count * kWsWprTab;
     wl.desc = nullptr;
     wl.ctr = ws_tail(p.ws, p.count) + kTailCtr + kWprBuckets;
-    WprKeyJobs jobs = {};
-    jobs.b[0] = wl;
-    jobs.njobs = 1;
-    const uint32_t kgrid = (p.count + kWprKeyThreads - 1u) / kWprKeyThreads;
-    with_form(p, open, [&](auto OPEN, auto C, auto T13) {
-        const dim3 g(kgrid), b(kWprKeyThreads);
-        hipLaunchKernelGGL((sg_wpr_keying_kernel<OPEN.value, false, C.value, T13.value>), g, b, 0, s, p, jobs);
-    });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    hipError_t e;
+    if ((e = launch_wpr_keying(p, open, wl, s)) != hipSuccess) return e;
     if ((e = mark(ev_mid, s)) != hipSuccess) return e;
     int cus = 0;
     if ((e = device_cus(&cus)) != hipSuccess) return e;
@@ -1377,25 +1022,6 @@ hipError_t launch_wpr(const KParams& p, bool open, hipStream_t s, hipEvent_t ev_
         const dim3 g(grid), b(512);  // (a TLS 1.3 batch is a TLS batch)
         if (p.tls) hipLaunchKernelGGL((sg_wpr_kernel<OPEN.value, true, 4, false, C.value, T13.value>), g, b, kWprWgLds, s, p, wl);
         else hipLaunchKernelGGL((sg_wpr_kernel<OPEN.value, false, 4, false, C.value, false>), g, b, kWprWgLds, s, p, wl);
-    });
-    return hipGetLastError();
-}
-
-hipError_t launch_wpr_keying_lists(const KParams& p, bool open, const WprList* wl, hipStream_t s) {
-    if (!p.tls) return hipErrorInvalidValue;  // buckets are TLS records: 1.2 of either construction, padded 1.3
-    WprKeyJobs jobs = {};
-    uint32_t grid = 0;
-    for (uint32_t b = 0; b < kWprBuckets; ++b) {
-        if (wl[b].count == 0) continue;
-        jobs.b[jobs.njobs] = wl[b];
-        jobs.blk0[jobs.njobs] = grid;
-        grid += (wl[b].count + kWprKeyThreads - 1u) / kWprKeyThreads;
-        ++jobs.njobs;
-    }
-    if (grid == 0) return hipSuccess;
-    with_form(p, open, [&](auto OPEN, auto C, auto T13) {
-        const dim3 g(grid), b(kWprKeyThreads);
-        hipLaunchKernelGGL((sg_wpr_keying_kernel<OPEN.value, true, C.value, T13.value>), g, b, 0, s, p, jobs);
     });
     return hipGetLastError();
 }
@@ -1421,13 +1047,6 @@ hipError_t launch_wpr_list(const KParams& p, bool open, uint32_t J, const WprLis
     });
     return hipGetLastError();
 }
-
-static EnvSwitch g_wpr{"SG_LOCKSTEP"};
-bool wpr_enabled() { return g_wpr.on(); }
-int set_wpr(int enable) { return g_wpr.set(enable); }
-static EnvSwitch g_tls13_buckets{"SG_TLS13_BUCKETS", -1, false};  // off unless set
-bool tls13_buckets_enabled() { return g_tls13_buckets.on(); }
-int set_tls13_buckets(int enable) { return g_tls13_buckets.set(enable); }
 
 const char* wpr_kernel_config() {
     return "sg_wpr_kernel v17: full 16 KiB records, one wave per record (8 per 512-thread workgroup, persistent "

@@ -1,4 +1,4 @@
-"""The wave-per-record keying table's grouped layout (sg_wpr.hip,
+"""The wave-per-record keying table's grouped layout (sg_wpr_layout.h,
 wpr_tab_unit): restated here and checked to be a
 bijection from (slot, unit, word) onto the count x 160 words the workspace
 reserves, for full and partial last groups, and to give every store

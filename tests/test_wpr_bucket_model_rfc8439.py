@@ -1,5 +1,5 @@
 """CPU check of the bucket keying in RFC 8439 form
-(sg_wpr_keying_kernel<OPEN, true, Construction::kRfc8439>, suruga_amd/csrc/sg_wpr.hip)
+(sg_wpr_keying_kernel<OPEN, true, Construction::kRfc8439>, suruga_amd/csrc/sg_wpr_keying.hip)
 with the model of tests/wpr_model.py (keying(..., n)).
 
 A bucket record of n = 64 k' bytes (4 KiB < n <= 16 KiB) runs right-aligned in the

@@ -1,5 +1,5 @@
 """CPU check of the bucket keying in TLS 1.3 form
-(sg_wpr_keying_kernel<OPEN, true, Construction::kRfc8439, true>, suruga_amd/csrc/sg_wpr.hip)
+(sg_wpr_keying_kernel<OPEN, true, Construction::kRfc8439, true>, suruga_amd/csrc/sg_wpr_keying.hip)
 with the model of tests/wpr_model.py.
 
 A padded TLS 1.3 record of n = 64 k' inner bytes (4 KiB < n <= 16 KiB) has the MAC stream

@@ -1,5 +1,5 @@
 """CPU check of the decomposition behind the wave-per-record kernel's Poly1305
-(sg_wpr_kernel and sg_wpr_keying_kernel in suruga_amd/csrc/sg_wpr.hip),
+(sg_wpr_kernel in suruga_amd/csrc/sg_wpr.hip and sg_wpr_keying_kernel in sg_wpr_keying.hip),
 draft form, with the model of tests/wpr_model.py: keying() for the keying kernel,
 wpr_tag() for the record kernel on its 16 KiB frame.  The other record forms run the
 same model: tests/test_wpr_mac_model_rfc8439.py, tests/test_wpr_mac_model_tls13.py,

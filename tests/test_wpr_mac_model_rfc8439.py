@@ -1,5 +1,5 @@
 """CPU check of the RFC 8439 constant term of the wave-per-record keying kernel
-(sg_wpr_keying_kernel<OPEN, false, Construction::kRfc8439>, suruga_amd/csrc/sg_wpr.hip)
+(sg_wpr_keying_kernel<OPEN, false, Construction::kRfc8439>, suruga_amd/csrc/sg_wpr_keying.hip)
 with the model of tests/wpr_model.py.
 
 In the RFC stream ad || 0.. || ct || 0.. || le64(|ad|) || le64(n) the ciphertext

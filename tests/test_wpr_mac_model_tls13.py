@@ -1,5 +1,5 @@
 """CPU check of the TLS 1.3 constant term of the wave-per-record keying kernel
-(sg_wpr_keying_kernel<OPEN, false, Construction::kRfc8439, true>, suruga_amd/csrc/sg_wpr.hip)
+(sg_wpr_keying_kernel<OPEN, false, Construction::kRfc8439, true>, suruga_amd/csrc/sg_wpr_keying.hip)
 with the model of tests/wpr_model.py (keying(..., tail=)).
 
 A full TLS 1.3 record is 2^14 content bytes and the inner type byte, n = 2^14 + 1

@@ -1,5 +1,5 @@
 """Python model of the wave-per-record kernel's Poly1305 (sg_wpr_kernel and
-sg_wpr_keying_kernel in suruga_amd/csrc/sg_wpr.hip) -- TEST
+sg_wpr_keying_kernel in suruga_amd/csrc/sg_wpr.hip and sg_wpr_keying.hip) -- TEST
 INFRASTRUCTURE ONLY.  tests/test_wpr_mac_model*.py and tests/test_wpr_bucket_model_*.py
 hold it against the references, one file per record form; tests/mac_forge.py builds
 ciphertext against its T operand.
@@ -120,7 +120,7 @@ def keying(construction: str, ad: bytes, r: int, n: int = N, tail: int | None = 
     a1 = sum(0x80 << (8 * k) for k in range(G.sigma, 16))
     a2 = sum(0x80 << (8 * k) for k in range(G.sigma))
     bias = g * (a1 * r + a2) * rdel
-    cj = (P - ((1 << 24) * sum(1 << (8 * c) for c in range(32))) % P) % P  # sg_wpr.hip kCJ*
+    cj = (P - ((1 << 24) * sum(1 << (8 * c) for c in range(32))) % P) % P  # sg_wpr_layout.h kCJ*
     seed = cj * sw
     pre = ad + (bytes(G.o - adlen) if construction == RFC8439 else struct.pack("<Q", adlen))
     hp = 0

@@ -14,6 +14,8 @@ kernel (rocprofv3's demangled name):
                        split into other_full (full-rate opcodes: add, xor,
                        and, or, mov, right shifts, bitop3) and other_half
   mfma, lds, vmem, salu
+  skeleton             a hash of the kernel's ordered memory, wait, barrier and
+                       MFMA opcodes (isa_count.skeleton)
   clk_per_valu         the issue model's clocks per VALU instruction of this
                        mix: full-rate opcodes 2 (paired with the SIMD's other
                        lock-step wave, as the FF A/B of profiles/r04_ab shows
@@ -25,8 +27,8 @@ Usage: python tools/isa_census.py [--keep DIR] [--against profiles/isa_<parent h
 
 --against compares this tree's census with an earlier one and writes only the
 comparison, profiles/isa_<hash>_vs_<parent hash>.json: how many of the parent's
-entries are identical in every field, the names of those that changed or are
-gone, and every new kernel with its registers, VALU, LDS and scratch (the whole
+entries are identical in every field, those that changed with the names of
+the fields that differ, those that are gone, and every new kernel with its registers, VALU, LDS and scratch (the whole
 census of a tree with every record form is some 16,000 lines).
 """
 from __future__ import annotations
@@ -52,6 +54,13 @@ DRAFT_ARG = ", (sg::Construction)0"  # Construction::kDraft as c++filt prints it
 T13_KERNELS = ("sg_wpr_kernel<", "sg_wpr_keying_kernel<", "sg_aead_kernel<", "sg_aead_list_kernel<", "sg_keying_kernel<",
                "sg_classify_kernel<", "sg_pack_kernel<")
 T13_OFF = ", false>("
+
+
+# every file of the library that holds a kernel (one that the tree does not have yet is passed over, so
+# that the tool can take the census of an earlier commit)
+SOURCES = [_build.CSRC / f for f in ("sg_wpr.hip", "sg_wpr_keying.hip", "sg_pack.hip", "sg_kernels.hip", "sg_plumb.hip",
+                                     "sg_msg.hip", "sg_msg_batch.hip", "sg_quic.hip", "sg_hkdf.hip")
+           if (_build.CSRC / f).exists()]
 
 
 def demangle(names):
@@ -109,6 +118,7 @@ def census_file(path: Path):
         out[dem]["whole"] = {"arx_full": waf, "arx_rot": war, "other_full": wof,
                              "other_half": sum(woth.values()) - wof, "valu": wtot}
         out[dem]["resources"] = res.get(mangled, {})
+        out[dem]["skeleton"] = ic.skeleton(body_all)  # the order its counted waits and barriers depend on
         out[dem]["clk_per_valu_whole"] =round((2 * (waf + wof) + 4 * (wtot - waf - wof)) / wtot, 4) if wtot else None
     return out
 
@@ -120,8 +130,12 @@ def compare(parent: dict, kernels: dict) -> dict:
         return {"vgpr": r.get("vgpr_count"), "sgpr": r.get("sgpr_count"), "valu": v["whole"]["valu"], "mfma": v["mfma"],
                 "lds_bytes": r.get("group_segment_fixed_size"), "scratch_bytes": r.get("private_segment_fixed_size")}
 
-    return {"parent_entries": len(parent), "identical": sum(1 for k in parent if kernels.get(k) == parent[k]),
-            "changed": sorted(k for k in parent if k in kernels and kernels[k] != parent[k]),
+    def fields(k):  # the fields of k that differ (a census from before the skeleton field: compared without it)
+        new = kernels[k] if "skeleton" in parent[k] else {f: v for f, v in kernels[k].items() if f != "skeleton"}
+        return sorted(f for f in set(new) | set(parent[k]) if new.get(f) != parent[k].get(f))
+
+    return {"parent_entries": len(parent), "identical": sum(1 for k in parent if k in kernels and not fields(k)),
+            "changed": {k: fields(k) for k in sorted(parent) if k in kernels and fields(k)},
             "missing": sorted(k for k in parent if k not in kernels),
             # a kernel that only gained a template argument is its parent's entry under a longer name
             "renamed": sum(1 for k in kernels if k not in parent and T13_OFF in k and k.replace(T13_OFF, ">(") in parent),
@@ -130,10 +144,11 @@ def compare(parent: dict, kernels: dict) -> dict:
 
 
 def dump_compact(cmp: dict) -> str:
-    """JSON with one new kernel per line."""
-    head = {k: v for k, v in cmp.items() if k != "new"}
-    rows = ",\n".join(f"  {json.dumps(k)}: {json.dumps(v)}" for k, v in cmp["new"].items())
-    return json.dumps(head, indent=1)[:-2] + ',\n "new": {\n' + rows + "\n }\n}\n"
+    """JSON with one changed and one new kernel per line."""
+    head = {k: v for k, v in cmp.items() if k not in ("changed", "new")}
+    rows = {f: ",\n".join(f"  {json.dumps(k)}: {json.dumps(v)}" for k, v in cmp[f].items()) for f in ("changed", "new")}
+    return (json.dumps(head, indent=1)[:-2] + ',\n "changed": {\n' + rows["changed"] + '\n },\n "new": {\n' + rows["new"]
+            + "\n }\n}\n")
 
 
 def main():
@@ -146,8 +161,7 @@ def main():
     with tempfile.TemporaryDirectory(prefix="sg_isa_") as td:
         wd = keep or Path(td)
         kernels = {}
-        for s in (_build.CSRC / "sg_wpr.hip", _build.CSRC / "sg_pack.hip", _build.CSRC / "sg_kernels.hip",
-                  _build.CSRC / "sg_plumb.hip", _build.CSRC / "sg_msg.hip", _build.CSRC / "sg_msg_batch.hip"):
+        for s in SOURCES:
             flags = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-mllvm",
                      "-amdgpu-atomic-optimizer-strategy=None", "--save-temps", f'-DSG_SOURCE_HASH="{src}"']
             subprocess.run([_build.hipcc(), *flags, "-c", "-o", str(wd / f"{s.stem}.o"), str(s)], cwd=wd, check=True,

@@ -98,6 +98,30 @@ def census(body, blocks=False):
     return arx, other, kinds, per_block
 
 
+SKELETON = ("global_", "flat_", "ds_", "s_load", "s_barrier", "v_mfma")
+
+
+def skeleton(body) -> str:
+    """Hash of the kernel's memory and synchronisation skeleton: the ordered
+    opcodes of its global_* / flat_* / ds_* / s_load* / v_mfma* instructions and
+    s_barrier, and every s_waitcnt with its operands -- inline asm included, no
+    registers, no s_nop.  A hand-counted vmcnt wait or a lock-step barrier holds
+    as long as this sequence does, whatever the scheduler did between its
+    members."""
+    import hashlib
+
+    seq = []
+    for l in body:
+        s = l.split(";")[0].split()
+        if not s or s[0].endswith(":") or s[0].startswith("."):
+            continue
+        if s[0] == "s_waitcnt":
+            seq.append(" ".join(s))
+        elif s[0].startswith(SKELETON):
+            seq.append(s[0])
+    return hashlib.sha256("\n".join(seq).encode()).hexdigest()[:16]
+
+
 def loop_body(lines):
     """Lines of the kernel's main loop: the smallest loop (a label and a
     backward branch to it) that contains every ChaCha20 double-round asm block

@@ -25,6 +25,7 @@ import isa_count as ic  # noqa: E402
 from suruga_amd import _build  # noqa: E402
 
 KERNEL = "sg_wpr_kernelILb0ELb1ELj4ELb0E"  # seal, TLS, 16 KiB, uniform
+SOURCE = "sg_wpr.hip"  # the file that holds it (its keying pre-pass, sg_wpr_keying.hip, is not part of this census)
 
 
 def census(edits):
@@ -41,9 +42,9 @@ def census(edits):
             f.write_text(txt.replace(old, new))
         subprocess.run([_build.hipcc(), "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-mllvm",
                         "-amdgpu-atomic-optimizer-strategy=None", "--save-temps", f"-I{tdp / 'include'}",
-                        '-DSG_SOURCE_HASH="x"', "-c", "-o", "w.o", str(tdp / "pkg" / "csrc" / "sg_wpr.hip")],
+                        '-DSG_SOURCE_HASH="x"', "-c", "-o", "w.o", str(tdp / "pkg" / "csrc" / SOURCE)],
                        cwd=tdp, check=True, capture_output=True)
-        body = ic.loop_body(ic.kernel_lines(str(tdp / "sg_wpr-hip-amdgcn-amd-amdhsa-gfx950.s"), KERNEL))
+        body = ic.loop_body(ic.kernel_lines(str(tdp / f"{Path(SOURCE).stem}-hip-amdgcn-amd-amdhsa-gfx950.s"), KERNEL))
         arx, other, kinds, _ = ic.census(body)
         return {"arx": sum(arx.values()), "other": sum(other.values()), "mfma": kinds.get("mfma", 0),
                 "lds": kinds.get("lds", 0), "other_by_op": dict(other)}

@@ -20,10 +20,10 @@ EDITS = [
     return;"""),
     ("sg_wpr.hip", """                gst16(pend_dst + 1024u * k + 16u * ln, ld16(pb + 1024u * k + 16u * wunit));""",
      """                asm volatile("" :: "v"(ld16(pb + 1024u * k + 16u * wunit)));"""),
-    ("sg_wpr.hip", """                st16(outb + n, u32x4{tw[0], tw[1], tw[2], tw[3]});  // ct || tag (chacha20_poly1305.rs:55)""",
-     """                asm volatile("" :: "v"(tw[0]), "v"(tw[1]), "v"(tw[2]), "v"(tw[3]));"""),
-    ("sg_wpr.hip", """                p.status[cd.rec] = tag_mismatch(rxl, tw);""",
-     """                asm volatile("" :: "v"((uint32_t)tag_mismatch(rxl, tw)));"""),
+    ("sg_wpr.hip", """        st16(tagp, tw);  // ct || tag (chacha20_poly1305.rs:55)""",
+     """        asm volatile("" :: "v"(tw[0]), "v"(tw[1]), "v"(tw[2]), "v"(tw[3]));"""),
+    ("sg_wpr.hip", """            *status = tag_mismatch(rxl, tw);""",
+     """            asm volatile("" :: "v"((uint32_t)tag_mismatch(rxl, tw)));"""),
     ("sg_wpr.hip", """        auto mac_load = [&](uint32_t jj, uint32_t i, MacRaw& R) {
 """, """        auto mac_load = [&](uint32_t jj, uint32_t i, MacRaw& R) {
             return;
