@@ -230,29 +230,30 @@ __device__ __forceinline__ F26 fmul_add(const F26 a, const F26 b, const F26 c) {
     return mul_add(a, b.v0, b.v1, b.v2, b.v3, b.v4, c);
 }
 
-// One carry pass over limbs < 2^32 (value unchanged mod p): limbs < 2^26 + 2^8.
-__device__ __forceinline__ F26 carry1(F26 f) {
+// One radix-2^26 pass, limb 0 up to limb 4 and limb 4's carry times 5 back into limb 0
+// (2^130 == 5 mod p): value unchanged mod p, limbs 1..4 < 2^26.
+__device__ __forceinline__ void carry_pass(F26& f) {
     uint32_t c;
     c = f.v0 >> 26; f.v0 &= M26; f.v1 += c;
     c = f.v1 >> 26; f.v1 &= M26; f.v2 += c;
     c = f.v2 >> 26; f.v2 &= M26; f.v3 += c;
     c = f.v3 >> 26; f.v3 &= M26; f.v4 += c;
     c = f.v4 >> 26; f.v4 &= M26; f.v0 += c * 5u;
-    c = f.v0 >> 26; f.v0 &= M26; f.v1 += c;
+}
+
+// One carry pass over limbs < 2^32 (value unchanged mod p): limbs < 2^26 + 2^8.
+__device__ __forceinline__ F26 carry1(F26 f) {
+    carry_pass(f);
+    const uint32_t c = f.v0 >> 26;
+    f.v0 &= M26;
+    f.v1 += c;
     return f;
 }
 
 // Strict normal form: every limb < 2^26 (value < 2^130), for limbs < 2^32.
 __device__ __forceinline__ F26 ripple_full(F26 h) {
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        uint32_t c;
-        c = h.v0 >> 26; h.v0 &= M26; h.v1 += c;
-        c = h.v1 >> 26; h.v1 &= M26; h.v2 += c;
-        c = h.v2 >> 26; h.v2 &= M26; h.v3 += c;
-        c = h.v3 >> 26; h.v3 &= M26; h.v4 += c;
-        c = h.v4 >> 26; h.v4 &= M26; h.v0 += c * 5u;
-    }
+    carry_pass(h);
+    carry_pass(h);
     // a second-pass fold implies v1..v4 wrapped to 0, so this cannot overflow v1
     const uint32_t c = h.v0 >> 26;
     h.v0 &= M26;
@@ -471,6 +472,17 @@ __device__ __forceinline__ RecKey record_key(const KParams& p, uint32_t rec) {
 __device__ __forceinline__ uint32_t record_len(const KParams& p, uint32_t rec) {
     return p.len ? p.len[rec] : p.uniform_len;
 }
+// The AEAD's input length of a record of len bytes: an open's ciphertext without its tag (0
+// for a record too short to hold one), a TLS 1.3 seal's inner plaintext, otherwise the record.
+template <bool OPEN, bool T13>
+__device__ __forceinline__ uint32_t aead_len(const KParams& p, uint32_t len) {
+    return OPEN ? (len >= 16u ? len - 16u : 0u) : T13 ? tls13_inner_len(len, p.pad_to) : len;
+}
+// The AD's length: the TLS 1.3 record header, the TLS 1.2 record-layer AD, or the call's.
+template <bool T13>
+__device__ __forceinline__ uint32_t ad_len(const KParams& p) {
+    return T13 ? 5u : p.tls ? 13u : p.ad_len;
+}
 // byte offset of record rec in the batch's input / output
 __device__ __forceinline__ uint64_t rec_in_off(const KParams& p, uint32_t rec) {
     return p.in_off ? p.in_off[rec] : p.in_stride * rec;
@@ -503,13 +515,21 @@ __device__ __forceinline__ uint8_t tls13_inner_type(const KParams& p, uint32_t r
     return p.inner_types ? p.inner_types[rec] : (uint8_t)p.tls_hdr;
 }
 
+// AD byte i (< ad_len<T13>(p)) of a record of n AEAD input bytes: the TLS 1.3 record header
+// (fragment length n + 16), the TLS 1.2 record-layer AD, or the call's own AD bytes
+template <bool T13>
+__device__ __forceinline__ uint8_t ad_byte(const KParams& p, uint32_t rec, uint64_t seq, uint32_t n, uint32_t i) {
+    if constexpr (T13) return tls13_ad_byte(n + 16u, i);
+    else return p.tls ? tls_ad_byte(seq, p.tls_hdr, n, i) : p.ads[(uint64_t)p.ad_stride * rec + i];
+}
+
 // Byte i (< ct_offset<C>(adlen)) of the MAC stream in front of the ciphertext:
 // ad || le64(|ad|) in the draft (chacha20_poly1305.rs:24-26), ad and its zero
 // padding in RFC 8439.
-template <Construction C>
+template <Construction C, bool T13 = false>
 __device__ __forceinline__ uint8_t prefix_byte(const KParams& p, uint32_t rec, uint64_t seq, uint32_t n, uint32_t adlen,
                                                uint32_t i) {
-    if (i < adlen) return p.tls ? tls_ad_byte(seq, p.tls_hdr, n, i) : p.ads[(uint64_t)p.ad_stride * rec + i];
+    if (i < adlen) return ad_byte<T13>(p, rec, seq, n, i);
     if constexpr (C == Construction::kRfc8439) return 0u;
     else return (uint8_t)((uint64_t)adlen >> (8u * (i - adlen)));
 }

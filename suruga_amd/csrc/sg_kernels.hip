@@ -51,6 +51,11 @@
 // beyond len is read.  The instantiations without T13 compile to what they were
 // before the parameter.
 //
+// A record's body is aead_record: record_lens, the LDS layout, phase 1 (class_keystream per
+// block), the MAC stream framing (ad_byte), load_tag, the lane's Horner run, its weight, the DPP
+// sum, finish_tag, store_tag or the compare.  The comment in front of it says which
+// of these are functions and which stay in its body.
+//
 // The launchers at the end are what the rest of the library sees of this file
 // (sg_internal.h); the dispatcher of a batch is sg_dispatch.cpp.
 #include "sg_internal.h"
@@ -153,7 +158,7 @@ __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const Ke
     recs[lane] = rec;
     uint32_t* out = stage + lane * kKeyLdsStride;
     const uint32_t len = act ? record_len(p, rec) : 0u;
-    const uint32_t n = OPEN ? (len >= 16u ? len - 16u : 0u) : T13 ? tls13_inner_len(len, p.pad_to) : len;
+    const uint32_t n = aead_len<OPEN, T13>(p, len);
     out[kKeyRecWords] = 0u;  // nothing to write unless keyed below
     if (act) {
         const RecKey rk = record_key<C>(p, rec);
@@ -168,7 +173,7 @@ __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const Ke
         out[kSOff + 1] = pk.s[1];
         out[kSOff + 2] = pk.s[2];
         out[kSOff + 3] = pk.s[3];
-        const uint32_t adlen = T13 ? 5u : p.tls ? 13u : p.ad_len;
+        const uint32_t adlen = ad_len<T13>(p);
         const MacGeom g = mac_geom<C>(adlen, n, mac_lanes(n));
         const F26 r = words_to_f26(pk.r0, pk.r1, pk.r2, pk.r3, 0u);
         // R = r^k by square-and-multiply; then R^0..R^7 and R^0, R^8, .., R^56.
@@ -222,30 +227,103 @@ __global__ __launch_bounds__(64) void sg_keying_kernel(const KParams p, const Ke
 // reads len content bytes, appends the inner type byte and pads with zeros to n,
 // so the block that holds the type takes the byte path; the AD is the 5-byte
 // record header.
+//
+// The steps of aead_record that stand as functions in front of it: record_lens, class_keystream,
+// load_tag / store_tag, finish_tag (and ad_byte, tag_mismatch of sg_device.h).  The
+// LDS layout, the two phase-1 block forms, the MAC stream framing, the lane's Horner run, its
+// weight and the DPP sum stay in the body under their phase comments: as functions each of them
+// changed registers or the order of memory operations of some instantiations (end of
+// section 4.3).
+
+// The record's length len, the AEAD's input length n (open: without the tag; TLS 1.3 seal: the
+// inner plaintext) and whether the group works on the record: a slot without one does not, and an
+// open too short for a tag is flagged (chacha20_poly1305.rs:68-70 "message too short").
+struct RecLens {
+    uint32_t len, n;
+    bool work;
+};
+template <bool OPEN, bool T13>
+__device__ __forceinline__ RecLens record_lens(const KParams& p, const uint32_t rec, const bool active,
+                                               const uint32_t t) {
+    RecLens q = {active ? record_len(p, rec) : 0u, 0u, active};
+    if (active) {
+        q.n = aead_len<false, T13 && !OPEN>(p, q.len);
+        if constexpr (OPEN) {
+            if (q.len < 16u) {
+                if (t == 0) p.status[rec] = 2u;
+                q.work = false;
+            }
+            q.n = q.len - 16u;  // (unguarded: n is not used when len < 16)
+        }
+    }
+    return q;
+}
+
+// Keystream block ctr of the record: a class whose groups are whole waves (L >= 64) starts from
+// the counter-free part of round 1 (pre = chacha_pre of the record, sg_device.h)
+template <uint32_t L>
+__device__ __forceinline__ void class_keystream(uint32_t ks[16], const ChaChaPre& pre, const RecKey& rk,
+                                                const uint32_t ctr) {
+    if constexpr (L >= 64u) chacha_block_pre(ks, pre, rk.k, ctr, rk.n13, rk.n14, rk.n15);
+    else chacha_block(ks, rk.k, ctr, rk.n13, rk.n14, rk.n15);
+}
+
+// The 16 tag bytes at any alignment as four little-endian words: aligned words, or bytes.
+// (load_tag: rx is zero on entry)
+__device__ __forceinline__ void load_tag(const uint8_t* ep, uint32_t rx[4]) {
+    if ((((uintptr_t)ep) & 3u) == 0u) {
+        const uint32_t* e32 = reinterpret_cast<const uint32_t*>(ep);
+        rx[0] = e32[0]; rx[1] = e32[1]; rx[2] = e32[2]; rx[3] = e32[3];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) rx[i >> 2] |= (uint32_t)ep[i] << (8 * (i & 3));
+    }
+}
+__device__ __forceinline__ void store_tag(uint8_t* tp, const uint32_t tw[4]) {
+    if ((((uintptr_t)tp) & 3u) == 0u) {
+        uint32_t* t32 = reinterpret_cast<uint32_t*>(tp);
+        t32[0] = tw[0]; t32[1] = tw[1]; t32[2] = tw[2]; t32[3] = tw[3];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) tp[i] = (uint8_t)(tw[i >> 2] >> (8 * (i & 3)));
+    }
+}
+
+// The finish: the tag words tw of the group's sum f (held by its last lane) and the keying
+// record's s; true in the lane that holds them, PL - 1.
+template <uint32_t PL>
+__device__ __forceinline__ bool finish_tag(const F26& f, const uint32_t* kr, const uint32_t t, uint32_t tw[4]) {
+    if constexpr (PL == 64u) {
+        // one record per wave: lift the sum out of lane 63 into SGPRs so the
+        // final reduction and s addition run on the scalar unit instead of
+        // occupying the whole wave's VALU for one lane's arithmetic
+        auto lane63 = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readlane((int)x, 63); };
+        const F26 fs = {lane63(f.v0), lane63(f.v1), lane63(f.v2), lane63(f.v3), lane63(f.v4)};
+        uint32_t s[4] = {uniform(kr[kSOff + 0]), uniform(kr[kSOff + 1]), uniform(kr[kSOff + 2]),
+                         uniform(kr[kSOff + 3])};
+        tag_words(fs, s, tw);
+        return t == PL - 1u;
+    } else {
+        if (t != PL - 1u) return false;
+        uint32_t s[4] = {kr[kSOff + 0], kr[kSOff + 1], kr[kSOff + 2], kr[kSOff + 3]};
+        tag_words(f, s, tw);
+        return true;
+    }
+}
+
 template <bool OPEN, uint32_t L, Construction C, bool T13>
 __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec, const bool active,
                                             uint8_t* lds, const uint32_t t) {
     constexpr uint32_t PL = L < 64u ? L : 64u;
+    constexpr bool SEAL13 = T13 && !OPEN;
     constexpr uint32_t Z = 32u * PL;  // space for the virtual blocks in front: 16 * max z
-    uint32_t n = 0;
-    bool work = active;
-    const uint32_t len = active ? record_len(p, rec) : 0u;
-    if (active) {
-        n = T13 && !OPEN ? tls13_inner_len(len, p.pad_to) : len;
-        if constexpr (OPEN) {
-            if (len < 16u) {  // chacha20_poly1305.rs:68-70 "message too short"
-                if (t == 0) p.status[rec] = 2u;
-                work = false;
-            }
-            n = len - 16u;
-        }
-    }
+    constexpr bool RFC = C == Construction::kRfc8439;
+    const RecLens q = record_lens<OPEN, T13>(p, rec, active, t);
+    const uint32_t len = q.len, n = q.n;
+    const bool work = q.work;
     const uint8_t* in = nullptr;
     uint8_t* out = nullptr;
-    constexpr bool RFC = C == Construction::kRfc8439;
-    RecKey rk = {};
-    uint8_t type = 0u;  // T13 seal: the inner type byte behind the content
-    const uint32_t adlen = T13 ? 5u : p.tls ? 13u : p.ad_len;
+    const uint32_t adlen = ad_len<T13>(p);
     // RFC 8439: [Z, A) ad and its zero padding | A: ct (n) | zeros to 16 | le64(adlen) le64(n)
     // A = Z + 16 ceil(ct_offset<C>(adlen) / 16) and S = A - ct_offset<C>(adlen) (sg_layout.h), spelt by
     // hand: taken from the header, 76 of this file's 102 kernels came out with other instructions
@@ -258,8 +336,9 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
     if (work) {
         in = p.in + rec_in_off(p, rec);
         out = p.out + rec_out_off(p, rec);
-        rk = record_key<C>(p, rec);
-        if constexpr (T13 && !OPEN) type = tls13_inner_type(p, rec);
+        const RecKey rk = record_key<C>(p, rec);
+        uint8_t type = 0u;  // T13 seal: the inner type byte behind the content
+        if constexpr (SEAL13) type = tls13_inner_type(p, rec);
 
         // ---- phase 1: keystream XOR, 64 bytes per lane-block ----------------
         const bool vec_ok = (((uintptr_t)in | (uintptr_t)out) & 15u) == 0u;
@@ -269,8 +348,8 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
         for (uint32_t b = t; b < nblocks; b += L) {
             const uint32_t off = b << 6;
             // (T13 seal: a block of content alone; or one of padding alone, which reads nothing)
-            const bool zeros = T13 && !OPEN && off > len;
-            if (vec_ok && (off + 64u <= (T13 && !OPEN ? len : n) || (zeros && off + 64u <= n))) {
+            const bool zeros = SEAL13 && off > len;
+            if (vec_ok && (off + 64u <= (SEAL13 ? len : n) || (zeros && off + 64u <= n))) {
                 u32x4 d0 = {}, d1 = {}, d2 = {}, d3 = {};
                 if (!zeros) {
                     d0 = ld16(in + off);
@@ -279,9 +358,7 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
                     d3 = ld16(in + off + 48);
                 }
                 uint32_t ks[16];
-                // data uses blocks 1.. (chacha20_poly1305.rs:52)
-                if constexpr (L >= 64u) chacha_block_pre(ks, pre, rk.k, b + 1u, rk.n13, rk.n14, rk.n15);
-                else chacha_block(ks, rk.k, b + 1u, rk.n13, rk.n14, rk.n15);
+                class_keystream<L>(ks, pre, rk, b + 1u);  // data uses blocks 1.. (chacha20_poly1305.rs:52)
                 const u32x4 r0 = d0 ^ u32x4{ks[0], ks[1], ks[2], ks[3]};
                 const u32x4 r1 = d1 ^ u32x4{ks[4], ks[5], ks[6], ks[7]};
                 const u32x4 r2 = d2 ^ u32x4{ks[8], ks[9], ks[10], ks[11]};
@@ -304,8 +381,7 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
             } else {
                 // partial last block or misaligned record: byte granular
                 uint32_t ks[16];
-                if constexpr (L >= 64u) chacha_block_pre(ks, pre, rk.k, b + 1u, rk.n13, rk.n14, rk.n15);
-                else chacha_block(ks, rk.k, b + 1u, rk.n13, rk.n14, rk.n15);
+                class_keystream<L>(ks, pre, rk, b + 1u);
 #pragma unroll
                 for (uint32_t w = 0; w < 16; ++w) {
 #pragma unroll
@@ -313,7 +389,7 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
                         const uint32_t idx = off + 4u * w + k;
                         if (idx < n) {
                             uint8_t x;
-                            if constexpr (T13 && !OPEN) x = idx < len ? in[idx] : idx == len ? type : (uint8_t)0u;  // content || type || zeros
+                            if constexpr (SEAL13) x = idx < len ? in[idx] : idx == len ? type : (uint8_t)0u;  // content || type || zeros
                             else x = in[idx];
                             const uint8_t y = x ^ (uint8_t)(ks[w] >> (8u * k));
                             out[idx] = y;
@@ -329,10 +405,7 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
             // ad || 0.. (to 16) || ct || 0.. (to 16) || le64(|ad|) || le64(|ct|)  (RFC 8439 section 2.8)
             for (uint32_t i = t; i < A - Z; i += PL) {
                 uint8_t v = 0u;
-                if constexpr (T13) {
-                    if (i < adlen) v = tls13_ad_byte(n + 16u, i);
-                } else if (i < adlen)
-                    v = p.tls ? tls_ad_byte(rk.seq, p.tls_hdr, n, i) : p.ads[(uint64_t)p.ad_stride * rec + i];
+                if (i < adlen) v = ad_byte<T13>(p, rec, rk.seq, n, i);
                 lds[S + i] = v;
             }
             const uint32_t zp = (0u - n) & 15u;  // zeros to the end of the last ciphertext block
@@ -347,7 +420,7 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
             for (uint32_t i = t; i < adlen + 8u; i += PL) {
                 uint8_t v;
                 if (i < adlen)
-                    v = p.tls ? tls_ad_byte(rk.seq, p.tls_hdr, n, i) : p.ads[(uint64_t)p.ad_stride * rec + i];
+                    v = ad_byte<T13>(p, rec, rk.seq, n, i);
                 else
                     v = (uint8_t)((uint64_t)adlen >> (8u * (i - adlen)));
                 lds[S + i] = v;
@@ -372,16 +445,7 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
     // that its latency hides behind the Horner loop
     uint32_t rx[4] = {0u, 0u, 0u, 0u};
     if constexpr (OPEN) {
-        if (t == PL - 1u) {  // the lane that finishes the tag
-            const uint8_t* ep = in + n;
-            if ((((uintptr_t)ep) & 3u) == 0u) {
-                const uint32_t* e32 = reinterpret_cast<const uint32_t*>(ep);
-                rx[0] = e32[0]; rx[1] = e32[1]; rx[2] = e32[2]; rx[3] = e32[3];
-            } else {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) rx[i >> 2] |= (uint32_t)ep[i] << (8 * (i & 3));
-            }
-        }
+        if (t == PL - 1u) load_tag(in + n, rx);  // the lane that finishes the tag
     }
 
     // lane t: virtual blocks [t*k, t*k + k); virtual block v is real iff v >= z
@@ -453,6 +517,8 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
     // broadcasts for 32 and 64.  mul_add leaves limbs < 2^27, so 32 terms sum
     // below 2^32; one carry pass precedes the last doubling.
     {
+        // (carry_pass of sg_device.h, spelt out: called from here, or the whole sum as a function
+        // group_sum<PL>, 5 AEAD kernels order their memory operations differently and 100 change length)
         auto carry = [&]() {
             uint32_t c;
             c = f.v0 >> 26; f.v0 &= M26; f.v1 += c;
@@ -478,34 +544,9 @@ __device__ __forceinline__ void aead_record(const KParams& p, const uint32_t rec
         }
     }
     uint32_t tw[4];
-    if constexpr (PL == 64u) {
-        // one record per wave: lift the sum out of lane 63 into SGPRs so the
-        // final reduction and s addition run on the scalar unit instead of
-        // occupying the whole wave's VALU for one lane's arithmetic
-        auto lane63 = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readlane((int)x, 63); };
-        const F26 fs = {lane63(f.v0), lane63(f.v1), lane63(f.v2), lane63(f.v3), lane63(f.v4)};
-        uint32_t s[4] = {uniform(kr[kSOff + 0]), uniform(kr[kSOff + 1]), uniform(kr[kSOff + 2]),
-                         uniform(kr[kSOff + 3])};
-        tag_words(fs, s, tw);
-        if (t != PL - 1u) return;
-    } else {
-        if (t != PL - 1u) return;
-        uint32_t s[4] = {kr[kSOff + 0], kr[kSOff + 1], kr[kSOff + 2], kr[kSOff + 3]};
-        tag_words(f, s, tw);
-    }
-
-    if constexpr (!OPEN) {
-        uint8_t* tp = out + n;  // ct || tag (chacha20_poly1305.rs:55)
-        if ((((uintptr_t)tp) & 3u) == 0u) {
-            uint32_t* t32 = reinterpret_cast<uint32_t*>(tp);
-            t32[0] = tw[0]; t32[1] = tw[1]; t32[2] = tw[2]; t32[3] = tw[3];
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) tp[i] = (uint8_t)(tw[i >> 2] >> (8 * (i & 3)));
-        }
-    } else {
-        p.status[rec] = tag_mismatch(rx, tw);
-    }
+    if (!finish_tag<PL>(f, kr, t, tw)) return;
+    if constexpr (OPEN) p.status[rec] = tag_mismatch(rx, tw);
+    else store_tag(out + n, tw);  // ct || tag (chacha20_poly1305.rs:55)
 }
 
 // Record slot of this lane's group.  For L >= 64 a group is a whole wave (or
@@ -584,7 +625,7 @@ __global__ __launch_bounds__(1024) void sg_classify_kernel(const KParams p, uint
         cls[i] = kNumLists;
         if (rec < p.count) {
             const uint32_t len = record_len(p, rec);
-            const uint32_t n = OPEN ? (len >= 16u ? len - 16u : 0u) : T13 ? tls13_inner_len(len, p.pad_to) : len;
+            const uint32_t n = aead_len<OPEN, T13>(p, len);
             if (n <= max_n) {
                 const uint32_t J = rec_wpr_bucket(p, rec, n);
                 cls[i] = J ? kNumClasses + J - kWprMinJ : rec_pack(p, rec, n) ? kPackList : size_class(n);

@@ -30,6 +30,9 @@
 //     Poly1305 term into the record's LDS accumulator;
 //   finish (waves 0-1, one lane per record): tag = (acc + constant) + s,
 //     appended (seal, :55) or compared in constant time (open, :84-93).
+// pack_run is these steps with every barrier between them; load_record (setup), block_owner
+// (chunks) and finish_record are functions, the constant term is one product sum (put_ctot), and
+// the slot write, the power tables, the lane's input block and the lane term stay in its body.
 //
 // MAC (poly1305.rs:207-228 over ad || le64(13) || ct || le64(n),
 // chacha20_poly1305.rs:19-42).  With the 13-byte TLS AD the ciphertext starts
@@ -277,8 +280,62 @@ __device__ __forceinline__ uint32_t slot_nb(const uint32_t* sl) {
     else return sl[kSNb];
 }
 
+// ---- the steps of pack_run that stand as functions (DESIGN.md section 4.5 lists the others, which
+// stay in its body because as functions they changed a kernel's registers or its order of memory
+// operations) ----
+
+// Setup (a), the loads of one record as three levels (list -> per-record arrays -> key words):
+// its length, the AEAD's input length n, where it lives, key and nonce.
+// Listed records: 64 <= n <= 4096, n % 64 == 0 (T13 seal: the inner length, as classified), so an
+// open's n is len - 16 unguarded (aead_len<true>'s guard reorders two kernels' memory operations).
+struct PackRec {
+    uint32_t len, n;
+    uint64_t io, oo;
+    RecKey rk;
+};
+template <bool OPEN, Construction C, bool T13>
+__device__ __forceinline__ PackRec load_record(const KParams& p, const uint32_t rec) {
+    PackRec q;
+    q.len = record_len(p, rec);
+    q.io = rec_in_off(p, rec);
+    q.oo = rec_out_off(p, rec);
+    q.rk = record_key<C>(p, rec);
+    q.n = OPEN ? q.len - 16u : aead_len<false, T13>(p, q.len);
+    return q;
+}
+
+// The record that owns run block 64 c + lane: the starts at or before it (start bitmap, mbcnt)
+__device__ __forceinline__ uint32_t block_owner(const PackLds& L, const uint32_t c, const uint32_t lane) {
+    const uint32_t mlo = L.bits[2u * c], mhi = L.bits[2u * c + 1u];
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));
+    const uint32_t own = ((lane < 32u ? mlo >> lane : mhi >> (lane - 32u)) & 1u);
+    return L.base[c] + below + own - 1u;
+}
+
+// The finish of one record of n ciphertext bytes: tag = (acc + constant) + s, appended (seal,
+// chacha20_poly1305.rs:55) or compared in constant time (open; rec: the status index)
+template <bool OPEN>
+__device__ __forceinline__ void finish_record(const KParams& p, const uint32_t* sl, const uint32_t* ac,
+                                              const uint32_t n, const uint32_t rec) {
+    // (v1 = lo + hi 2^32 -> hi 2^58 = (hi << 6) 2^52 joins limb 2 after the
+    // first carry pass: limb 2's raw sum can reach 2^32 - 64, and hi <= 1)
+    F26 f = carry1(F26{ac[0], ac[4], ac[1], ac[2], ac[3]});
+    f.v2 += ac[5] << 6;
+    f = carry1(f26_add(f, load_f26(sl + kSCtot)));
+    const uint32_t s[4] = {sl[kSS + 0], sl[kSS + 1], sl[kSS + 2], sl[kSS + 3]};
+    uint32_t tw[4];
+    tag_words(f, s, tw);
+    // (the offsets' two words spelt out here and in the chunk loop: read through a slot_u64(sl, k),
+    // in any of three forms, every packed kernel came out with other registers)
+    const uint64_t io = (uint64_t)sl[kSIn] | ((uint64_t)sl[kSIn + 1] << 32);
+    const uint64_t oo = (uint64_t)sl[kSOut] | ((uint64_t)sl[kSOut + 1] << 32);
+    if constexpr (!OPEN) st16(p.out + oo + n, u32x4{tw[0], tw[1], tw[2], tw[3]});
+    else p.status[rec] = tag_mismatch(ld16(p.in + io + n), tw);
+}
+
 // One run: records first .. first + nrec - 1 of the packed list.
 // T13 (with Construction::kRfc8439 only): the TLS 1.3 record form, header comment.
+// Every barrier that the eight waves must meet alike, and every profiling stamp, stands in this body.
 template <bool OPEN, Construction C, bool T13>
 __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __restrict__ list, const uint32_t first,
                                          const uint32_t nrec, PackLds& L, const uint32_t tid, const uint32_t lane,
@@ -304,12 +361,10 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
         uint32_t* sl = L.slot + m0 * kSlotWords;
         uint32_t* tb = L.tab + m0 * kTabWords;
         if (act) {
-            const uint32_t len = record_len(p, rec);
-            const uint64_t io = rec_in_off(p, rec);
-            const uint64_t oo = rec_out_off(p, rec);
-            const RecKey rk = record_key<C>(p, rec);
-            // listed records: 64 <= n <= 4096, n % 64 == 0 (T13 seal: the inner length, as classified)
-            const uint32_t n = OPEN ? len - 16u : T13 ? tls13_inner_len(len, p.pad_to) : len;
+            const PackRec q = load_record<OPEN, C, T13>(p, rec);
+            const uint32_t len = q.len, n = q.n;
+            const uint64_t io = q.io, oo = q.oo;
+            const RecKey& rk = q.rk;
             nb = n >> 6;
 #if SG_PACK_PROFILE
             if (rk.k[0] == 0x12345678u && rk.seq == 1u) g_pack_prof[0][11] = io + oo;  // wait for the loads
@@ -355,27 +410,26 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
             const uint32_t il = nb - 1u;
             const F26 wl = tab_weight(tb, il);
             const F26 rB = fmul(fmul(wl, R), r);
+            // blk0 r^B + sfx r, blk0 block 0 with its pad 2^128 and sfx the last block's part, per record form
+            // (one function per form that returns the two changed the TLS 1.3 open kernel's registers)
+            auto put_ctot = [&](const F26& blk0, const F26& sfx) {
+                store_f26(sl + kSCtot, fmul_add(blk0, rB, fmul(sfx, r)));
+            };
             // block 0: be64(seq) || type || major || minor || be16(n) || le64(13)[0..3] (tls.rs:103-112)
             const uint32_t w2 = (p.tls_hdr & 0x00ffffffu) | (((n >> 8) & 0xffu) << 24);
             if constexpr (T13) {
                 // block 0: the record header 17 03 03 be16(n + 16) and eleven zero bytes (RFC 8446
-                // section 5.2); last block: le64(5) || le64(n)
+                // section 5.2); last block: le64(5) || le64(n), 5 + n 2^64 + 2^128
                 const uint32_t L = n + 16u;
-                const F26 blk0 = words_to_f26(0x00030317u | ((L >> 8) << 24), L & 0xffu, 0u, 0u, 1u);  // + the pad 2^128
-                const F26 sfx = words_to_f26(5u, 0u, n, 0u, 1u);                                       // 5 + n 2^64 + 2^128
-                store_f26(sl + kSCtot, fmul_add(blk0, rB, fmul(sfx, r)));
+                put_ctot(words_to_f26(0x00030317u | ((L >> 8) << 24), L & 0xffu, 0u, 0u, 1u), words_to_f26(5u, 0u, n, 0u, 1u));
             } else if constexpr (RFC) {
                 // block 0: the AD and three zero bytes; its be64(seq) from the sequence number
-                // (the nonce words carry the write IV, RFC 7905); last block: le64(13) || le64(n)
+                // (the nonce words carry the write IV, RFC 7905); last block: le64(13) || le64(n), 13 + n 2^64 + 2^128
                 const uint32_t a0 = bswap32((uint32_t)(rk.seq >> 32)), a1 = bswap32((uint32_t)rk.seq);
-                const F26 blk0 = words_to_f26(a0, a1, w2, n & 0xffu, 1u);  // + the pad 2^128
-                const F26 sfx = words_to_f26(13u, 0u, n, 0u, 1u);          // 13 + n 2^64 + 2^128
-                store_f26(sl + kSCtot, fmul_add(blk0, rB, fmul(sfx, r)));
-            } else {
+                put_ctot(words_to_f26(a0, a1, w2, n & 0xffu, 1u), words_to_f26(13u, 0u, n, 0u, 1u));
+            } else {  // last block: n 2^40 + 2^104
                 const uint32_t w3 = (n & 0xffu) | (13u << 8);
-                const F26 blk0 = words_to_f26(rk.n14, rk.n15, w2, w3, 1u);   // + the pad 2^128
-                const F26 sfx = words_to_f26(0u, n << 8, 0u, 256u, 0u);      // n 2^40 + 2^104
-                store_f26(sl + kSCtot, fmul_add(blk0, rB, fmul(sfx, r)));
+                put_ctot(words_to_f26(rk.n14, rk.n15, w2, w3, 1u), words_to_f26(0u, n << 8, 0u, 256u, 0u));
             }
         }
         const uint32_t incl = wave_incl_scan(nb, lane);
@@ -436,14 +490,8 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
         }
         const uint32_t b = 64u * c + lane;
         const bool valid = c < nchunks && b < total;
-        // the record of run block b: the starts at or before it
         uint32_t m = 0u;
-        if (c < nchunks) {
-            const uint32_t mlo = L.bits[2u * c], mhi = L.bits[2u * c + 1u];
-            const uint32_t below = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));
-            const uint32_t own = ((lane < 32u ? mlo >> lane : mhi >> (lane - 32u)) & 1u);
-            m = L.base[c] + below + own - 1u;
-        }
+        if (c < nchunks) m = block_owner(L, c, lane);
         if (!valid) m = 0u;
         const uint32_t* sl = L.slot + m * kSlotWords;
         const uint32_t j = b - sl[kSStart];
@@ -547,26 +595,10 @@ __device__ __forceinline__ void pack_run(const KParams& p, const uint32_t* __res
     // ---- finish: one lane per record (waves 0-1) --------------------------------
     if (act) {
         const uint32_t* sl = L.slot + m0 * kSlotWords;
-        const uint32_t n = 64u * slot_nb<T13SEAL>(sl);
         uint32_t rec = 0u;  // (open: the status index)
         if constexpr (!RFC) rec = sl[kSRec];
         else if constexpr (OPEN) rec = list[first + m0];  // the slot word holds n13
-        const uint32_t* ac = L.acc + kAccWords * m0;
-        // (v1 = lo + hi 2^32 -> hi 2^58 = (hi << 6) 2^52 joins limb 2 after the
-        // first carry pass: limb 2's raw sum can reach 2^32 - 64, and hi <= 1)
-        F26 f = carry1(F26{ac[0], ac[4], ac[1], ac[2], ac[3]});
-        f.v2 += ac[5] << 6;
-        f = carry1(f26_add(f, load_f26(sl + kSCtot)));
-        const uint32_t s[4] = {sl[kSS + 0], sl[kSS + 1], sl[kSS + 2], sl[kSS + 3]};
-        uint32_t tw[4];
-        tag_words(f, s, tw);
-        const uint64_t io = (uint64_t)sl[kSIn] | ((uint64_t)sl[kSIn + 1] << 32);
-        const uint64_t oo = (uint64_t)sl[kSOut] | ((uint64_t)sl[kSOut + 1] << 32);
-        if constexpr (!OPEN) {
-            st16(p.out + oo + n, u32x4{tw[0], tw[1], tw[2], tw[3]});  // ct || tag (chacha20_poly1305.rs:55)
-        } else {
-            p.status[rec] = tag_mismatch(ld16(p.in + io + n), tw);
-        }
+        finish_record<OPEN>(p, sl, L.acc + kAccWords * m0, 64u * slot_nb<T13SEAL>(sl), rec);
     }
     SG_STAMP(0u, 5);
 }

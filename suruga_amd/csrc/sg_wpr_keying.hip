@@ -183,7 +183,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void sg
 #pragma unroll
     for (uint32_t i = 0; i < kWprRecWords; ++i) rbuf[i] = 0u;
     uint32_t* st = rbuf + 80;  // the second half first (offsets below are half-relative)
-    const uint32_t adlen = T13 ? 5u : p.tls ? 13u : p.ad_len;
+    const uint32_t adlen = ad_len<T13>(p);
     if (blockIdx.x == b0 && lane == 0u) *wl.ctr = 0u;  // the record kernel's group counter
 
     const bool act = slot < wl.count;

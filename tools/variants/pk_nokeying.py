@@ -35,6 +35,6 @@ EDITS = [
     ("sg_pack.hip", """            const F26 wl = tab_weight(tb, il);
             const F26 rB = fmul(fmul(wl, R), r);""", """            const F26 rB = f26_zero();
             (void)il;"""),
-    ("sg_pack.hip", """            store_f26(sl + kSCtot, fmul_add(blk0, rB, fmul(sfx, r)));""",
-     """            store_f26(sl + kSCtot, f26_add(blk0, f26_add(rB, sfx)));""", "all"),  # both constructions' branches
+    ("sg_pack.hip", """                store_f26(sl + kSCtot, fmul_add(blk0, rB, fmul(sfx, r)));""",
+     """                store_f26(sl + kSCtot, f26_add(blk0, f26_add(rB, sfx)));"""),  # put_ctot: every record form
 ]
