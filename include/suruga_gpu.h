@@ -423,6 +423,102 @@ int sg_open_batch_quic(const sg_quic_batch* b);
  * cut to 8 * pn_len bits. */
 uint64_t sg_quic_decode_pn(uint64_t expected_pn, uint32_t truncated, uint32_t pn_len);
 
+/* ---- WireGuard transport data batch (whitepaper section 5.4.6) ----------------
+ * Many transport data messages sealed or opened in one launch (sg_wg.hip).  The message:
+ *
+ *   le32(4)                       type 4, three reserved zero bytes
+ *   le32(receiver)                the peer's index for this session
+ *   le64(counter)
+ *   AEAD(key, nonce = 00 00 00 00 || le64(counter), plaintext = inner || zeros, AD = empty)   -> P bytes || 16-byte tag
+ *
+ * A message is 32 + P bytes; a keepalive has P = 0.  The AEAD is RFC 8439: ChaCha20
+ * blocks 1 onward, the Poly1305 key from block 0, the MAC over ct || pad16 || le64(0) ||
+ * le64(P).  A generic AEAD call cannot give the two things fused here: the zero padding
+ * of the inner packet on seal, and the inner packet's length from its IP header on open.
+ *
+ * Packet i lies at in + in_off_i (off_i = off ? off[i] : stride * i) and has len_i =
+ * len ? len[i] : uniform_len bytes, as in sg_quic_batch; any alignment of `in`, `out`
+ * and the offsets.  k = min(key_index ? key_index[i] : 0, num_keys - 1) names the row of
+ * `keys` and, on seal, of `receiver`.
+ *
+ * Seal.  The input is the inner packet, len_i bytes (0 allowed), contents not inspected.
+ * P_i = sg_wg_padded_len(len_i, pad_cap): len_i rounded up to 16 and, where pad_cap != 0,
+ * at most max(len_i, pad_cap) -- the Linux implementation's min(MTU, ALIGN(len, 16)) for
+ * len <= MTU; a pad_cap that is no multiple of 16 yields ragged messages, which open
+ * accepts.  The output is 32 + P_i bytes: header (receiver[k], counter[i]), ciphertext,
+ * tag.  Plaintext bytes len_i .. P_i are zero and are never read from the input: no
+ * input byte at or beyond len_i is read.  Status SG_OK, or SG_STATUS_SKIPPED and nothing
+ * written where len_i > max_len.  max_len is at most SG_WG_MAX_MESSAGE_LEN - 32.
+ *
+ * Open.  The input is a message of len_i bytes.  In this order: len_i > max_len is
+ * SG_STATUS_SKIPPED, len_i < 32 is SG_E_SHORT, a type word other than 04 00 00 00 is
+ * SG_STATUS_BAD_HEADER; nothing is written for any of them (counter_out and inner_len
+ * included).  Otherwise the counter is read from bytes 8..16 and n = len_i - 32 bytes are
+ * decrypted into `out`.  Bad tag: SG_E_BAD_MAC, all n output bytes zero, counter_out[i]
+ * 0 and inner_len[i] 0; under SG_WG_KEEP_FAILED the decryption and the wire counter are
+ * left instead and inner_len[i] stays 0: nothing derived from an unauthenticated message
+ * leaves the call by default.  Good tag: counter_out[i] is the counter, and with
+ * inner_len != NULL: n == 0 is a keepalive, inner_len[i] = 0, SG_OK; version nibble 4
+ * needs n >= 20 and L = be16(out[2..4]) with 20 <= L <= n; version nibble 6 needs
+ * n >= 40 and L = 40 + be16(out[4..6]) with L <= n; then inner_len[i] = L, SG_OK.
+ * Anything else is SG_STATUS_BAD_INNER with inner_len[i] = 0, the plaintext and
+ * counter_out[i] left in place: the packet was authentic, and the receiver's replay
+ * window advances for it, as in the Linux receive path.  With inner_len == NULL nothing
+ * is parsed and a good tag is SG_OK.
+ *
+ * In place.  Per packet, `in` and `out` either do not overlap or overlap in exactly one
+ * way, the payload staying at its address: seal out_i + 16 == in_i (16 bytes of headroom
+ * in front of the inner packet, sg_wg_message_len bytes of room from out_i), open
+ * out_i == in_i + 16.  Any other overlap is undefined and not checked (the offsets are
+ * device arrays).
+ *
+ * Left with the caller: the mapping from a received message's receiver index to
+ * key_index; the replay window (RFC 6479) over counter_out; the counter limit
+ * REJECT_AFTER_MESSAGES (2^64 - 2^13 - 1); the allowed-IPs check of the inner source
+ * address; the handshake messages (types 1-3) and their BLAKE2s key derivation.
+ *
+ * One launch, no workspace, no host read-back: the call is capturable.  count == 0
+ * returns SG_OK and launches nothing.  SG_E_ARG before any GPU work: NULL b, unknown
+ * flags, NULL keys / status / in / out, NULL receiver or counter on seal, NULL
+ * counter_out on open, a misaligned per-packet array (4 bytes; 8 for counter,
+ * counter_out, in_off, out_off), num_keys zero, pad_cap above SG_WG_MAX_MESSAGE_LEN - 32,
+ * the length bound above SG_WG_MAX_MESSAGE_LEN (seal: - 32). */
+#define SG_WG_HEADER_LEN      16u
+#define SG_WG_MAX_MESSAGE_LEN 16384u      /* header and tag included */
+#define SG_WG_KEEP_FAILED     0x1u
+#define SG_STATUS_BAD_HEADER  6           /* open: first four bytes are not 04 00 00 00 */
+#define SG_STATUS_BAD_INNER   7           /* open: tag good, inner IP header's length does not fit */
+
+typedef struct sg_wg_batch {
+    uint32_t        count, flags;
+    const uint8_t*  keys;        /* device [num_keys][32]: one row per session direction              */
+    const uint32_t* receiver;    /* seal: device [num_keys], the index written into the header; open: not read */
+    const uint32_t* key_index;   /* device, or NULL: 0                                                */
+    const uint64_t* counter;     /* seal: device, the counter of each packet; open: not read          */
+    uint64_t*       counter_out; /* open: device, the counter read from the wire; seal: not read      */
+    uint32_t*       inner_len;   /* open: device or NULL (above); seal: not read                      */
+    uint32_t        num_keys, pad_cap;
+    const uint8_t*  in;
+    const uint64_t* in_off;
+    uint64_t        in_stride;
+    uint8_t*        out;
+    const uint64_t* out_off;
+    uint64_t        out_stride;
+    const uint32_t* len;
+    uint32_t        uniform_len;
+    uint32_t        max_len;
+    uint8_t*        status;      /* device, count bytes, required for seal and open                   */
+    void*           stream;      /* as sg_batch.stream: non-NULL asynchronous, NULL waits             */
+} sg_wg_batch;                   /* 144 bytes */
+int sg_seal_batch_wg(const sg_wg_batch* b);
+int sg_open_batch_wg(const sg_wg_batch* b);
+
+/* Host only.  sg_wg_padded_len: P of an inner packet of len bytes (above); a len whose
+ * rounding does not fit 32 bits is returned as it is.  sg_wg_message_len: 32 + P, the
+ * room a seal needs from out_i; 0xffffffff where that does not fit 32 bits. */
+uint32_t sg_wg_padded_len(uint32_t len, uint32_t pad_cap);
+uint32_t sg_wg_message_len(uint32_t len, uint32_t pad_cap);
+
 /* ---- long messages: any data and AD length, one message over the whole chip
  * Encryptor::encrypt / Decryptor::decrypt take data and additional data of any
  * length (cipher/mod.rs:22-32, chacha20_poly1305.rs:19-94).  sg_seal, sg_open

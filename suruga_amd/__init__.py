@@ -12,6 +12,8 @@ Layout:
                              sg_write_records_tls13 / sg_read_records_tls13
   suruga_amd/quic.py         QUIC packet protection of a device-resident batch (RFC 9001):
                              AEAD and header protection, seal_quic / open_quic
+  suruga_amd/wg.py           WireGuard transport data messages of a device-resident batch:
+                             header, zero padding, AEAD and the inner length, seal_wg / open_wg
   suruga_amd/_native.py      ctypes binding of libsuruga_gpu.so
 
 The HIP library is the only compute path; importing the cipher classes works
@@ -22,11 +24,13 @@ from .cipher import (Aead, ChaCha20Poly1305, ChaCha20Poly1305Decryptor, ChaCha20
                      ChaCha20Poly1305Rfc8439, CipherSuite, Decryptor, Encryptor, TlsError, TlsErrorKind)
 from .keysched import quic_packet_keys
 from .quic import QuicBatch, decode_pn, open_quic, seal_quic
+from .wg import SG_STATUS_BAD_HEADER, SG_STATUS_BAD_INNER, WgBatch, message_len, open_wg, padded_len, seal_wg
 
 __all__ = [
     "Aead", "ChaCha20Poly1305", "ChaCha20Poly1305Decryptor", "ChaCha20Poly1305Encryptor", "ChaCha20Poly1305Rfc8439",
     "CipherSuite", "Decryptor", "Encryptor", "TlsError", "TlsErrorKind", "load_native",
     "QuicBatch", "seal_quic", "open_quic", "decode_pn", "quic_packet_keys",
+    "WgBatch", "seal_wg", "open_wg", "padded_len", "message_len", "SG_STATUS_BAD_HEADER", "SG_STATUS_BAD_INNER",
 ]
 
 

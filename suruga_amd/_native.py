@@ -58,6 +58,7 @@ EXPORTS = [
     "sg_msg_batch_workspace_size", "sg_seal_msg_batch", "sg_open_msg_batch", "sg_msg_batch_plan_for",
     "sg_msg_batch_plan_for_flags",
     "sg_seal_batch_quic", "sg_open_batch_quic", "sg_quic_decode_pn", "sg_quic_packet_keys",
+    "sg_seal_batch_wg", "sg_open_batch_wg", "sg_wg_padded_len", "sg_wg_message_len",
 ]
 SG_MSG_BATCH_MAX_COUNT = 1 << 20
 SG_MSG_MAX_GROUPS = 1024
@@ -150,6 +151,41 @@ class SgQuicBatch(C.Structure):
         ("pn_off", C.c_void_p),
         ("num_keys", C.c_uint32),
         ("uniform_pn_off", C.c_uint32),
+        ("in_", C.c_void_p),
+        ("in_off", C.c_void_p),
+        ("in_stride", C.c_uint64),
+        ("out", C.c_void_p),
+        ("out_off", C.c_void_p),
+        ("out_stride", C.c_uint64),
+        ("len", C.c_void_p),
+        ("uniform_len", C.c_uint32),
+        ("max_len", C.c_uint32),
+        ("status", C.c_void_p),
+        ("stream", C.c_void_p),
+    ]
+
+
+SG_WG_HEADER_LEN = 16
+SG_WG_MAX_MESSAGE_LEN = 16384
+SG_WG_KEEP_FAILED = 0x1
+SG_STATUS_BAD_HEADER = 6
+SG_STATUS_BAD_INNER = 7
+
+
+class SgWgBatch(C.Structure):
+    """Mirror of ``struct sg_wg_batch``."""
+
+    _fields_ = [
+        ("count", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("keys", C.c_void_p),
+        ("receiver", C.c_void_p),
+        ("key_index", C.c_void_p),
+        ("counter", C.c_void_p),
+        ("counter_out", C.c_void_p),
+        ("inner_len", C.c_void_p),
+        ("num_keys", C.c_uint32),
+        ("pad_cap", C.c_uint32),
         ("in_", C.c_void_p),
         ("in_off", C.c_void_p),
         ("in_stride", C.c_uint64),
@@ -430,6 +466,12 @@ def _declare(lib: C.CDLL) -> None:
     lib.sg_quic_decode_pn.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
     lib.sg_quic_packet_keys.restype = C.c_int
     lib.sg_quic_packet_keys.argtypes = [C.c_uint32, vp, vp, vp, vp, C.c_int, C.c_int]
+    for f in (lib.sg_seal_batch_wg, lib.sg_open_batch_wg):
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(SgWgBatch)]
+    for f in (lib.sg_wg_padded_len, lib.sg_wg_message_len):
+        f.restype = C.c_uint32
+        f.argtypes = [C.c_uint32, C.c_uint32]
     lib.sg_ctx_set_traffic_secret.restype = C.c_int
     lib.sg_ctx_set_traffic_secret.argtypes = [C.c_void_p, C.c_char_p]
     lib.sg_ctx_key_update.restype = C.c_int
