@@ -519,6 +519,123 @@ int sg_open_batch_wg(const sg_wg_batch* b);
 uint32_t sg_wg_padded_len(uint32_t len, uint32_t pad_cap);
 uint32_t sg_wg_message_len(uint32_t len, uint32_t pad_cap);
 
+/* ---- IPsec ESP batch, ChaCha20-Poly1305 (RFC 7634 over RFC 4303) ---------------
+ * Many ESP packets sealed or opened in one launch (sg_esp.hip).  The packet:
+ *
+ *   be32(spi)
+ *   be32(seq_lo)                        low 32 bits of the sequence number
+ *   iv, 8 bytes                         be64(iv_i)
+ *   AEAD(key, nonce = salt(4) || iv(8),
+ *        plaintext = payload || 01 02 .. pad || u8(pad) || u8(next_header),
+ *        AD = be32(spi) || be32(seq_lo)                  (8 bytes), or under SG_ESP_ESN
+ *             be32(spi) || be32(seq_hi) || be32(seq_lo)  (12 bytes; seq_hi is not on the wire))
+ *                                       -> P bytes || 16-byte ICV
+ *
+ * A packet is 32 + P bytes: 16 bytes of header, P bytes of ciphertext and a 16-byte ICV.
+ * The AEAD is RFC 8439: ChaCha20 blocks 1 onward, the Poly1305 key from block 0, the MAC
+ * over pad16(AD) || ct || pad16 || le64(|AD|) || le64(P).  A generic AEAD call leaves the
+ * nonce, the AD with its implicit high half, the trailer and, on receive, the look at the
+ * plaintext that finds the trailer to the host; here they are part of the launch.
+ *
+ * Packet i lies at in + in_off_i (off_i = off ? off[i] : stride * i) and has len_i =
+ * len ? len[i] : uniform_len bytes, as in sg_wg_batch; any alignment of `in`, `out` and
+ * the offsets.  k = min(sa_index ? sa_index[i] : 0, num_sas - 1) names the row of `keys`,
+ * `salts`, `spi` and `replay_top`: one row per security association and direction.
+ *
+ * Seal.  The input is the payload, len_i bytes (0 allowed), contents not inspected.
+ * pad_i = (align - (len_i + 2) mod align) mod align with `align` a multiple of 4 in
+ * 4..256, so pad_i <= 255 and P_i = len_i + pad_i + 2 = sg_esp_padded_len(len_i, align).
+ * The padding bytes are 1 .. pad_i (RFC 4303 section 2.4), then u8(pad_i), then the next
+ * header: next_header ? next_header[i] : uniform_next_header.  They are never read from
+ * the input: no input byte at or beyond len_i is read.  The sequence number is seq[i];
+ * without SG_ESP_ESN it is taken mod 2^32 (the high half is ignored, also where it
+ * stands in for the IV).  The IV is iv ? iv[i] : that sequence number; it must never
+ * repeat under one key (RFC 7634 section 2), which a counter gives.  The output is
+ * 32 + P_i bytes: header (spi[k]), ciphertext, ICV.  Status SG_OK, or SG_STATUS_SKIPPED
+ * and nothing written where len_i > max_len.  The bound is on P: sg_esp_packet_len(
+ * max_len or uniform_len, align) is at most SG_ESP_MAX_PACKET_LEN, so no packet of a seal
+ * is longer than that -- a payload bound of SG_ESP_MAX_PACKET_LEN - 34 at align 4 and 16.
+ *
+ * Open.  The input is a packet of len_i bytes.  In this order: len_i > max_len is
+ * SG_STATUS_SKIPPED, len_i < 34 is SG_E_SHORT (no trailer fits), a wire SPI other than
+ * spi[k] is SG_STATUS_BAD_HEADER; nothing is written for any of them (seq_out,
+ * payload_len and next_header_out included).  Otherwise seq_lo and the IV are read off
+ * the wire, under SG_ESP_ESN seq_hi = sg_esp_seq_hi(replay_top[k], window, seq_lo) (RFC
+ * 4303 appendix A2.1: the one 64-bit number with those low bits in [T - W + 1,
+ * T - W + 1 + 2^32), all arithmetic mod 2^32 as in Linux xfrm_replay_seqhi; a wrapped
+ * guess fails its ICV), and n = len_i - 32 bytes are decrypted into `out`: payload,
+ * padding and trailer, left in place.  Bad ICV: SG_E_BAD_MAC, all n output bytes zero,
+ * seq_out[i], payload_len[i] and next_header_out[i] 0; under SG_ESP_KEEP_FAILED the
+ * decryption and the inferred 64-bit sequence number are left instead, payload_len[i]
+ * and next_header_out[i] still 0.  Good ICV: seq_out[i] is the 64-bit sequence number
+ * (zero-extended without ESN), and with payload_len != NULL: pad = out[n - 2], nh =
+ * out[n - 1]; where pad + 2 <= n and the pad bytes are exactly 1 .. pad, payload_len[i] =
+ * n - 2 - pad, next_header_out[i] = nh, SG_OK.  Anything else is SG_STATUS_BAD_INNER with
+ * payload_len[i] and next_header_out[i] 0, the plaintext and seq_out[i] left: the packet
+ * was authentic, and the caller's window advances for it.  With payload_len == NULL
+ * nothing is parsed and a good ICV is SG_OK.  max_len is at most SG_ESP_MAX_PACKET_LEN.
+ *
+ * In place.  Per packet, `in` and `out` either do not overlap or overlap in exactly one
+ * way, the payload staying at its address: seal out_i + 16 == in_i (16 bytes of headroom
+ * in front of the payload, sg_esp_packet_len bytes of room from out_i), open
+ * out_i == in_i + 16.  Any other overlap is undefined and not checked.
+ *
+ * Left with the caller: the lookup from a received SPI to sa_index; the anti-replay
+ * window itself over seq_out and the update of replay_top; sequence number overflow and
+ * rekeying; TFC padding and dummy packets (next header 59); tunnel versus transport
+ * mode, that is what the payload is; UDP encapsulation (RFC 3948); IKE.
+ *
+ * One launch, no workspace, no host read-back: the call is capturable.  count == 0
+ * returns SG_OK and launches nothing.  SG_E_ARG before any GPU work: NULL b, unknown
+ * flags, NULL keys / salts / spi / status / in / out, NULL seq on seal, NULL seq_out on
+ * open, payload_len without next_header_out or the reverse, under SG_ESP_ESN on open a
+ * NULL replay_top or a window outside 1..2^31, a misaligned array (4 bytes for salts,
+ * spi, sa_index, payload_len, len; 8 for seq, iv, seq_out, replay_top, in_off, out_off),
+ * num_sas zero, an align that is no multiple of 4 in 4..256, uniform_next_header above
+ * 255, the length bounds above. */
+#define SG_ESP_HEADER_LEN     16u
+#define SG_ESP_MAX_PACKET_LEN 16384u      /* header and ICV included */
+#define SG_ESP_ESN            0x1u        /* extended sequence numbers: 12-byte AD, seq_hi implicit */
+#define SG_ESP_KEEP_FAILED    0x2u
+
+typedef struct sg_esp_batch {
+    uint32_t        count, flags;
+    const uint8_t*  keys;            /* device [num_sas][32]                                             */
+    const uint8_t*  salts;           /* device [num_sas][4], 4-byte aligned                              */
+    const uint32_t* spi;             /* device [num_sas], values: written and compared big-endian        */
+    const uint32_t* sa_index;        /* device, or NULL: 0                                               */
+    const uint64_t* seq;             /* seal: device, the sequence number of each packet; open: not read */
+    const uint64_t* iv;              /* seal: device, or NULL: the sequence number; open: not read       */
+    const uint8_t*  next_header;     /* seal: device, or NULL: uniform_next_header; open: not read       */
+    uint64_t*       seq_out;         /* open: device, the 64-bit sequence number; seal: not read         */
+    uint32_t*       payload_len;     /* open: device or NULL (above); seal: not read                     */
+    uint8_t*        next_header_out; /* open: device, with payload_len; seal: not read                   */
+    const uint64_t* replay_top;      /* open under SG_ESP_ESN: device [num_sas], T of each SA            */
+    uint32_t        num_sas, align;
+    uint32_t        uniform_next_header, window;
+    const uint8_t*  in;
+    const uint64_t* in_off;
+    uint64_t        in_stride;
+    uint8_t*        out;
+    const uint64_t* out_off;
+    uint64_t        out_stride;
+    const uint32_t* len;
+    uint32_t        uniform_len;
+    uint32_t        max_len;
+    uint8_t*        status;          /* device, count bytes, required for seal and open                  */
+    void*           stream;          /* as sg_batch.stream: non-NULL asynchronous, NULL waits            */
+} sg_esp_batch;                      /* 192 bytes */
+int sg_seal_batch_esp(const sg_esp_batch* b);
+int sg_open_batch_esp(const sg_esp_batch* b);
+
+/* Host only.  sg_esp_padded_len: P of a payload of len bytes (above; an align of 0 is
+ * taken as 1); sg_esp_packet_len: 32 + P, the room a seal needs from out_i.  Both give
+ * 0xffffffff where the result does not fit 32 bits.  sg_esp_seq_hi: what the open kernel
+ * infers per packet from T = top and W = window. */
+uint32_t sg_esp_padded_len(uint32_t len, uint32_t align);
+uint32_t sg_esp_packet_len(uint32_t len, uint32_t align);
+uint32_t sg_esp_seq_hi(uint64_t top, uint32_t window, uint32_t seq_lo);
+
 /* ---- long messages: any data and AD length, one message over the whole chip
  * Encryptor::encrypt / Decryptor::decrypt take data and additional data of any
  * length (cipher/mod.rs:22-32, chacha20_poly1305.rs:19-94).  sg_seal, sg_open

@@ -14,6 +14,8 @@ Layout:
                              AEAD and header protection, seal_quic / open_quic
   suruga_amd/wg.py           WireGuard transport data messages of a device-resident batch:
                              header, zero padding, AEAD and the inner length, seal_wg / open_wg
+  suruga_amd/esp.py          IPsec ESP packets of a device-resident batch (RFC 7634): header, padding
+                             and trailer, AEAD with the ESN additional data, seal_esp / open_esp
   suruga_amd/_native.py      ctypes binding of libsuruga_gpu.so
 
 The HIP library is the only compute path; importing the cipher classes works
@@ -24,6 +26,8 @@ from .cipher import (Aead, ChaCha20Poly1305, ChaCha20Poly1305Decryptor, ChaCha20
                      ChaCha20Poly1305Rfc8439, CipherSuite, Decryptor, Encryptor, TlsError, TlsErrorKind)
 from .keysched import quic_packet_keys
 from .quic import QuicBatch, decode_pn, open_quic, seal_quic
+from .esp import EspBatch, open_esp, seal_esp
+from .esp import packet_len as esp_packet_len, padded_len as esp_padded_len, seq_hi as esp_seq_hi
 from .wg import SG_STATUS_BAD_HEADER, SG_STATUS_BAD_INNER, WgBatch, message_len, open_wg, padded_len, seal_wg
 
 __all__ = [
@@ -31,6 +35,7 @@ __all__ = [
     "CipherSuite", "Decryptor", "Encryptor", "TlsError", "TlsErrorKind", "load_native",
     "QuicBatch", "seal_quic", "open_quic", "decode_pn", "quic_packet_keys",
     "WgBatch", "seal_wg", "open_wg", "padded_len", "message_len", "SG_STATUS_BAD_HEADER", "SG_STATUS_BAD_INNER",
+    "EspBatch", "seal_esp", "open_esp", "esp_padded_len", "esp_packet_len", "esp_seq_hi",
 ]
 
 

@@ -59,6 +59,7 @@ EXPORTS = [
     "sg_msg_batch_plan_for_flags",
     "sg_seal_batch_quic", "sg_open_batch_quic", "sg_quic_decode_pn", "sg_quic_packet_keys",
     "sg_seal_batch_wg", "sg_open_batch_wg", "sg_wg_padded_len", "sg_wg_message_len",
+    "sg_seal_batch_esp", "sg_open_batch_esp", "sg_esp_padded_len", "sg_esp_packet_len", "sg_esp_seq_hi",
 ]
 SG_MSG_BATCH_MAX_COUNT = 1 << 20
 SG_MSG_MAX_GROUPS = 1024
@@ -186,6 +187,47 @@ class SgWgBatch(C.Structure):
         ("inner_len", C.c_void_p),
         ("num_keys", C.c_uint32),
         ("pad_cap", C.c_uint32),
+        ("in_", C.c_void_p),
+        ("in_off", C.c_void_p),
+        ("in_stride", C.c_uint64),
+        ("out", C.c_void_p),
+        ("out_off", C.c_void_p),
+        ("out_stride", C.c_uint64),
+        ("len", C.c_void_p),
+        ("uniform_len", C.c_uint32),
+        ("max_len", C.c_uint32),
+        ("status", C.c_void_p),
+        ("stream", C.c_void_p),
+    ]
+
+
+SG_ESP_HEADER_LEN = 16
+SG_ESP_MAX_PACKET_LEN = 16384
+SG_ESP_ESN = 0x1
+SG_ESP_KEEP_FAILED = 0x2
+
+
+class SgEspBatch(C.Structure):
+    """Mirror of ``struct sg_esp_batch``."""
+
+    _fields_ = [
+        ("count", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("keys", C.c_void_p),
+        ("salts", C.c_void_p),
+        ("spi", C.c_void_p),
+        ("sa_index", C.c_void_p),
+        ("seq", C.c_void_p),
+        ("iv", C.c_void_p),
+        ("next_header", C.c_void_p),
+        ("seq_out", C.c_void_p),
+        ("payload_len", C.c_void_p),
+        ("next_header_out", C.c_void_p),
+        ("replay_top", C.c_void_p),
+        ("num_sas", C.c_uint32),
+        ("align", C.c_uint32),
+        ("uniform_next_header", C.c_uint32),
+        ("window", C.c_uint32),
         ("in_", C.c_void_p),
         ("in_off", C.c_void_p),
         ("in_stride", C.c_uint64),
@@ -472,6 +514,14 @@ def _declare(lib: C.CDLL) -> None:
     for f in (lib.sg_wg_padded_len, lib.sg_wg_message_len):
         f.restype = C.c_uint32
         f.argtypes = [C.c_uint32, C.c_uint32]
+    for f in (lib.sg_seal_batch_esp, lib.sg_open_batch_esp):
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(SgEspBatch)]
+    for f in (lib.sg_esp_padded_len, lib.sg_esp_packet_len):
+        f.restype = C.c_uint32
+        f.argtypes = [C.c_uint32, C.c_uint32]
+    lib.sg_esp_seq_hi.restype = C.c_uint32
+    lib.sg_esp_seq_hi.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
     lib.sg_ctx_set_traffic_secret.restype = C.c_int
     lib.sg_ctx_set_traffic_secret.argtypes = [C.c_void_p, C.c_char_p]
     lib.sg_ctx_key_update.restype = C.c_int
