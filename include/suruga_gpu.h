@@ -636,6 +636,131 @@ uint32_t sg_esp_padded_len(uint32_t len, uint32_t align);
 uint32_t sg_esp_packet_len(uint32_t len, uint32_t align);
 uint32_t sg_esp_seq_hi(uint64_t top, uint32_t window, uint32_t seq_lo);
 
+/* ---- DTLS 1.3 record batch, TLS_CHACHA20_POLY1305_SHA256 (RFC 9147 section 4) ----
+ * Many DTLSCiphertext records sealed or opened in one launch (sg_dtls13.hip).  The record:
+ *
+ *   0 0 1 C S L E E                     first byte: C = 0x10, S = 0x08, L = 0x04, EE = epoch mod 4
+ *   connection ID, cid_len bytes        where C is set
+ *   sequence number, low 8 bits (S = 0) or low 16 bits (S = 1), big-endian
+ *   be16(|encrypted_record|)            where L is set
+ *   encrypted_record = AEAD(key, nonce = iv XOR (00 00 00 00 || be64(seq)),
+ *        plaintext = content || u8(type) || zeros,
+ *        AD = the header above, its sequence number bytes as they are before record
+ *             number encryption)        -> n bytes || 16-byte tag
+ *
+ * hdr_len = sg_dtls13_header_len(flags, cid_len) = 1 + cid_len + (S ? 2 : 1) + (L ? 2 : 0),
+ * 2..255 bytes; a record is hdr_len + n + 16 bytes.  The AEAD is RFC 8439: ChaCha20 blocks
+ * 1 onward, the Poly1305 key from block 0, the MAC over pad16(AD) || ct || pad16 ||
+ * le64(hdr_len) || le64(n).  The nonce takes the 64-bit sequence number alone; the epoch
+ * does not enter it.  Record number encryption (section 4.2.3): sample = the first 16
+ * bytes of encrypted_record (tag bytes among them where n < 16); mask = the first bytes
+ * of the ChaCha20 block under sn_key with counter le32(sample[0..4)) and nonce
+ * sample[4..16); the one or two sequence number bytes are XORed with mask[0..].  The
+ * first byte is not masked.
+ *
+ * Tables.  k = min(key_index ? key_index[i] : 0, num_conns - 1).  Without
+ * SG_DTLS13_EPOCH_ROWS keys, ivs, sn_keys and expected have num_conns rows and the row is
+ * k.  With it they have 4 * num_conns rows and the row is 4 k + EE: unlike QUIC's header
+ * protection key, sn_key changes with the epoch.  EE is epoch ? epoch[i] : uniform_epoch,
+ * mod 4, on seal and the wire's two bits on open.  cids has one row of cid_len bytes per
+ * connection, row k, and is read on seal only.
+ *
+ * Record i lies at in + in_off_i (off_i = off ? off[i] : stride * i) and has len_i =
+ * len ? len[i] : uniform_len bytes, as in sg_quic_batch; any alignment of `in`, `out` and
+ * the offsets.  `in` and `out` of a call must not overlap (not checked; the result is
+ * undefined where they do): there is no in-place form.
+ *
+ * Seal.  The input is the content, len_i bytes (0 allowed), not inspected.  n_i =
+ * sg_dtls13_inner_len(len_i, pad_to): len_i + 1, and where pad_to > 1 that rounded up to
+ * a multiple of pad_to but to at most 2^14 + 1.  The type byte (type ? type[i] :
+ * uniform_type; a zero would read as padding) and the zeros are made by the call: no
+ * input byte at or beyond len_i is read.  SG_DTLS13_SEQ16 and SG_DTLS13_LENGTH choose S
+ * and L for the whole call; C is set where cid_len != 0.  The output is
+ * sg_dtls13_record_len(len_i, pad_to, flags, cid_len) bytes: header, ciphertext, tag,
+ * with the mask applied last.  Status SG_OK, or SG_STATUS_SKIPPED and nothing written
+ * where len_i > max_len.  max_len is at most SG_DTLS13_MAX_CONTENT_LEN.
+ *
+ * Open.  The input is a record of len_i bytes; cid_len is the call's (the caller found
+ * the connection by its CID), S, L and EE are the record's.  In this order, with nothing
+ * written (seq_out, epoch_out, content_len and type_out included): len_i > max_len is
+ * SG_STATUS_SKIPPED; len_i == 0 is SG_E_SHORT; top three bits other than 001, or C
+ * disagreeing with cid_len != 0, is SG_STATUS_BAD_HEADER; len_i < hdr_len + 16 is
+ * SG_E_SHORT; L set and the length field other than len_i - hdr_len is
+ * SG_STATUS_BAD_HEADER.  Otherwise the sequence number bytes are unmasked and the full
+ * number is sg_quic_decode_pn(expected[row], those bits, 1 or 2): expected is the
+ * caller's to keep at the highest deprotected number + 1 of each row, as ESP's
+ * replay_top.  n = len_i - hdr_len - 16 inner bytes are decrypted into `out`;
+ * epoch_out[i] = EE.  Bad tag: SG_E_BAD_MAC, all n output bytes zero, seq_out[i],
+ * content_len[i] and type_out[i] 0; under SG_DTLS13_KEEP_FAILED the decryption and the
+ * decoded number are left instead, content_len[i] and type_out[i] still 0.  Good tag:
+ * seq_out[i] is the number, and the last non-zero inner byte is the type: type_out[i],
+ * content_len[i] = its index, SG_OK; no such byte (or n = 0) is SG_STATUS_NO_TYPE with
+ * both 0.  The inner plaintext is left in `out` either way.  max_len is at most
+ * SG_DTLS13_MAX_RECORD_LEN.
+ *
+ * Left with the caller: the handshake and its messages; ACKs; the replay window over
+ * seq_out and the update of expected; the epoch's upper bits (which of the generations
+ * with these two low bits is meant) and the key tables behind them; the AEAD usage limits
+ * of section 4.5.3; splitting a datagram into records (a record without L ends it) and
+ * the lookup from a CID to key_index.  The AES suites, whose mask is AES-ECB, are not here.
+ *
+ * One launch, no workspace, no host read-back: the call is capturable.  count == 0
+ * returns SG_OK and launches nothing.  SG_E_ARG before any GPU work: NULL b, unknown
+ * flags, NULL keys / ivs / sn_keys / status / in / out, NULL seq on seal, NULL expected /
+ * seq_out / epoch_out / content_len / type_out on open, cids NULL with cid_len != 0 on
+ * seal, a misaligned array (4 bytes for ivs, key_index, content_len, len; 8 for seq,
+ * expected, seq_out, in_off, out_off), num_conns zero, cid_len above
+ * SG_DTLS13_MAX_CID_LEN, pad_to above 2^14, the length bounds above. */
+#define SG_DTLS13_MAX_CONTENT_LEN 16384u
+#define SG_DTLS13_MAX_CID_LEN       250u  /* so that the header (AD) is <= 255 = SG_MAX_AD_LEN */
+#define SG_DTLS13_MAX_RECORD_LEN  (255u + 16384u + 1u + 16u)
+#define SG_DTLS13_SEQ16           0x1u    /* seal: 16-bit sequence number on the wire (S) */
+#define SG_DTLS13_LENGTH          0x2u    /* seal: the length field is present (L) */
+#define SG_DTLS13_EPOCH_ROWS      0x4u    /* four rows per connection, chosen by EE */
+#define SG_DTLS13_KEEP_FAILED     0x8u
+
+typedef struct sg_dtls13_batch {
+    uint32_t        count, flags;
+    const uint8_t*  keys;          /* device [rows][32]                                              */
+    const uint8_t*  ivs;           /* device [rows][12], 4-byte aligned                              */
+    const uint8_t*  sn_keys;       /* device [rows][32]                                              */
+    const uint8_t*  cids;          /* seal: device [num_conns][cid_len], NULL where cid_len is 0; open: not read */
+    const uint32_t* key_index;     /* device, or NULL: 0                                             */
+    const uint64_t* seq;           /* seal: device, the sequence number of each record; open: not read */
+    const uint8_t*  type;          /* seal: device, or NULL: uniform_type; open: not read            */
+    const uint8_t*  epoch;         /* seal: device, or NULL: uniform_epoch; open: not read           */
+    const uint64_t* expected;      /* open: device [rows], highest deprotected number + 1; seal: not read */
+    uint64_t*       seq_out;       /* open: device, the decoded sequence number; seal: not read      */
+    uint8_t*        epoch_out;     /* open: device, EE off the wire; seal: not read                  */
+    uint32_t*       content_len;   /* open: device, the content's length; seal: not read             */
+    uint8_t*        type_out;      /* open: device, the content type; seal: not read                 */
+    uint32_t        num_conns, cid_len;
+    uint32_t        pad_to;        /* seal: 0 or 1 none, else the inner plaintext's multiple         */
+    uint8_t         uniform_type, uniform_epoch;
+    const uint8_t*  in;
+    const uint64_t* in_off;
+    uint64_t        in_stride;
+    uint8_t*        out;
+    const uint64_t* out_off;
+    uint64_t        out_stride;
+    const uint32_t* len;
+    uint32_t        uniform_len;
+    uint32_t        max_len;
+    uint8_t*        status;        /* device, count bytes, required for seal and open                */
+    void*           stream;        /* as sg_batch.stream: non-NULL asynchronous, NULL waits          */
+} sg_dtls13_batch;                 /* 208 bytes */
+int sg_seal_batch_dtls13(const sg_dtls13_batch* b);
+int sg_open_batch_dtls13(const sg_dtls13_batch* b);
+
+/* Host only.  sg_dtls13_header_len: hdr_len of a seal with these flags (the bits other
+ * than SG_DTLS13_SEQ16 and SG_DTLS13_LENGTH are ignored).  sg_dtls13_inner_len: n of a
+ * content of len bytes (above; a len of 2^14 or more is not padded).  sg_dtls13_record_len:
+ * hdr_len + n + 16, the room a seal needs from out_i.  The last two give 0xffffffff where
+ * the result does not fit 32 bits. */
+uint32_t sg_dtls13_header_len(uint32_t flags, uint32_t cid_len);
+uint32_t sg_dtls13_inner_len(uint32_t len, uint32_t pad_to);
+uint32_t sg_dtls13_record_len(uint32_t len, uint32_t pad_to, uint32_t flags, uint32_t cid_len);
+
 /* ---- long messages: any data and AD length, one message over the whole chip
  * Encryptor::encrypt / Decryptor::decrypt take data and additional data of any
  * length (cipher/mod.rs:22-32, chacha20_poly1305.rs:19-94).  sg_seal, sg_open
@@ -1111,6 +1236,18 @@ int sg_tls13_traffic_keys(uint32_t count, uint8_t* secrets, uint8_t* keys, uint8
  * SG_E_ARG.  Host memory; the tables feed sg_quic_batch. */
 int sg_quic_packet_keys(uint32_t count, uint8_t* secrets, uint8_t* keys, uint8_t* ivs, uint8_t* hps, int update,
                         int threads);
+
+/* DTLS 1.3 record protection keys (RFC 9147 section 5.9, 4.2.3) for `count` traffic secrets,
+ * with the shape and rules of the call above.  Expand-Label is RFC 8446's with the label
+ * prefix "dtls13" (no space) where TLS 1.3 has "tls13 ":
+ *   update != 0:  secrets[i] <- Expand-Label(secrets[i], "traffic upd", "", 32)   (in place, first)
+ *   keys[i]    = Expand-Label(secrets[i], "key", "", 32)   [count][32], may be NULL
+ *   ivs[i]     = Expand-Label(secrets[i], "iv",  "", 12)   [count][12], may be NULL
+ *   sn_keys[i] = Expand-Label(secrets[i], "sn",  "", 32)   [count][32], may be NULL
+ * count == 0 is SG_OK; a call that would do nothing is SG_E_ARG.  Host memory; the tables
+ * feed sg_dtls13_batch (under SG_DTLS13_EPOCH_ROWS one secret per connection and epoch). */
+int sg_dtls13_record_keys(uint32_t count, uint8_t* secrets, uint8_t* keys, uint8_t* ivs, uint8_t* sn_keys, int update,
+                          int threads);
 
 /* The same on the device: one launch turns a device table of traffic secrets
  * into the keys / ivs tables of the batch calls, in place in HBM (sg_hkdf.hip:

@@ -16,6 +16,8 @@ Layout:
                              header, zero padding, AEAD and the inner length, seal_wg / open_wg
   suruga_amd/esp.py          IPsec ESP packets of a device-resident batch (RFC 7634): header, padding
                              and trailer, AEAD with the ESN additional data, seal_esp / open_esp
+  suruga_amd/dtls13.py       DTLS 1.3 records of a device-resident batch (RFC 9147): unified header, inner
+                             plaintext, AEAD and record number encryption, seal_dtls13 / open_dtls13
   suruga_amd/_native.py      ctypes binding of libsuruga_gpu.so
 
 The HIP library is the only compute path; importing the cipher classes works
@@ -28,6 +30,9 @@ from .keysched import quic_packet_keys
 from .quic import QuicBatch, decode_pn, open_quic, seal_quic
 from .esp import EspBatch, open_esp, seal_esp
 from .esp import packet_len as esp_packet_len, padded_len as esp_padded_len, seq_hi as esp_seq_hi
+from .dtls13 import Dtls13Batch, open_dtls13, seal_dtls13
+from .dtls13 import header_len as dtls13_header_len, inner_len as dtls13_inner_len
+from .dtls13 import record_keys as dtls13_record_keys, record_len as dtls13_record_len
 from .wg import SG_STATUS_BAD_HEADER, SG_STATUS_BAD_INNER, WgBatch, message_len, open_wg, padded_len, seal_wg
 
 __all__ = [
@@ -36,6 +41,8 @@ __all__ = [
     "QuicBatch", "seal_quic", "open_quic", "decode_pn", "quic_packet_keys",
     "WgBatch", "seal_wg", "open_wg", "padded_len", "message_len", "SG_STATUS_BAD_HEADER", "SG_STATUS_BAD_INNER",
     "EspBatch", "seal_esp", "open_esp", "esp_padded_len", "esp_packet_len", "esp_seq_hi",
+    "Dtls13Batch", "seal_dtls13", "open_dtls13", "dtls13_header_len", "dtls13_inner_len", "dtls13_record_len",
+    "dtls13_record_keys",
 ]
 
 

@@ -30,11 +30,13 @@ HIP_SOURCES = [CSRC / "sg_kernels.hip", CSRC / "sg_wpr.hip", CSRC / "sg_wpr_keyi
                CSRC / "sg_msg_batch.hip", CSRC / "sg_msg_batch_capi.cpp", CSRC / "sg_hkdf.hip",
                CSRC / "sg_quic.hip", CSRC / "sg_quic_capi.cpp", CSRC / "sg_quic_host.cpp",
                CSRC / "sg_wg.hip", CSRC / "sg_wg_capi.cpp", CSRC / "sg_wg_host.cpp",
-               CSRC / "sg_esp.hip", CSRC / "sg_esp_capi.cpp", CSRC / "sg_esp_host.cpp"]
+               CSRC / "sg_esp.hip", CSRC / "sg_esp_capi.cpp", CSRC / "sg_esp_host.cpp",
+               CSRC / "sg_dtls13.hip", CSRC / "sg_dtls13_capi.cpp", CSRC / "sg_dtls13_host.cpp"]
 HIP_DEPS = HIP_SOURCES + [CSRC / "sg_internal.h", CSRC / "sg_device.h", CSRC / "sg_host.h", CSRC / "sg_err.h",
                           CSRC / "sg_wire.h", CSRC / "sg_copy_pool.h", CSRC / "sg_env.h", CSRC / "sg_chacha_grp.inc",
                           CSRC / "sg_msg_plan.h", CSRC / "sg_msg_device.h", CSRC / "sg_layout.h",
                           CSRC / "sg_wpr_layout.h", CSRC / "sg_hkdf.h", CSRC / "sg_quic.h", CSRC / "sg_wg.h", CSRC / "sg_esp.h",
+                          CSRC / "sg_dtls13.h", CSRC / "sg_lane_aead.h",
                           ROOT / "include" / "suruga_gpu.h"]
 ORACLE_SOURCES = [ORACLE_DIR / "suruga_oracle.c"]
 ORACLE_DEPS = ORACLE_SOURCES + [ORACLE_DIR / "suruga_oracle.h", ORACLE_DIR / "so_pool.h"]

@@ -60,6 +60,8 @@ EXPORTS = [
     "sg_seal_batch_quic", "sg_open_batch_quic", "sg_quic_decode_pn", "sg_quic_packet_keys",
     "sg_seal_batch_wg", "sg_open_batch_wg", "sg_wg_padded_len", "sg_wg_message_len",
     "sg_seal_batch_esp", "sg_open_batch_esp", "sg_esp_padded_len", "sg_esp_packet_len", "sg_esp_seq_hi",
+    "sg_seal_batch_dtls13", "sg_open_batch_dtls13", "sg_dtls13_header_len", "sg_dtls13_inner_len", "sg_dtls13_record_len",
+    "sg_dtls13_record_keys",
 ]
 SG_MSG_BATCH_MAX_COUNT = 1 << 20
 SG_MSG_MAX_GROUPS = 1024
@@ -228,6 +230,53 @@ class SgEspBatch(C.Structure):
         ("align", C.c_uint32),
         ("uniform_next_header", C.c_uint32),
         ("window", C.c_uint32),
+        ("in_", C.c_void_p),
+        ("in_off", C.c_void_p),
+        ("in_stride", C.c_uint64),
+        ("out", C.c_void_p),
+        ("out_off", C.c_void_p),
+        ("out_stride", C.c_uint64),
+        ("len", C.c_void_p),
+        ("uniform_len", C.c_uint32),
+        ("max_len", C.c_uint32),
+        ("status", C.c_void_p),
+        ("stream", C.c_void_p),
+    ]
+
+
+SG_DTLS13_MAX_CONTENT_LEN = 16384
+SG_DTLS13_MAX_CID_LEN = 250
+SG_DTLS13_MAX_RECORD_LEN = 255 + 16384 + 1 + 16
+SG_DTLS13_SEQ16 = 0x1
+SG_DTLS13_LENGTH = 0x2
+SG_DTLS13_EPOCH_ROWS = 0x4
+SG_DTLS13_KEEP_FAILED = 0x8
+
+
+class SgDtls13Batch(C.Structure):
+    """Mirror of ``struct sg_dtls13_batch``."""
+
+    _fields_ = [
+        ("count", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("keys", C.c_void_p),
+        ("ivs", C.c_void_p),
+        ("sn_keys", C.c_void_p),
+        ("cids", C.c_void_p),
+        ("key_index", C.c_void_p),
+        ("seq", C.c_void_p),
+        ("type", C.c_void_p),
+        ("epoch", C.c_void_p),
+        ("expected", C.c_void_p),
+        ("seq_out", C.c_void_p),
+        ("epoch_out", C.c_void_p),
+        ("content_len", C.c_void_p),
+        ("type_out", C.c_void_p),
+        ("num_conns", C.c_uint32),
+        ("cid_len", C.c_uint32),
+        ("pad_to", C.c_uint32),
+        ("uniform_type", C.c_uint8),
+        ("uniform_epoch", C.c_uint8),
         ("in_", C.c_void_p),
         ("in_off", C.c_void_p),
         ("in_stride", C.c_uint64),
@@ -522,6 +571,17 @@ def _declare(lib: C.CDLL) -> None:
         f.argtypes = [C.c_uint32, C.c_uint32]
     lib.sg_esp_seq_hi.restype = C.c_uint32
     lib.sg_esp_seq_hi.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
+    for f in (lib.sg_seal_batch_dtls13, lib.sg_open_batch_dtls13):
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(SgDtls13Batch)]
+    lib.sg_dtls13_header_len.restype = C.c_uint32
+    lib.sg_dtls13_header_len.argtypes = [C.c_uint32, C.c_uint32]
+    lib.sg_dtls13_inner_len.restype = C.c_uint32
+    lib.sg_dtls13_inner_len.argtypes = [C.c_uint32, C.c_uint32]
+    lib.sg_dtls13_record_len.restype = C.c_uint32
+    lib.sg_dtls13_record_len.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+    lib.sg_dtls13_record_keys.restype = C.c_int
+    lib.sg_dtls13_record_keys.argtypes = [C.c_uint32, vp, vp, vp, vp, C.c_int, C.c_int]
     lib.sg_ctx_set_traffic_secret.restype = C.c_int
     lib.sg_ctx_set_traffic_secret.argtypes = [C.c_void_p, C.c_char_p]
     lib.sg_ctx_key_update.restype = C.c_int

@@ -81,11 +81,15 @@ constexpr size_t kMaxContext = 255;  // u8(context_len)
 constexpr size_t kMaxInfo = 2 + 1 + 6 + kMaxLabel + 1 + kMaxContext;
 constexpr size_t kMaxOut = 255 * 32;  // RFC 5869 section 2.3
 
-// out <- be16(out_len) || u8(6 + label_len) || "tls13 " || label || u8(context_len) || context;
+// The label prefix, six bytes in either protocol: TLS 1.3's (RFC 8446 section 7.1) and
+// DTLS 1.3's (RFC 9147 section 5.9, no trailing space).
+constexpr char kPrefixTls13[7] = "tls13 ";
+constexpr char kPrefixDtls13[7] = "dtls13";
+
+// out <- be16(out_len) || u8(6 + label_len) || prefix || label || u8(context_len) || context;
 // returns its length (at most kMaxInfo; the bounds are the caller's to check)
 constexpr size_t hkdf_label(uint8_t* out, size_t out_len, const char* label, size_t label_len,
-                            const uint8_t* context, size_t context_len) {
-    constexpr char prefix[7] = "tls13 ";
+                            const uint8_t* context, size_t context_len, const char (&prefix)[7] = kPrefixTls13) {
     size_t n = 0;
     out[n++] = (uint8_t)(out_len >> 8);
     out[n++] = (uint8_t)out_len;

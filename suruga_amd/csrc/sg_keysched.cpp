@@ -377,4 +377,39 @@ int sg_quic_packet_keys(uint32_t count, uint8_t* secrets, uint8_t* keys, uint8_t
     return SG_OK;
 }
 
+int sg_dtls13_record_keys(uint32_t count, uint8_t* secrets, uint8_t* keys, uint8_t* ivs, uint8_t* sn_keys, int update,
+                          int threads) {
+    if (!count) return SG_OK;
+    if (!secrets) return fail(SG_E_ARG, "NULL argument%s");
+    if (!keys && !ivs && !sn_keys && !update) return fail(SG_E_ARG, "nothing to do: no keys, no ivs, no sn_keys and no update%s");
+    // RFC 9147 section 5.9: RFC 8446's Expand-Label with the prefix "dtls13"
+    auto expand = [](const uint8_t* s, const char* label, size_t label_len, uint8_t* out, size_t out_len) {
+        uint8_t info[sg::hkdf::kMaxInfo];
+        const size_t n = sg::hkdf::hkdf_label(info, out_len, label, label_len, nullptr, 0, sg::hkdf::kPrefixDtls13);
+        sg::hkdf_expand(s, info, n, out, out_len);
+    };
+    const uint32_t nt = (uint32_t)std::max(1, std::min<int>(threads, (int)std::min<uint32_t>(count, 1u << 16)));
+    auto work = [&](uint32_t t) {
+        for (uint32_t i = t; i < count; i += nt) {
+            uint8_t* s = secrets + 32ull * i;
+            if (update) {  // RFC 8446 section 7.2: the next generation's secret
+                uint8_t next[32];
+                expand(s, "traffic upd", 11, next, 32);
+                std::memcpy(s, next, 32);
+            }
+            if (keys) expand(s, "key", 3, keys + 32ull * i, 32);
+            if (ivs) expand(s, "iv", 2, ivs + 12ull * i, 12);
+            if (sn_keys) expand(s, "sn", 2, sn_keys + 32ull * i, 32);
+        }
+    };
+    if (nt == 1) {
+        work(0);
+    } else {
+        std::vector<std::thread> pool;
+        for (uint32_t t = 0; t < nt; ++t) pool.emplace_back(work, t);
+        for (auto& th : pool) th.join();
+    }
+    return SG_OK;
+}
+
 }  // extern "C"

@@ -59,7 +59,7 @@ T13_OFF = ", false>("
 # every file of the library that holds a kernel (one that the tree does not have yet is passed over, so
 # that the tool can take the census of an earlier commit)
 SOURCES = [_build.CSRC / f for f in ("sg_wpr.hip", "sg_wpr_keying.hip", "sg_pack.hip", "sg_kernels.hip", "sg_plumb.hip",
-                                     "sg_msg.hip", "sg_msg_batch.hip", "sg_quic.hip", "sg_wg.hip", "sg_esp.hip", "sg_hkdf.hip")
+                                     "sg_msg.hip", "sg_msg_batch.hip", "sg_quic.hip", "sg_wg.hip", "sg_esp.hip", "sg_dtls13.hip", "sg_hkdf.hip")
            if (_build.CSRC / f).exists()]
 
 
